@@ -57,6 +57,8 @@ def parse(argv=None):
                     help="one GPU, with --loopback: run the multi-rank legs (rank check against the unsplit lattice, configs[3], 32^4 / N) as a world of one rank "
                          "exchanging with itself -- the code path the N > 1 run takes, minus the rendezvous")
     ap.add_argument("--opt", action="append", default=[], help="library option name=value (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--loopback", type=int, default=0,
                     help="1-GPU rehearsal of the multi-GPU path: 1 = faces exchanged with self by a D2D copy, 2 = through a one-rank RCCL communicator")
     return ap.parse_args(argv)
@@ -519,6 +521,33 @@ def time_cg(ph, R, lat, P, Q, total_iters, n_short=5, n_long=25):
             "ms_per_solve_setup": 1e3 * (ts / reps - n_short * (tl - ts) / iters)}
 
 
+DUMP_BYTES = 60 * 10 ** 6      # the arrays of --dump-outputs together, over all ranks: with the .npy headers under 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(d, fields, world, rank):
+    """--dump-outputs DIR: the fields a caller of the timed path receives, as float64 DIR/<name>.npy (rank r of N > 1:
+    <name>_rank<r>.npy).  A field larger than its share of DUMP_BYTES is written as a fixed sample of its sites: the same
+    seeded, sorted choice in every run, so that two builds can be compared output for output.  Returns what was written."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // (len(fields) * world)
+    written = {}
+    for name, f in fields:
+        a = f.download()
+        nsites, site_bytes = a.shape[0], a[0].nbytes
+        rec = {"sites": nsites, "shape": list(a.shape)}
+        if a.nbytes > share:
+            k = share // site_bytes
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nsites, size=k, replace=False))
+            a = a[idx]
+            rec.update(sampled_sites=k, sample_seed=DUMP_SEED)
+        fn = name + ("_rank%d" % rank if world > 1 else "")
+        np.save(os.path.join(d, fn + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        written[fn] = rec
+    return written
+
+
 REF_CACHE = {}   # rank 0: the unsplit lattice's results per global T (built once, reused by the second carrier's leg)
 
 
@@ -752,6 +781,11 @@ def rank_main(args, world, rank, local_rank):
         P, Q = box["PQ"]
         cg = time_cg(hl, R, lat, P, Q, args.cg_iters)
         WALL["headline"] = time.perf_counter() - t_hl
+        if args.dump_outputs:
+            # f1 = H_eo f0 and f2 = H_oe f1 of the last timed step; P = the last timed cg_her solve (n_long iterations from P = 0)
+            dumped = hl.step("dump outputs", lambda: dump_outputs(args.dump_outputs, (("hopping_f1", f1), ("hopping_f2", f2),
+                                                                                     ("cg_solution", P)), world, rank))
+            extra["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     except PhaseAbort:
         # the headline itself failed on some rank: still ONE well-formed line (value null, the step and the ranks), non-zero exit
         if rank == 0:

@@ -53,5 +53,10 @@ for n in (0, 1, 7, 288, 576, 1000):
     b = bytes(rng.integers(0, 256, n, dtype=np.uint8))
     assert ib.ref_crc32(b) == (zlib.crc32(b) & 0xffffffff)
     out["crc32_known_answers"].append({"hex": b.hex(), "crc32": "%08x" % ib.ref_crc32(b)})
+# DML_checksum_accum over a seeded record at site ranks inside and outside the 29 / 31 windows (tests/test_ildg_oracle.py)
+rec = np.random.default_rng(4).integers(0, 256, 576 * 70, dtype=np.uint8)
+out["checksum_accum_known_answers"] = {"record": "np.random.default_rng(4).integers(0, 256, 576 * 70, dtype=np.uint8), 70 sites of 576 bytes",
+                                       "sums": [dict(zip(("rank0", "suma", "sumb"), (r0,) + tuple("%08x" % v for v in ib.ref_checksum(rec, 576, r0))))
+                                                for r0 in (0, 29 * 31 - 3, 123456)]}
 json.dump(out, open(os.path.join(ROOT, "tests", "golden", "ildg_checksums.json"), "w"), indent=1)
 print(json.dumps(out["files"], indent=1))

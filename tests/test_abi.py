@@ -135,8 +135,8 @@ def test_c_host_program_links_against_the_drop_in_at_link_time(c_host_program):
 
 def test_register_budget_guard_of_the_build():
     """tools/check_resources.py (a prerequisite of libtmlqcd_hip.so in the Makefile): it must FAIL on a default-dispatch stencil
-    instance that spills or drops below three waves per SIMD, pass on a clean one, and the table the last build committed must
-    say that nothing failed."""
+    instance that spills or drops below three waves per SIMD, pass on a clean one, and both the table of this build
+    (lib/resource_usage.txt) and the one last committed to profiles/ must say that nothing failed."""
     import subprocess
     import sys
     import tempfile
@@ -158,5 +158,6 @@ def test_register_budget_guard_of_the_build():
             open(f, "w").write(text)
             r = subprocess.run([sys.executable, tool, f], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
             assert r.returncode == want, (tag, r.stdout, r.stderr)
-    table = open(os.path.join(ROOT, "profiles", "r04_resource_usage.txt")).read()
-    assert " 0 failing" in table and "hop64::hop_kernel<0, 3, true, 256, 3, -1, 64>" in table
+    for path in (("tmlqcd_amd", "lib", "resource_usage.txt"), ("profiles", "r04_resource_usage.txt")):
+        table = open(os.path.join(ROOT, *path)).read()
+        assert " 0 failing" in table and "hop64::hop_kernel<0, 3, true, 256, 3, -1, 64>" in table, path
