@@ -177,6 +177,24 @@ int mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params solver_p
 int rg_mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params solver_params, const int max_iter,
                     const double eps_sq, const int rel_prec, const int N, matrix_mult f, matrix_mult32 f32);
 
+/* ---- operator/tm_operators_nd.h, solver/cg_her_nd.h, solver/cg_mms_tm_nd.h: the non-degenerate doublet --------
+ * g_mubar, g_epsbar (global.h:202) and phmc_invmaxev (phmc.h:31) are read at every call (weak references: a host program
+ * without them gets 0, 0, 1).  Unsplit lattices only: with g_nproc_t > 1 every symbol below ends the program with a message.
+ * The output pair may be the input pair where the reference allows it (Qtm_pm_ndpsi, M_ee_inv_ndpsi, H_eo_tm_ndpsi,
+ * mul_one_pm_itau2).  The clover doublet and the polynomial helpers (Qsw_*_ndpsi, P_ndpsi, Qtau1_P_ndpsi, ...) are not here. */
+typedef void (*matrix_mult_nd)(spinor *const, spinor *const, spinor *const, spinor *const);   /* solver/matrix_mult_typedef.h:33 */
+void Qtm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);          /* :68-89 */
+void Qtm_dagger_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);   /* :130-152 */
+void Qtm_pm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);       /* :195-238 */
+void M_ee_inv_ndpsi(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c, const double mu, const double eps);  /* :639-696 */
+void H_eo_tm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm, const int ieo);   /* :508-519 */
+void mul_one_pm_itau2(spinor *const p, spinor *const q, spinor *const r, spinor *const s, const double sign, const int N);        /* :582-597 */
+/* solver/cg_her_nd.c:57-160 and solver/cg_mms_tm_nd.c:64-215 run on the device for f / M_ndpsi = Qtm_pm_ndpsi on N = VOLUME/2
+ * sites (up to 32 shifts); anything else ends the program with a message */
+int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *const Q_dn, const int max_iter, double eps_sq,
+              const int rel_prec, const int N, matrix_mult_nd f);
+int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *solver_params);
+
 /* ---- deriv_Sb.h: hopping part of the fermion force -------- */
 typedef struct { double d1, d2, d3, d4, d5, d6, d7, d8; } su3adj;           /* su3adj.h:23-26 */
 typedef struct {                                                             /* hamiltonian_field.h:26-32 */

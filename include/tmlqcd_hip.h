@@ -144,6 +144,31 @@ enum { TMHIP_OP_QTM_PM = 0, TMHIP_OP_QTM_PLUS = 1, TMHIP_OP_QTM_MINUS = 2, TMHIP
 int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec,
                  int N, int op, int *iters, double *res_hist, int hist_len);
 
+/* ---- non-degenerate twisted-mass doublet (operator/tm_operators_nd.c) ------------------------
+ * A doublet is a pair of EO fields (strange = up, charm = dn).  Unsplit lattices only: a context with nproc_t > 1 refuses every
+ * entry point below with a message.  Wilson twisted mass, fp64 (no clover term, no fp32 twins). */
+/* g_mubar, g_epsbar (global.h:202) and phmc_invmaxev (phmc.h:31; default 1), read by the operators and solvers at call time */
+int tmhip_set_nd(tmhip_ctx *ctx, double mubar, double epsbar, double invmaxev);
+/* M_ee_inv_ndpsi(l_s,l_c,k_s,k_c,mu,eps)          tm_operators_nd.c:639-696; l may be k */
+int tmhip_M_ee_inv_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, double mu, double eps);
+/* M_oo_sub_g5_ndpsi(l_s,l_c,k_s,k_c,j_s,j_c,mu,eps)  :698-757; l may be k or j */
+int tmhip_M_oo_sub_g5_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, tmhip_field *j_s,
+                            tmhip_field *j_c, double mu, double eps);
+int tmhip_Qtm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);          /* :68-89 */
+int tmhip_Qtm_dagger_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);   /* :130-152 */
+int tmhip_Qtm_pm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);       /* :195-238; l may be k */
+int tmhip_H_eo_tm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, int ieo);   /* :508-519 */
+/* cg_her_nd(P_up,P_dn,Q_up,Q_dn,max_iter,eps_sq,rel_prec,N,Qtm_pm_ndpsi)   solver/cg_her_nd.c:57-160; *iters = its return value */
+int tmhip_cg_her_nd(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_field *Q_up, tmhip_field *Q_dn, int max_iter, double eps_sq,
+                    int rel_prec, int N, int *iters);
+/* cg_mms_tm_nd(Pup,Pdn,Qup,Qdn,solver_params) with M_ndpsi = Qtm_pm_ndpsi   solver/cg_mms_tm_nd.c:64-215: Pup[s], Pdn[s] solve
+ * (Qtm_pm_ndpsi + shifts[s]^2) P = Q for s = 0 .. nshifts-1 (1 <= nshifts <= 32); the last shift is dropped every 20 iterations once
+ * its correction is below eps_sq (:158-167); *iters = the reference's return value (:208-209) */
+int tmhip_cg_mms_tm_nd(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmhip_field *Qup, tmhip_field *Qdn, const double *shifts,
+                       int nshifts, int max_iter, double eps_sq, int rel_prec, int *iters);
+/* shifts still active at the end of the last tmhip_cg_mms_tm_nd (the reference's local `shifts`, cg_mms_tm_nd.c:68,163) */
+int tmhip_nd_active_shifts(tmhip_ctx *ctx);
+
 /* ---- fermion force, hopping part (deriv_Sb.c:401-700) ------------------------------
  * deriv_Sb(ieo, l, k, hf, factor) accumulates 2 factor trlambda(...) of the one-hop terms into hf->derivative.  Here the
  * accumulator is device-resident: zero it, call tmhip_deriv_Sb any number of times (one call per deriv_Sb call of the
@@ -361,6 +386,8 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *   "cg_fused_dot" 2 (default: alpha / residual / norm in the stencil epilogues), 1 scalar product only, 0 plain linalg kernels
  *   "cg_self" 1 (default) | 0: small unsplit lattices (the hop-split stencil) -- the fused CG iteration adds up its partial sums inside the residual stencil
  *                (alpha) and the (P, p) kernel (stopping test, beta) instead of two one-block sum + scalar kernels in between
+ *   "nd_fused" 1 (default) | 0: the doublet operators (tmhip_*_ndpsi, the nd solvers) -- 1: one stencil per hop for both flavours with the
+ *                flavour mixing in its epilogue; 0: two single-flavour stencils per hop and a mixing pass
  *   "cg_sync" 1: host-side scalars as in the reference loop;  "cg_batch" n: iterations enqueued between two polls of `done`
  *   "gauge_cache" -1 (automatic) / 0 / 1: the 64-thread stencil launches of small unsplit lattices, and the stencil launches of a T-split rank,
  *                  load the links with (0) or without (1) the streaming hint; automatic = without while the gauge copy is <= 200 MB (it then

@@ -155,6 +155,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
     ctx->flag_timeout_ticks = (unsigned long long)(sec * 1.0e8);
   }
   ctx->opt_stg = 1; ctx->opt_stg32 = 0; ctx->opt_hopsplit = -1; ctx->opt_occ32 = 0; ctx->opt_recon = 0; ctx->opt_swall_order = 2; ctx->opt_swterm_order = 1; ctx->opt_gauge_cache = -1;
+  ctx->opt_nd_fused = 1; ctx->invmaxev = 1.0;
   ctx->gauge_recon_dev = -1.0;
   TMHIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   {  // boundary pipeline (pack, exchange, boundary kernels) must not queue behind the interior kernel's blocks
@@ -215,6 +216,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
+  tmhip_nd_destroy(ctx);
   for (int i = 0; i < 3; i++) { tmhip_field_free(ctx, ctx->scratch[i]); tmhip_field_free(ctx, ctx->sf[i]); }
   tmhip_field_free(ctx, ctx->sf_extra);
   for (int i = 0; i < 2; i++) tmhip_field_free(ctx, ctx->scratch32[i]);
@@ -318,6 +320,7 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "lds")) { if (value < 0 || value > 1) TMHIP_FAIL("lds must be 0 (gather kernel) or 1 (per-wave LDS staging of the own-site spinors)"); ctx->opt_stg = value; }
   else if (!strcmp(name, "cg_self")) ctx->opt_cg_self = value != 0;
   else if (!strcmp(name, "cg_sync")) ctx->opt_cg_sync = value;
+  else if (!strcmp(name, "nd_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_fused must be 0 (two single-flavour stencils + a mixing pass) or 1 (doublet stencil)"); ctx->opt_nd_fused = value; }
   else if (!strcmp(name, "cg_batch")) ctx->opt_cg_batch = value > 0 ? value : 1;
   else TMHIP_FAIL("unknown option %s", name);
   return 0;

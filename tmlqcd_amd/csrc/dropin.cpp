@@ -6,6 +6,7 @@
 #include "../../include/tmlqcd_dropin.h"
 #include "../../include/tmlqcd_hip.h"
 
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +38,9 @@ extern double g_mu3 __attribute__((weak));                        /* global.h:19
 extern TM_COMPLEX ka0, ka1, ka2, ka3;                             /* boundary.h:25 */
 extern su3 ***sw __attribute__((weak));                           /* clovertm_operators.c:58 */
 extern su3 ***sw_inv __attribute__((weak));                       /* clovertm_operators.c:59 */
+extern double g_mubar __attribute__((weak));                       /* global.h:202: the doublet's twist ... */
+extern double g_epsbar __attribute__((weak));                      /* ... and its flavour splitting */
+extern double phmc_invmaxev __attribute__((weak));                 /* phmc.h:31 */
 extern double mixcg_innereps __attribute__((weak));               /* read_input.h:112 (only needed by mixed_cg_her) */
 extern int mixcg_maxinnersolverit __attribute__((weak));          /* read_input.h:113 */
 // Present in a full tmLQCD link (update_backward_gauge.c, libhmc.a); refreshes the HOST gauge
@@ -879,6 +883,57 @@ void Qtm_plus_psi_nocom(spinor *const l, spinor *const k) { Qtm_plus_psi(l, k); 
 void Mtm_plus_psi_nocom(spinor *const l, spinor *const k) { Mtm_plus_psi(l, k); }
 void Qtm_pm_psi_nocom(spinor *const l, spinor *const k) { Qtm_pm_psi(l, k); }
 
+// ------------------------------------------------------------------ non-degenerate doublet (tm_operators_nd.c)
+static tmhip_ctx *refresh_nd(const char *who) {
+  if (g_nproc_t > 1) {
+    char m[160];
+    snprintf(m, sizeof(m), "%s: the doublet operators and solvers run on unsplit lattices only", who);
+    die(m);
+  }
+  tmhip_ctx *c = refresh(true);
+  CK(tmhip_set_nd(c, &g_mubar ? g_mubar : 0., &g_epsbar ? g_epsbar : 0., &phmc_invmaxev ? phmc_invmaxev : 1.));
+  return c;
+}
+#define ND_OP(NAME, CORE)                                                                                           \
+  void NAME(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c) {                           \
+    tmhip_ctx *c = refresh_nd(#NAME);                                                                               \
+    tmhip_field *fks = in(c, k_s, TMHIP_FIELD_EO), *fkc = in(c, k_c, TMHIP_FIELD_EO);                               \
+    tmhip_field *fls = out(c, l_s, TMHIP_FIELD_EO), *flc = out(c, l_c, TMHIP_FIELD_EO);                             \
+    CK(CORE(c, fls, flc, fks, fkc));                                                                                \
+    done(c, l_s); done(c, l_c);                                                                                     \
+  }
+ND_OP(Qtm_ndpsi, tmhip_Qtm_ndpsi)                /* tm_operators_nd.c:68-89 */
+ND_OP(Qtm_dagger_ndpsi, tmhip_Qtm_dagger_ndpsi)  /* :130-152 */
+ND_OP(Qtm_pm_ndpsi, tmhip_Qtm_pm_ndpsi)          /* :195-238 */
+void M_ee_inv_ndpsi(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c, const double mu, const double eps) {   /* :639-696 */
+  tmhip_ctx *c = refresh_nd("M_ee_inv_ndpsi");
+  tmhip_field *fks = in(c, k_s, TMHIP_FIELD_EO), *fkc = in(c, k_c, TMHIP_FIELD_EO);
+  tmhip_field *fls = out(c, l_s, TMHIP_FIELD_EO), *flc = out(c, l_c, TMHIP_FIELD_EO);
+  CK(tmhip_M_ee_inv_ndpsi(c, fls, flc, fks, fkc, mu, eps));
+  done(c, l_s); done(c, l_c);
+}
+void H_eo_tm_ndpsi(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c, const int ieo) {   /* :508-519 */
+  tmhip_ctx *c = refresh_nd("H_eo_tm_ndpsi");
+  tmhip_field *fks = in(c, k_s, TMHIP_FIELD_EO), *fkc = in(c, k_c, TMHIP_FIELD_EO);
+  tmhip_field *fls = out(c, l_s, TMHIP_FIELD_EO), *flc = out(c, l_c, TMHIP_FIELD_EO);
+  CK(tmhip_H_eo_tm_ndpsi(c, fls, flc, fks, fkc, ieo));
+  done(c, l_s); done(c, l_c);
+}
+/* :582-597, the same sequence of add / diff / mul_r (so p or q may be r or s exactly as in the reference) */
+void mul_one_pm_itau2(spinor *const p, spinor *const q, spinor *const r, spinor *const s, const double sign, const int N) {
+  tmhip_ctx *c = refresh(false);
+  if (N == 0) return;
+  if (N < 0 || N > VOLUME / 2) die("mul_one_pm_itau2: N must be in [0, VOLUME/2]");
+  tmhip_field *fr = in(c, r, TMHIP_FIELD_EO, N), *fs = in(c, s, TMHIP_FIELD_EO, N);
+  tmhip_field *fp = out(c, p, TMHIP_FIELD_EO, N), *fq = out(c, q, TMHIP_FIELD_EO, N);
+  const double fac = 1. / sqrt(2.);
+  if (sign > 0) { CK(tmhip_add(c, fp, fr, fs, N)); CK(tmhip_diff(c, fq, fs, fr, N)); }
+  else { CK(tmhip_diff(c, fp, fr, fs, N)); CK(tmhip_add(c, fq, fr, fs, N)); }
+  CK(tmhip_mul_r(c, fp, fac, fp, N));
+  CK(tmhip_mul_r(c, fq, fac, fq, N));
+  done(c, p); done(c, q);
+}
+
 /* tm_operators.c:508-526 */
 void H_eo_tm_inv_psi(spinor *const l, spinor *const k, const int ieo, const double sign) {
   tmhip_ctx *c = refresh(true);
@@ -1500,6 +1555,33 @@ int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, 
 /* solver/mixed_cg_her.c:65-202 with f = Qtm_pm_psi: fp32 inner CG + fp64 defect correction, all in HBM */
 static_assert(sizeof(tmlqcd_solver_params) == 144 && offsetof(tmlqcd_solver_params, mcg_delta) == 52,
               "solver_params_t layout (solver/solver_params.h:46-109)");
+/* solver/cg_her_nd.c:57-160 with f = Qtm_pm_ndpsi, device-resident */
+int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *const Q_dn, const int max_iter, double eps_sq,
+              const int rel_prec, const int N, matrix_mult_nd f) {
+  if (f != &Qtm_pm_ndpsi || N != VOLUME / 2) die("cg_her_nd: only f = Qtm_pm_ndpsi on VOLUME/2 sites runs on the device");
+  tmhip_ctx *c = refresh_nd("cg_her_nd");
+  tmhip_field *fqu = in(c, Q_up, TMHIP_FIELD_EO), *fqd = in(c, Q_dn, TMHIP_FIELD_EO);
+  tmhip_field *fpu = in(c, P_up, TMHIP_FIELD_EO), *fpd = in(c, P_dn, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_cg_her_nd(c, fpu, fpd, fqu, fqd, max_iter, eps_sq, rel_prec, N, &iters));
+  done(c, P_up); done(c, P_dn);
+  return iters;
+}
+/* solver/cg_mms_tm_nd.c:64-215 with M_ndpsi = Qtm_pm_ndpsi, device-resident */
+int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *sp) {
+  if (sp->M_ndpsi != &Qtm_pm_ndpsi || sp->sdim != VOLUME / 2) die("cg_mms_tm_nd: only M_ndpsi = Qtm_pm_ndpsi on VOLUME/2 sites runs on the device");
+  const int n = sp->no_shifts;
+  if (n < 1 || n > 32) die("cg_mms_tm_nd: no_shifts must be in [1, 32]");
+  tmhip_ctx *c = refresh_nd("cg_mms_tm_nd");
+  tmhip_field *fqu = in(c, Qup, TMHIP_FIELD_EO), *fqd = in(c, Qdn, TMHIP_FIELD_EO);
+  tmhip_field *fu[32], *fd[32];
+  for (int s = 0; s < n; s++) { fu[s] = out(c, Pup[s], TMHIP_FIELD_EO); fd[s] = out(c, Pdn[s], TMHIP_FIELD_EO); }
+  int iters = -1;
+  CK(tmhip_cg_mms_tm_nd(c, fu, fd, fqu, fqd, sp->shifts, n, sp->max_iter, sp->squared_solver_prec, sp->rel_prec, &iters));
+  for (int s = 0; s < n; s++) { done(c, Pup[s]); done(c, Pdn[s]); }
+  return iters;
+}
+
 int mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params, const int max_iter, double eps_sq,
                  const int rel_prec, const int N, matrix_mult f, matrix_mult32) {
   if ((f != &Qtm_pm_psi && f != &Qsw_pm_psi) || N != VOLUME / 2) die("mixed_cg_her: only f = Qtm_pm_psi / Qsw_pm_psi on VOLUME/2 sites runs on the device");

@@ -1,0 +1,650 @@
+// The non-degenerate twisted-mass doublet (operator/tm_operators_nd.c, solver/cg_her_nd.c, solver/cg_mms_tm_nd.c) on the device.
+//
+// A doublet is a pair of one-parity fields (strange = up, charm = dn).  Every composition of tm_operators_nd.c is a
+// hop of BOTH flavours followed by a site-local mixing of the two:
+//   M_ee_inv_ndpsi     (:639-696)  l_s = nrm [(1 -+ i mu) k_s + eps k_c],  l_c = nrm [(1 +- i mu) k_c + eps k_s],  nrm = 1/(1 + mu^2 - eps^2)
+//   M_oo_sub_g5_ndpsi  (:698-757)  the same mixing without nrm, minus j on spins 0, 1 and j minus it on spins 2, 3
+// (upper sign: spins 0, 1).  nd_hop_kernel does both flavours of a site in one thread: each of the eight links is loaded ONCE
+// and applied to the two projected half-spinors, and the mixing runs in the epilogue on the two accumulators, so a
+// Qtm_pm_ndpsi is four launches and nothing else.  The flavour swaps the reference writes as argument orders (tau_1) are
+// pointer choices here.  Option "nd_fused" 0 builds the same operator from two single-flavour stencil launches (EPI_STORE)
+// per hop plus one mixing pass (nd_mix_kernel) -- the A/B of DESIGN.md section 4.
+//
+// The solvers share one device-resident engine (nd_solve): the coefficients of the multi-shift recurrences
+// (cg_mms_tm_nd.c:116-194) live in NdState and are updated by one-block kernels, the field updates read them from there,
+// and the host polls `done` at batch boundaries only.  cg_her_nd is the one-shift, sigma = 0 case with its own start
+// (P != 0 allowed) and return convention.
+#include "hopping_common.h"
+
+namespace {
+TMHIP_SCALAR_COMPLEX_OPS(v2d, double)
+TMHIP_SPINOR_IO_PLANES
+
+__device__ __forceinline__ v2d cfma(v2d a, v2d b, v2d c) {   // c + a*b
+  const v2d t = __builtin_elementwise_fma(v2d{a.x, a.x}, b, c);
+  return __builtin_elementwise_fma(v2d{-a.y, a.y}, v2d{b.y, b.x}, t);
+}
+__device__ __forceinline__ v2d cfmac(v2d a, v2d b, v2d c) {  // c + conj(a)*b
+  const v2d t = __builtin_elementwise_fma(v2d{a.x, a.x}, b, c);
+  return __builtin_elementwise_fma(v2d{a.y, -a.y}, v2d{b.y, b.x}, t);
+}
+__device__ __forceinline__ v2d cmul(v2d a, v2d b) { return __builtin_elementwise_fma(v2d{-a.y, a.y}, v2d{b.y, b.x}, v2d{a.x, a.x} * b); }
+__device__ __forceinline__ v2d cmulc(v2d a, v2d b) { return __builtin_elementwise_fma(v2d{a.y, -a.y}, v2d{b.y, b.x}, v2d{a.x, a.x} * b); }
+
+enum { ND_EE_INV = 0, ND_OO = 1, ND_OO_DOT = 2 };
+
+struct NdArgs {
+  v2d *out_s, *out_c;
+  const v2d *in_a, *in_b;     // stencil: accumulator a is gathered from in_a, b from in_b; nd_mix_kernel: a, b are read at the site
+  const v2d *k_s, *k_c;       // ND_OO*: the local pair that is mixed (a, b are then j_s, j_c)
+  const v2d *p_s, *p_c;       // ND_OO_DOT: out += sigma p, partial sums of <p, out> over both flavours
+  double *partials;           // ND_OO_DOT: one per wave (stencil) / per block (mix kernel)
+  const v2d *gauge;           // already offset to the parity of the output sites
+  int ns, gs, T, LX, LY, LZh, Vh, face, YZh, par_off;
+  int nxcd_chunk, map_nb;     // > 0: blocks b, b+8, .. share an XCD and take a contiguous chunk of the lattice
+  double ka[4][2];
+  double mu, eps, nrm, scale, sigma;
+};
+
+// projection (1 -+ gamma_mu) of one spinor for hop D = 2 mu + (0: +mu, 1: -mu); the same lines as hop_dir (hopping_impl.inc)
+template <int D>
+__device__ __forceinline__ void nd_project(const v2d (&s)[12], v2d (&pa)[3], v2d (&pb)[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const v2d s0 = s[c], s1 = s[3 + c], s2 = s[6 + c], s3 = s[9 + c];
+    if (D == 0) { pa[c] = s0 + s2; pb[c] = s1 + s3; }
+    if (D == 1) { pa[c] = s0 - s2; pb[c] = s1 - s3; }
+    if (D == 2) { pa[c] = v2d{s0.x - s3.y, s0.y + s3.x}; pb[c] = v2d{s1.x - s2.y, s1.y + s2.x}; }
+    if (D == 3) { pa[c] = v2d{s0.x + s3.y, s0.y - s3.x}; pb[c] = v2d{s1.x + s2.y, s1.y - s2.x}; }
+    if (D == 4) { pa[c] = s0 + s3; pb[c] = s1 - s2; }
+    if (D == 5) { pa[c] = s0 - s3; pb[c] = s1 + s2; }
+    if (D == 6) { pa[c] = v2d{s0.x - s2.y, s0.y + s2.x}; pb[c] = v2d{s1.x + s3.y, s1.y - s3.x}; }
+    if (D == 7) { pa[c] = v2d{s0.x + s2.y, s0.y - s2.x}; pb[c] = v2d{s1.x - s3.y, s1.y + s3.x}; }
+  }
+}
+
+// link times half-spinor, ka, and the reconstruction into the accumulator
+template <int D>
+__device__ __forceinline__ void nd_apply(v2d (&acc)[12], const v2d (&u)[9], const v2d (&pa)[3], const v2d (&pb)[3], v2d ka) {
+  v2d ca[3], cb[3];
+  if ((D & 1) == 0) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      ca[r] = cfma(u[3 * r + 2], pa[2], cfma(u[3 * r + 1], pa[1], cmul(u[3 * r], pa[0])));
+      cb[r] = cfma(u[3 * r + 2], pb[2], cfma(u[3 * r + 1], pb[1], cmul(u[3 * r], pb[0])));
+    }
+#pragma unroll
+    for (int r = 0; r < 3; r++) { ca[r] = cmul(ka, ca[r]); cb[r] = cmul(ka, cb[r]); }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      ca[r] = cfmac(u[6 + r], pa[2], cfmac(u[3 + r], pa[1], cmulc(u[r], pa[0])));
+      cb[r] = cfmac(u[6 + r], pb[2], cfmac(u[3 + r], pb[1], cmulc(u[r], pb[0])));
+    }
+#pragma unroll
+    for (int r = 0; r < 3; r++) { ca[r] = cmulc(ka, ca[r]); cb[r] = cmulc(ka, cb[r]); }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const v2d a = ca[c], b = cb[c];
+    acc[c] += a;
+    acc[3 + c] += b;
+    if (D == 0) { acc[6 + c] += a; acc[9 + c] += b; }
+    if (D == 1) { acc[6 + c] -= a; acc[9 + c] -= b; }
+    if (D == 2) { acc[9 + c] += v2d{a.y, -a.x}; acc[6 + c] += v2d{b.y, -b.x}; }
+    if (D == 3) { acc[9 + c] += v2d{-a.y, a.x}; acc[6 + c] += v2d{-b.y, b.x}; }
+    if (D == 4) { acc[9 + c] += a; acc[6 + c] -= b; }
+    if (D == 5) { acc[9 + c] -= a; acc[6 + c] += b; }
+    if (D == 6) { acc[6 + c] += v2d{a.y, -a.x}; acc[9 + c] += v2d{-b.y, b.x}; }
+    if (D == 7) { acc[6 + c] += v2d{-a.y, a.x}; acc[9 + c] += v2d{b.y, -b.x}; }
+  }
+}
+
+// one hop of both flavours: the link is read once
+template <int D, bool NT>
+__device__ __forceinline__ void nd_hop_dir(v2d (&aa)[12], v2d (&ab)[12], const v2d *__restrict__ ia, const v2d *__restrict__ ib, size_t ns, int j,
+                                           const v2d *__restrict__ g, size_t gs, int i, v2d ka) {
+  v2d u[9];
+  const v2d *gd = g + (size_t)D * 9 * gs + i;
+#pragma unroll
+  for (int e = 0; e < 9; e++) u[e] = ldc<NT>(gd + (size_t)e * gs);
+  v2d s[12], pa[3], pb[3];
+  ld6<false>(s, ia, ns, j, 0); ld6<false>(s + 6, ia, ns, j, 1);
+  nd_project<D>(s, pa, pb);
+  nd_apply<D>(aa, u, pa, pb, ka);
+  ld6<false>(s, ib, ns, j, 0); ld6<false>(s + 6, ib, ns, j, 1);
+  nd_project<D>(s, pa, pb);
+  nd_apply<D>(ab, u, pa, pb, ka);
+}
+
+// The site-local mixing of both flavours, on a (= strange slot) and b (= charm slot), and the stores; returns this site's
+// share of <p, out> (ND_OO_DOT).  Written once for the fused stencil and for the mixing pass of the two-stencil form.
+template <int EPI>
+__device__ __forceinline__ double nd_epilogue(const NdArgs &a, int i, const v2d (&va)[12], const v2d (&vb)[12]) {
+  const size_t ns = (size_t)a.ns;
+  const double mu = a.mu, eps = a.eps;
+  double d = 0.0;
+#pragma unroll
+  for (int b = 0; b < 2; b++) {       // spins 0, 1 | spins 2, 3
+    const v2d zs = v2d{1.0, b == 0 ? -mu : mu}, zc = v2d{1.0, b == 0 ? mu : -mu};
+    v2d ks[6], kc[6], os[6], oc[6];
+    if (EPI == ND_EE_INV) {
+#pragma unroll
+      for (int c = 0; c < 6; c++) { ks[c] = va[6 * b + c]; kc[c] = vb[6 * b + c]; }
+    } else {
+      ld6<false>(ks, a.k_s, ns, i, b); ld6<false>(kc, a.k_c, ns, i, b);
+    }
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      const v2d phi1 = cmul(zs, ks[c]) + eps * kc[c];   // _complex_times_vector + _vector_add_mul
+      const v2d phi2 = cmul(zc, kc[c]) + eps * ks[c];
+      if (EPI == ND_EE_INV) {
+        os[c] = a.nrm * phi1; oc[c] = a.nrm * phi2;
+      } else {
+        const v2d js = va[6 * b + c], jc = vb[6 * b + c];
+        os[c] = a.scale * (b == 0 ? phi1 - js : js - phi1);   // then mul_r(l, phmc_invmaxev, ..)
+        oc[c] = a.scale * (b == 0 ? phi2 - jc : jc - phi2);
+      }
+    }
+    if (EPI == ND_OO_DOT) {           // the shifted operator of cg_mms_tm_nd.c:120-124 and its (p, A p) over both flavours
+      v2d ps[6], pc[6];
+      ld6<false>(ps, a.p_s, ns, i, b); ld6<false>(pc, a.p_c, ns, i, b);
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+        os[c] = os[c] + a.sigma * ps[c];
+        oc[c] = oc[c] + a.sigma * pc[c];
+        d += cdotd(ps[c], os[c]) + cdotd(pc[c], oc[c]);
+      }
+    }
+    st6<false>(a.out_s, ns, i, b, os);
+    st6<false>(a.out_c, ns, i, b, oc);
+  }
+  return d;
+}
+
+__device__ __forceinline__ void nd_wave_partial(double d, double *partials, int slot) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
+  if ((threadIdx.x & 63) == 0) partials[slot] = d;
+}
+
+// One thread per output site, both flavours.  Every thread reaches the end (inactive ones with d = 0), so the reducing form
+// writes one partial per wave of the grid, padding blocks included: the sum never depends on the block order.
+template <int EPI, int BS, bool NT>
+__global__ __launch_bounds__(BS) void nd_hop_kernel(const NdArgs a) {
+  int bid = blockIdx.x;
+  if (a.nxcd_chunk > 0) bid = (bid & 7) * a.nxcd_chunk + (bid >> 3);
+  const int i = bid * BS + (int)threadIdx.x;
+  double d = 0.0;
+  if (bid < a.map_nb && i < a.Vh) {
+    const int LZh = a.LZh;
+    const int k = i % LZh;
+    int r = i / LZh;
+    const int y = r % a.LY;
+    r /= a.LY;
+    const int x = r % a.LX;
+    const int t = r / a.LX;
+    const int o = (t + x + y + a.par_off) & 1;   // z = 2k + o  (geometry_eo.c:807-811)
+    const int XYZh = a.face, YZh = a.YZh;
+    const int jtp = (t + 1 < a.T) ? i + XYZh : i - (a.T - 1) * XYZh;
+    const int jtm = (t > 0) ? i - XYZh : i + (a.T - 1) * XYZh;
+    const int jxp = (x + 1 < a.LX) ? i + YZh : i - (a.LX - 1) * YZh;
+    const int jxm = (x > 0) ? i - YZh : i + (a.LX - 1) * YZh;
+    const int jyp = (y + 1 < a.LY) ? i + LZh : i - (a.LY - 1) * LZh;
+    const int jym = (y > 0) ? i - LZh : i + (a.LY - 1) * LZh;
+    const int jzp = o ? ((k + 1 < LZh) ? i + 1 : i - (LZh - 1)) : i;
+    const int jzm = o ? i : ((k > 0) ? i - 1 : i + (LZh - 1));
+    v2d aa[12], ab[12];
+#pragma unroll
+    for (int c = 0; c < 12; c++) { aa[c] = czero(); ab[c] = czero(); }
+    const v2d ka0 = cbcast(a.ka[0][0], a.ka[0][1]), ka1 = cbcast(a.ka[1][0], a.ka[1][1]);
+    const v2d ka2 = cbcast(a.ka[2][0], a.ka[2][1]), ka3 = cbcast(a.ka[3][0], a.ka[3][1]);
+    const size_t ns = (size_t)a.ns, gs = (size_t)a.gs;
+    nd_hop_dir<0, NT>(aa, ab, a.in_a, a.in_b, ns, jtp, a.gauge, gs, i, ka0);
+    nd_hop_dir<1, NT>(aa, ab, a.in_a, a.in_b, ns, jtm, a.gauge, gs, i, ka0);
+    nd_hop_dir<2, NT>(aa, ab, a.in_a, a.in_b, ns, jxp, a.gauge, gs, i, ka1);
+    nd_hop_dir<3, NT>(aa, ab, a.in_a, a.in_b, ns, jxm, a.gauge, gs, i, ka1);
+    nd_hop_dir<4, NT>(aa, ab, a.in_a, a.in_b, ns, jyp, a.gauge, gs, i, ka2);
+    nd_hop_dir<5, NT>(aa, ab, a.in_a, a.in_b, ns, jym, a.gauge, gs, i, ka2);
+    nd_hop_dir<6, NT>(aa, ab, a.in_a, a.in_b, ns, jzp, a.gauge, gs, i, ka3);
+    nd_hop_dir<7, NT>(aa, ab, a.in_a, a.in_b, ns, jzm, a.gauge, gs, i, ka3);
+    d = nd_epilogue<EPI>(a, i, aa, ab);
+  }
+  if (EPI == ND_OO_DOT) nd_wave_partial(d, a.partials, blockIdx.x * (BS / 64) + (int)(threadIdx.x >> 6));
+}
+
+// The mixing alone, a and b read at the site: the standalone M_ee_inv_ndpsi / M_oo_sub_g5_ndpsi and the second half of the
+// two-stencil form.  One partial per wave as above.
+template <int EPI>
+__global__ __launch_bounds__(256) void nd_mix_kernel(const NdArgs a, int N) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  double d = 0.0;
+  if (i < N) {
+    v2d va[12], vb[12];
+    const size_t ns = (size_t)a.ns;
+    ld6<false>(va, a.in_a, ns, i, 0); ld6<false>(va + 6, a.in_a, ns, i, 1);
+    ld6<false>(vb, a.in_b, ns, i, 0); ld6<false>(vb + 6, a.in_b, ns, i, 1);
+    d = nd_epilogue<EPI>(a, i, va, vb);
+  }
+  if (EPI == ND_OO_DOT) nd_wave_partial(d, a.partials, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+}
+
+// ---------------------------------------------------------------- solver state and kernels
+#define ND_MAX_SHIFTS 32
+struct NdState {
+  double normsq, err, target, eps_sq;                  // eps_sq: the absolute threshold of the shift drop (cg_mms_tm_nd.c:162)
+  int it, done, conv, active, max_iter, pad;
+  double sigma[ND_MAX_SHIFTS], zita[ND_MAX_SHIFTS], zitam1[ND_MAX_SHIFTS], alphas[ND_MAX_SHIFTS], betas[ND_MAX_SHIFTS];
+};
+
+// fixed-order sum of n partials by one block of 256 threads (every thread gets the total)
+__device__ __forceinline__ double nd_block_sum(const double *__restrict__ v, int n) {
+  __shared__ double ws[4];
+  double acc = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) acc += v[j];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
+// alphas[0] = normsq / pro and the zita / alphas recurrences of the shifts still active (cg_mms_tm_nd.c:126-146)
+__global__ __launch_bounds__(256) void nd_alpha_kernel(NdState *st, const double *partials, int n) {
+  const double pro = nd_block_sum(partials, n);
+  if (threadIdx.x != 0 || st->done) return;
+  const double alpham1 = st->alphas[0];
+  const double a0 = st->normsq / pro;
+  st->alphas[0] = a0;
+  const double b0 = st->betas[0];
+  for (int im = 1; im < st->active; im++) {
+    const double gamma = st->zita[im] * alpham1 / (a0 * b0 * (1. - st->zita[im] / st->zitam1[im]) + alpham1 * (1. + st->sigma[im] * a0));
+    st->zitam1[im] = st->zita[im];
+    st->zita[im] = gamma;
+    st->alphas[im] = a0 * st->zita[im] / st->zitam1[im];
+  }
+}
+
+// field table of the shifts: tab[4 s + 0 / 1] = P_up[s] / P_dn[s], tab[4 s + 2 / 3] = ps_up[s] / ps_dn[s] (shift 0: the x and p of the CG)
+// blockIdx.y = s.  s = 0: x += alphas[0] p, r -= alphas[0] A p, partials of |r|^2 (cg_mms_tm_nd.c:170-180);
+// s >= 1 (active): P[s] += alphas[s] ps[s] (:149-150), and on a check iteration the last active shift adds up |ps|^2 (:158-160)
+__global__ __launch_bounds__(256) void nd_x_kernel(NdState *st, v2d *const *tab, v2d *r_up, v2d *r_dn, const v2d *ap_up, const v2d *ap_dn,
+                                                   int ns, int N, double *part_r, double *part_sn, int check) {
+  const int s = blockIdx.y;
+  if (st->done || s >= st->active) return;   // block-uniform
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  const double al = st->alphas[s];
+  v2d *xu = tab[4 * s], *xd = tab[4 * s + 1];
+  const v2d *pu = tab[4 * s + 2], *pd = tab[4 * s + 3];
+  double d = 0.0;
+  const bool sn = check && s >= 1 && s == st->active - 1;
+  if (i < N) {
+#pragma unroll 4
+    for (int c = 0; c < 12; c++) {
+      const size_t o = (size_t)c * ns + i;
+      const v2d a = pu[o], b = pd[o];
+      xu[o] = xu[o] + al * a;
+      xd[o] = xd[o] + al * b;
+      if (s == 0) {
+        const v2d ru = r_up[o] + (-al) * ap_up[o], rd = r_dn[o] + (-al) * ap_dn[o];
+        r_up[o] = ru; r_dn[o] = rd;
+        d += cdotd(ru, ru) + cdotd(rd, rd);
+      } else if (sn) {
+        d += cdotd(a, a) + cdotd(b, b);
+      }
+    }
+  }
+  if (s == 0) nd_wave_partial(d, part_r, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+  else if (sn) nd_wave_partial(d, part_sn, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+}
+
+// shift drop (cg_mms_tm_nd.c:158-167), stopping test (:186-190), betas (:195-201)
+__global__ __launch_bounds__(256) void nd_beta_kernel(NdState *st, const double *part_r, const double *part_sn, int n, int check) {
+  const double err = nd_block_sum(part_r, n);
+  __syncthreads();
+  const double sn = check ? nd_block_sum(part_sn, n) : 0.0;
+  if (threadIdx.x != 0 || st->done) return;
+  if (check && st->active > 1) {
+    const double al = st->alphas[st->active - 1];
+    if (al * al * sn <= st->eps_sq) st->active -= 1;
+  }
+  st->err = err;
+  st->it += 1;
+  if (err <= st->target) { st->done = 1; st->conv = 1; return; }
+  if (st->it >= st->max_iter) { st->done = 1; return; }
+  const double b0 = err / st->normsq;
+  st->betas[0] = b0;
+  st->normsq = err;
+  for (int im = 1; im < st->active; im++) st->betas[im] = b0 * st->zita[im] * st->alphas[im] / (st->zitam1[im] * st->alphas[0]);
+}
+
+// p = beta p + r (s = 0, :193-194), ps[s] = betas[s] ps[s] + zita[s] r (:199-200)
+__global__ __launch_bounds__(256) void nd_p_kernel(const NdState *st, v2d *const *tab, const v2d *r_up, const v2d *r_dn, int ns, int N) {
+  const int s = blockIdx.y;
+  if (st->done || s >= st->active) return;
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= N) return;
+  const double be = st->betas[s], ze = s ? st->zita[s] : 1.0;
+  v2d *pu = tab[4 * s + 2], *pd = tab[4 * s + 3];
+#pragma unroll 4
+  for (int c = 0; c < 12; c++) {
+    const size_t o = (size_t)c * ns + i;
+    if (s == 0) { pu[o] = be * pu[o] + r_up[o]; pd[o] = be * pd[o] + r_dn[o]; }
+    else { pu[o] = be * pu[o] + ze * r_up[o]; pd[o] = be * pd[o] + ze * r_dn[o]; }
+  }
+}
+}  // namespace
+
+// ---------------------------------------------------------------- host side
+struct TmhipNd {
+  tmhip_field *s[6];           // operator scratch: [0, 1] EE outputs, [2, 3] first OO output of Qtm_pm_ndpsi, [4, 5] single-flavour hops (two-stencil form)
+  tmhip_field *w[6];           // solver: r_up, r_dn, p_up, p_dn, Ap_up, Ap_dn
+  tmhip_field *ps[2 * ND_MAX_SHIFTS];   // shifted directions (allocated as needed)
+  int nps;
+  double *partials; int max_partials;   // [3][max_partials]: pro, |r|^2, |ps|^2
+  NdState *st;
+  v2d **tab;
+};
+
+void tmhip_nd_destroy(tmhip_ctx *ctx) {
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  if (!n) return;
+  for (int k = 0; k < 6; k++) { tmhip_field_free(ctx, n->s[k]); tmhip_field_free(ctx, n->w[k]); }
+  for (int k = 0; k < n->nps; k++) tmhip_field_free(ctx, n->ps[k]);
+  if (n->partials) (void)hipFree(n->partials);
+  if (n->st) (void)hipFree(n->st);
+  if (n->tab) (void)hipFree(n->tab);
+  delete n;
+  ctx->nd = nullptr;
+}
+
+static int nd_prepare(tmhip_ctx *ctx, const char *who) {
+  if (ctx->g.nproc_t > 1) TMHIP_FAIL("%s: the doublet operators and solvers run on unsplit lattices only (nproc_t = %d)", who, ctx->g.nproc_t);
+  if (!ctx->gauge_set) TMHIP_FAIL("%s called before tmhip_set_gauge", who);
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (ctx->nd) return 0;
+  TmhipNd *n = new TmhipNd();
+  ctx->nd = n;
+  for (int k = 0; k < 6; k++)
+    if (tmhip_field_alloc(ctx, TMHIP_FIELD_EO, &n->s[k]) || tmhip_field_alloc(ctx, TMHIP_FIELD_EO, &n->w[k])) return 1;
+  // stencil: one partial per wave of the padded grid (64-thread blocks, rounded up to a multiple of 8); mix / x kernels: 4 per block
+  n->max_partials = ctx->Vh / 64 + 64;
+  TMHIP_CHECK(hipMalloc((void **)&n->partials, (size_t)3 * n->max_partials * sizeof(double)));
+  TMHIP_CHECK(hipMalloc((void **)&n->st, sizeof(NdState)));
+  TMHIP_CHECK(hipMalloc((void **)&n->tab, (size_t)4 * ND_MAX_SHIFTS * sizeof(v2d *)));
+  return 0;
+}
+
+static bool nd_eo(const tmhip_field *f) { return f && f->kind == TMHIP_FIELD_EO && f->prec == 0; }
+
+static void nd_fill(NdArgs &a, tmhip_ctx *ctx, int ieo) {
+  memset(&a, 0, sizeof(a));
+  a.gauge = ctx->gauge + (size_t)(ieo ? 1 : 0) * 72 * ctx->gs;
+  a.ns = ctx->ns; a.gs = ctx->gs;
+  a.T = ctx->g.T; a.LX = ctx->g.LX; a.LY = ctx->g.LY; a.LZh = ctx->g.LZ / 2;
+  a.Vh = ctx->Vh; a.face = ctx->face; a.YZh = ctx->g.LY * ctx->g.LZ / 2;
+  a.par_off = ieo & 1;
+  for (int m = 0; m < 4; m++) { a.ka[m][0] = ctx->ka[m][0]; a.ka[m][1] = ctx->ka[m][1]; }
+  a.scale = 1.0;
+}
+
+template <int EPI, int BS>
+static void nd_launch_hop(tmhip_ctx *ctx, NdArgs a, int *npart) {
+  int nb = (ctx->Vh + BS - 1) / BS;
+  a.map_nb = nb;
+  if (ctx->opt_xcd && nb >= 64) { a.nxcd_chunk = (nb + 7) / 8; nb = 8 * a.nxcd_chunk; }
+  // the links stay in the Infinity Cache between calls while the gauge copy is small (the rule of hop_kernel's GAUX = -2)
+  const bool cached = ctx->opt_gauge_cache < 0 ? (size_t)2 * 72 * ctx->gs * sizeof(v2d) <= (size_t)200 << 20 : ctx->opt_gauge_cache != 0;
+  if (cached) hipLaunchKernelGGL((nd_hop_kernel<EPI, BS, false>), dim3(nb), dim3(BS), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((nd_hop_kernel<EPI, BS, true>), dim3(nb), dim3(BS), 0, ctx->stream, a);
+  if (npart) *npart = nb * (BS / 64);
+}
+
+template <int EPI>
+static void nd_launch_mix(tmhip_ctx *ctx, const NdArgs &a, int N, int *npart) {
+  const int nb = (N + 255) / 256;
+  hipLaunchKernelGGL((nd_mix_kernel<EPI>), dim3(nb), dim3(256), 0, ctx->stream, a, N);
+  if (npart) *npart = 4 * nb;
+}
+
+// One hop of a doublet + its mixing epilogue.  out = (out_s, out_c); the accumulators a / b gather in_a / in_b of the other parity.
+// ND_EE_INV: mix(a, b; mu, eps) * nrm.  ND_OO[_DOT]: scale * [mix(k_s, k_c; mu, eps) -/+ (a, b)] (+ sigma p, partials of <p, out>).
+static int nd_stage(tmhip_ctx *ctx, int epi, int ieo, v2d *out_s, v2d *out_c, const v2d *in_a, const v2d *in_b, const v2d *k_s,
+                    const v2d *k_c, double mu, double eps, double scale, const v2d *p_s = nullptr, const v2d *p_c = nullptr,
+                    double sigma = 0.0, int *npart = nullptr) {
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  NdArgs a;
+  nd_fill(a, ctx, ieo);
+  a.out_s = out_s; a.out_c = out_c; a.k_s = k_s; a.k_c = k_c; a.p_s = p_s; a.p_c = p_c;
+  a.mu = mu; a.eps = eps; a.nrm = 1. / (1. + mu * mu - eps * eps); a.scale = scale; a.sigma = sigma;
+  a.partials = n->partials;
+  if (ctx->opt_nd_fused) {
+    a.in_a = in_a; a.in_b = in_b;
+    const bool b64 = tmhip_hop_block(ctx) == 64;
+    if (b64 && ctx->Vh / 64 + 8 > n->max_partials) TMHIP_FAIL("nd: partials buffer too small");
+#define ND_HOP(E) (b64 ? nd_launch_hop<E, 64>(ctx, a, npart) : nd_launch_hop<E, 256>(ctx, a, npart))
+    if (epi == ND_EE_INV) ND_HOP(ND_EE_INV);
+    else if (epi == ND_OO) ND_HOP(ND_OO);
+    else ND_HOP(ND_OO_DOT);
+#undef ND_HOP
+  } else {
+    v2d *ha = n->s[4]->d, *hb = n->s[5]->d;
+    if (tmhip_launch_hopping(ctx, ieo, ha, in_a, nullptr, EPI_STORE, 0, 0, HOP_COMM)) return 1;
+    if (tmhip_launch_hopping(ctx, ieo, hb, in_b, nullptr, EPI_STORE, 0, 0, HOP_COMM)) return 1;
+    a.in_a = ha; a.in_b = hb;
+    if (epi == ND_EE_INV) nd_launch_mix<ND_EE_INV>(ctx, a, ctx->Vh, npart);
+    else if (epi == ND_OO) nd_launch_mix<ND_OO>(ctx, a, ctx->Vh, npart);
+    else nd_launch_mix<ND_OO_DOT>(ctx, a, ctx->Vh, npart);
+  }
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Qtm_pm_ndpsi (tm_operators_nd.c:195-238): four stages.  l may alias k (the reference allows it): k is last read in stage 2.
+static int nd_qpm(tmhip_ctx *ctx, v2d *l_s, v2d *l_c, const v2d *k_s, const v2d *k_c, double scale2,
+                  const v2d *p_s = nullptr, const v2d *p_c = nullptr, double sigma = 0.0, int *npart = nullptr) {
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  const double mb = ctx->mubar, eb = ctx->epsbar;
+  v2d *d0 = n->s[0]->d, *d1 = n->s[1]->d, *e0 = n->s[2]->d, *e1 = n->s[3]->d;
+  // M_ee_inv(D2, D3; H k_c, H k_s; mubar, eps)                         -- k_charm feeds the first EO hop
+  if (nd_stage(ctx, ND_EE_INV, TMHIP_EO, d0, d1, k_c, k_s, nullptr, nullptr, mb, eb, 1.0)) return 1;
+  // M_oo_sub_g5(D2', D3'; k_c, k_s; H D2, H D3; -mubar, -eps)
+  if (nd_stage(ctx, ND_OO, TMHIP_OE, e0, e1, d0, d1, k_c, k_s, -mb, -eb, 1.0)) return 1;
+  // M_ee_inv(D5, D4; H D2', H D3'; -mubar, eps)
+  if (nd_stage(ctx, ND_EE_INV, TMHIP_EO, d1, d0, e0, e1, nullptr, nullptr, -mb, eb, 1.0)) return 1;
+  // l = invmaxev^2 M_oo_sub_g5(D3', D2'; H D4, H D5; -mubar, -eps)
+  return nd_stage(ctx, p_s ? ND_OO_DOT : ND_OO, TMHIP_OE, l_s, l_c, d0, d1, e1, e0, -mb, -eb, scale2, p_s, p_c, sigma, npart);
+}
+
+static int nd_check4(tmhip_ctx *ctx, const char *who, tmhip_field *a, tmhip_field *b, tmhip_field *c, tmhip_field *d) {
+  if (nd_prepare(ctx, who)) return 1;
+  if (!nd_eo(a) || !nd_eo(b) || !nd_eo(c) || !nd_eo(d)) TMHIP_FAIL("%s needs four fp64 one-parity (EO) fields", who);
+  if (a->d == b->d) TMHIP_FAIL("%s: the two output flavours must be different fields", who);
+  return 0;
+}
+
+// ---------------------------------------------------------------- solver engine
+// Solves (Qtm_pm_ndpsi + sigma_s) x_s = Q for s = 0 .. nsh-1 (cg_mms_tm_nd.c:64-215; nsh = 1, sigma = 0: cg_her_nd.c:57-160).
+// x_up / x_dn: nsh solution pairs; her: x holds the start vector on entry.  Returns the iteration count the reference returns.
+static int nd_solve(tmhip_ctx *ctx, bool her, tmhip_field **x_up, tmhip_field **x_dn, tmhip_field *q_up, tmhip_field *q_dn,
+                    const double *shifts, int nsh, int max_iter, double eps_sq, int rel_prec, int *iters) {
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  const int N = ctx->Vh;
+  const double s2 = ctx->invmaxev * ctx->invmaxev;
+  tmhip_field *r_up = n->w[0], *r_dn = n->w[1], *p_up = n->w[2], *p_dn = n->w[3], *ap_up = n->w[4], *ap_dn = n->w[5];
+  for (; n->nps < 2 * (nsh - 1); n->nps++)
+    if (tmhip_field_alloc(ctx, TMHIP_FIELD_EO, &n->ps[n->nps])) return 1;
+  NdState h;
+  memset(&h, 0, sizeof(h));
+  double qa, qb;
+  if (tmhip_square_norm(ctx, q_up, N, 0, &qa) || tmhip_square_norm(ctx, q_dn, N, 0, &qb)) return 1;
+  const double squarenorm = qa + qb;
+  if (her) {
+    double pa, pb;
+    if (tmhip_square_norm(ctx, x_up[0], N, 0, &pa) || tmhip_square_norm(ctx, x_dn[0], N, 0, &pb)) return 1;
+    if (pa + pb == 0) {   // cg_her_nd.c:83-91
+      if (tmhip_assign(ctx, r_up, q_up, N) || tmhip_assign(ctx, r_dn, q_dn, N)) return 1;
+      h.normsq = squarenorm;
+    } else {              // :93-104
+      if (nd_qpm(ctx, ap_up->d, ap_dn->d, x_up[0]->d, x_dn[0]->d, s2)) return 1;
+      if (tmhip_diff(ctx, r_up, q_up, ap_up, N) || tmhip_diff(ctx, r_dn, q_dn, ap_dn, N)) return 1;
+      if (tmhip_square_norm(ctx, r_up, N, 0, &pa) || tmhip_square_norm(ctx, r_dn, N, 0, &pb)) return 1;
+      h.normsq = pa + pb;
+    }
+    h.target = rel_prec == 0 ? eps_sq : (rel_prec == 1 ? eps_sq * squarenorm : -1.0);   // :108: rel_prec other than 0 / 1 never converges
+    h.sigma[0] = 0.0;
+  } else {
+    if (tmhip_assign(ctx, r_up, q_up, N) || tmhip_assign(ctx, r_dn, q_dn, N)) return 1;
+    for (int s = 0; s < nsh; s++)
+      if (tmhip_field_zero(ctx, x_up[s]) || tmhip_field_zero(ctx, x_dn[s])) return 1;
+    h.sigma[0] = shifts[0] * shifts[0];
+    for (int s = 1; s < nsh; s++) {
+      h.sigma[s] = shifts[s] * shifts[s] - h.sigma[0];
+      h.zita[s] = h.zitam1[s] = h.alphas[s] = 1.0;
+      if (tmhip_assign(ctx, n->ps[2 * s - 2], q_up, N) || tmhip_assign(ctx, n->ps[2 * s - 1], q_dn, N)) return 1;
+    }
+    h.normsq = squarenorm;
+    h.target = rel_prec > 0 ? eps_sq * squarenorm : eps_sq;
+  }
+  if (tmhip_assign(ctx, p_up, r_up, N) || tmhip_assign(ctx, p_dn, r_dn, N)) return 1;
+  h.alphas[0] = 1.0; h.betas[0] = 0.0;
+  h.eps_sq = eps_sq; h.active = nsh; h.max_iter = max_iter;
+  v2d *tab[4 * ND_MAX_SHIFTS];
+  tab[0] = x_up[0]->d; tab[1] = x_dn[0]->d; tab[2] = p_up->d; tab[3] = p_dn->d;
+  for (int s = 1; s < nsh; s++) { tab[4 * s] = x_up[s]->d; tab[4 * s + 1] = x_dn[s]->d; tab[4 * s + 2] = n->ps[2 * s - 2]->d; tab[4 * s + 3] = n->ps[2 * s - 1]->d; }
+  TMHIP_CHECK(hipMemcpyAsync(n->tab, tab, sizeof(v2d *) * 4 * nsh, hipMemcpyHostToDevice, ctx->stream));
+  TMHIP_CHECK(hipMemcpyAsync(n->st, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
+  const int nbl = (N + 255) / 256;
+  double *pa = n->partials, *pr = n->partials + n->max_partials, *psn = n->partials + 2 * n->max_partials;
+  if (4 * nbl > n->max_partials) TMHIP_FAIL("nd: partials buffer too small");
+  const int batch = ctx->opt_cg_batch > 0 ? ctx->opt_cg_batch : 4;
+  int *flag = (int *)(ctx->result_host + 2);
+  double *err_host = ctx->result_host + 3;
+  int enq = 0, done = 0;
+  bool near = false;
+  while (enq < max_iter && !done) {
+    const int want = near ? 1 : batch;
+    const int nb = (max_iter - enq) < want ? (max_iter - enq) : want;
+    for (int b = 0; b < nb; b++) {
+      const int iteration = enq + b;
+      const int check = !her && nsh > 1 && iteration > 0 && iteration % 20 == 0;
+      int np = 0;
+      if (nd_qpm(ctx, ap_up->d, ap_dn->d, p_up->d, p_dn->d, s2, p_up->d, p_dn->d, h.sigma[0], &np)) return 1;
+      hipLaunchKernelGGL(nd_alpha_kernel, dim3(1), dim3(256), 0, ctx->stream, n->st, (const double *)pa, np);
+      hipLaunchKernelGGL(nd_x_kernel, dim3(nbl, nsh), dim3(256), 0, ctx->stream, n->st, (v2d *const *)n->tab, r_up->d, r_dn->d,
+                         (const v2d *)ap_up->d, (const v2d *)ap_dn->d, ctx->ns, N, pr, psn, check);
+      hipLaunchKernelGGL(nd_beta_kernel, dim3(1), dim3(256), 0, ctx->stream, n->st, (const double *)pr, (const double *)psn, 4 * nbl, check);
+      hipLaunchKernelGGL(nd_p_kernel, dim3(nbl, nsh), dim3(256), 0, ctx->stream, (const NdState *)n->st, (v2d *const *)n->tab,
+                         (const v2d *)r_up->d, (const v2d *)r_dn->d, ctx->ns, N);
+    }
+    enq += nb;
+    TMHIP_CHECK(hipGetLastError());
+    TMHIP_CHECK(hipMemcpyAsync(flag, &n->st->done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    TMHIP_CHECK(hipMemcpyAsync(err_host, &n->st->err, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    done = *flag;
+    near = *err_host <= 1.0e3 * (h.target > 0 ? h.target : eps_sq);
+  }
+  TMHIP_CHECK(hipMemcpyAsync(&h, n->st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ctx->nd_active_shifts = h.active;
+  if (her) *iters = h.conv ? h.it : -1;                 // cg_her_nd.c:115,159
+  else *iters = h.it >= max_iter ? -1 : h.it;           // cg_mms_tm_nd.c:208-209
+  return 0;
+}
+
+extern "C" {
+
+int tmhip_set_nd(tmhip_ctx *ctx, double mubar, double epsbar, double invmaxev) {
+  ctx->mubar = mubar; ctx->epsbar = epsbar; ctx->invmaxev = invmaxev;
+  return 0;
+}
+
+int tmhip_M_ee_inv_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, double mu, double eps) {
+  if (nd_check4(ctx, "M_ee_inv_ndpsi", l_s, l_c, k_s, k_c)) return 1;
+  NdArgs a;
+  nd_fill(a, ctx, 0);
+  a.out_s = l_s->d; a.out_c = l_c->d; a.in_a = k_s->d; a.in_b = k_c->d;
+  a.mu = mu; a.eps = eps; a.nrm = 1. / (1. + mu * mu - eps * eps);
+  nd_launch_mix<ND_EE_INV>(ctx, a, ctx->Vh, nullptr);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_M_oo_sub_g5_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, tmhip_field *j_s,
+                            tmhip_field *j_c, double mu, double eps) {
+  if (nd_check4(ctx, "M_oo_sub_g5_ndpsi", l_s, l_c, k_s, k_c)) return 1;
+  if (!nd_eo(j_s) || !nd_eo(j_c)) TMHIP_FAIL("M_oo_sub_g5_ndpsi needs fp64 one-parity (EO) fields");
+  NdArgs a;
+  nd_fill(a, ctx, 0);
+  a.out_s = l_s->d; a.out_c = l_c->d; a.in_a = j_s->d; a.in_b = j_c->d; a.k_s = k_s->d; a.k_c = k_c->d;
+  a.mu = mu; a.eps = eps;
+  nd_launch_mix<ND_OO>(ctx, a, ctx->Vh, nullptr);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_Qtm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c) {
+  if (nd_check4(ctx, "Qtm_ndpsi", l_s, l_c, k_s, k_c)) return 1;
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  const double mb = ctx->mubar, eb = ctx->epsbar;
+  v2d *d0 = n->s[0]->d, *d1 = n->s[1]->d;
+  // M_ee_inv(D3, D2; H k_s, H k_c; mubar, eps) ; l = invmaxev M_oo_sub_g5(k_s, k_c; H D3, H D2; -mubar, -eps)   (:68-89)
+  if (nd_stage(ctx, ND_EE_INV, TMHIP_EO, d1, d0, k_s->d, k_c->d, nullptr, nullptr, mb, eb, 1.0)) return 1;
+  return nd_stage(ctx, ND_OO, TMHIP_OE, l_s->d, l_c->d, d1, d0, k_s->d, k_c->d, -mb, -eb, ctx->invmaxev);
+}
+
+int tmhip_Qtm_dagger_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c) {
+  if (nd_check4(ctx, "Qtm_dagger_ndpsi", l_s, l_c, k_s, k_c)) return 1;
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  const double mb = ctx->mubar, eb = ctx->epsbar;
+  v2d *d0 = n->s[0]->d, *d1 = n->s[1]->d;
+  // M_ee_inv(D2, D3; H k_c, H k_s; mubar, eps) ; l = invmaxev M_oo_sub_g5(k_s, k_c; j = (H D3, H D2); mubar, -eps)   (:130-152)
+  if (nd_stage(ctx, ND_EE_INV, TMHIP_EO, d0, d1, k_c->d, k_s->d, nullptr, nullptr, mb, eb, 1.0)) return 1;
+  return nd_stage(ctx, ND_OO, TMHIP_OE, l_s->d, l_c->d, d1, d0, k_s->d, k_c->d, mb, -eb, ctx->invmaxev);
+}
+
+int tmhip_Qtm_pm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c) {
+  if (nd_check4(ctx, "Qtm_pm_ndpsi", l_s, l_c, k_s, k_c)) return 1;
+  return nd_qpm(ctx, l_s->d, l_c->d, k_s->d, k_c->d, ctx->invmaxev * ctx->invmaxev);
+}
+
+int tmhip_H_eo_tm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, int ieo) {
+  if (nd_check4(ctx, "H_eo_tm_ndpsi", l_s, l_c, k_s, k_c)) return 1;
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  // M_ee_inv(l_c, l_s; H k_s, H k_c; -mubar, eps)   (:508-519): the result lands as (l_charm, l_strange)
+  const bool alias = l_s->d == k_s->d || l_s->d == k_c->d || l_c->d == k_s->d || l_c->d == k_c->d;
+  v2d *o_c = alias ? n->s[0]->d : l_c->d, *o_s = alias ? n->s[1]->d : l_s->d;
+  if (nd_stage(ctx, ND_EE_INV, ieo, o_c, o_s, k_s->d, k_c->d, nullptr, nullptr, -ctx->mubar, ctx->epsbar, 1.0)) return 1;
+  if (alias) {   // the reference hops into scratch first, so l may be k
+    TMHIP_CHECK(hipMemcpyAsync(l_c->d, o_c, (size_t)12 * ctx->ns * sizeof(v2d), hipMemcpyDeviceToDevice, ctx->stream));
+    TMHIP_CHECK(hipMemcpyAsync(l_s->d, o_s, (size_t)12 * ctx->ns * sizeof(v2d), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  return 0;
+}
+
+int tmhip_cg_her_nd(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_field *Q_up, tmhip_field *Q_dn, int max_iter, double eps_sq,
+                    int rel_prec, int N, int *iters) {
+  if (nd_check4(ctx, "cg_her_nd", P_up, P_dn, Q_up, Q_dn)) return 1;
+  if (N != ctx->Vh) TMHIP_FAIL("cg_her_nd: N must be VOLUME/2");
+  if (max_iter < 0) TMHIP_FAIL("cg_her_nd: max_iter < 0");
+  if (max_iter == 0) { *iters = -1; return 0; }
+  return nd_solve(ctx, true, &P_up, &P_dn, Q_up, Q_dn, nullptr, 1, max_iter, eps_sq, rel_prec, iters);
+}
+
+int tmhip_cg_mms_tm_nd(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmhip_field *Qup, tmhip_field *Qdn, const double *shifts,
+                       int nshifts, int max_iter, double eps_sq, int rel_prec, int *iters) {
+  if (nshifts < 1 || nshifts > ND_MAX_SHIFTS) TMHIP_FAIL("cg_mms_tm_nd: nshifts = %d is outside [1, %d]", nshifts, ND_MAX_SHIFTS);
+  if (!Pup || !Pdn || !shifts) TMHIP_FAIL("cg_mms_tm_nd: null argument");
+  if (nd_check4(ctx, "cg_mms_tm_nd", Pup[0], Pdn[0], Qup, Qdn)) return 1;
+  for (int s = 0; s < nshifts; s++) {
+    if (!nd_eo(Pup[s]) || !nd_eo(Pdn[s])) TMHIP_FAIL("cg_mms_tm_nd needs fp64 one-parity (EO) solution fields");
+    if (Pup[s]->d == Qup->d || Pup[s]->d == Qdn->d || Pdn[s]->d == Qup->d || Pdn[s]->d == Qdn->d) TMHIP_FAIL("cg_mms_tm_nd: a solution field is the source");
+  }
+  if (max_iter < 1) TMHIP_FAIL("cg_mms_tm_nd: max_iter < 1");
+  return nd_solve(ctx, false, Pup, Pdn, Qup, Qdn, shifts, nshifts, max_iter, eps_sq, rel_prec, iters);
+}
+
+int tmhip_nd_active_shifts(tmhip_ctx *ctx) { return ctx->nd_active_shifts; }
+
+}  // extern "C"

@@ -162,6 +162,10 @@ struct tmhip_ctx {
   int opt_cg_sync, opt_cg_batch, opt_cg_fused_dot, opt_cg_self;         // cg_her
   int opt_swall_order;                                                  // block order of the owner-computes sw_all: 0 one contiguous chunk per XCD, 1 slab order, 2 tile order (default; 4 / 8: x-planes per tile)
   int opt_swterm_order;                                                 // block order of sw_term: 0 one contiguous chunk per XCD, 1 (default) tiles walked through all time-slices
+  int opt_nd_fused;                                                     // 1 (default): doublet stencil with fused mixing (nd.hip); 0: two single-flavour stencils + a mixing pass
+  // non-degenerate doublet (nd.hip): g_mubar, g_epsbar (global.h:202), phmc_invmaxev (phmc.h:31); work fields and solver state
+  double mubar, epsbar, invmaxev;
+  void *nd; int nd_active_shifts;
   double gauge_recon_dev;   // max |U_row2 - conj(row0 x row1)| over all links of the resident gauge field (-1: not measured)
 };
 
@@ -275,6 +279,7 @@ int tmhip_prepare_fp32(tmhip_ctx *ctx);
 int tmhip_exchange_gauge_halo(tmhip_ctx *ctx);   // md_update.hip: t = 0 / T-1 slices of the resident links -> the ring neighbours' halo slabs
 int tmhip_resort_gauge(tmhip_ctx *ctx);   // md_update.hip: stencil gauge copy from the device-resident lexicographic links
 int tmhip_prepare_clover32(tmhip_ctx *ctx);  // fp32 gauge copy + fp32 scratch / solver fields
+void tmhip_nd_destroy(tmhip_ctx *ctx);   // nd.hip: work fields and state of the doublet
 // launch geometry shared by linalg.hip and cg.hip
 #define LA_BS 256
 #define LA_UNROLL 4

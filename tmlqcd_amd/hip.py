@@ -149,6 +149,15 @@ def load_library():
         "tmhip_event_record": [vp, i],
         "tmhip_event_elapsed_ms": [vp, i, i, pd],
         "tmhip_set_option": [vp, C.c_char_p, i],
+        "tmhip_set_nd": [vp, d, d, d],
+        "tmhip_M_ee_inv_ndpsi": [vp, vp, vp, vp, vp, d, d],
+        "tmhip_M_oo_sub_g5_ndpsi": [vp, vp, vp, vp, vp, vp, vp, d, d],
+        "tmhip_Qtm_ndpsi": [vp, vp, vp, vp, vp], "tmhip_Qtm_dagger_ndpsi": [vp, vp, vp, vp, vp],
+        "tmhip_Qtm_pm_ndpsi": [vp, vp, vp, vp, vp],
+        "tmhip_H_eo_tm_ndpsi": [vp, vp, vp, vp, vp, i],
+        "tmhip_cg_her_nd": [vp, vp, vp, vp, vp, i, d, i, i, C.POINTER(i)],
+        "tmhip_cg_mms_tm_nd": [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, i, d, i, C.POINTER(i)],
+        "tmhip_nd_active_shifts": [vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -604,6 +613,52 @@ class Lattice:
                                   hist.ctypes.data_as(C.POINTER(C.c_double)), hist.size), "cg_her")
         n = it.value if it.value > 0 else max_iter
         return it.value, hist[:n]
+
+    # --- non-degenerate doublet (operator/tm_operators_nd.c; strange = up = first field of a pair) ---
+    def set_nd(self, mubar, epsbar, invmaxev=1.0):
+        """g_mubar, g_epsbar (global.h:202) and phmc_invmaxev (phmc.h:31)."""
+        _ck(self.lib.tmhip_set_nd(self.h, mubar, epsbar, invmaxev), "tmhip_set_nd")
+
+    def M_ee_inv_ndpsi(self, l_s, l_c, k_s, k_c, mu, eps):
+        _ck(self.lib.tmhip_M_ee_inv_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h, mu, eps), "M_ee_inv_ndpsi")
+
+    def M_oo_sub_g5_ndpsi(self, l_s, l_c, k_s, k_c, j_s, j_c, mu, eps):
+        _ck(self.lib.tmhip_M_oo_sub_g5_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h, j_s.h, j_c.h, mu, eps), "M_oo_sub_g5_ndpsi")
+
+    def Qtm_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_Qtm_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Qtm_ndpsi")
+
+    def Qtm_dagger_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_Qtm_dagger_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Qtm_dagger_ndpsi")
+
+    def Qtm_pm_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_Qtm_pm_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Qtm_pm_ndpsi")
+
+    def H_eo_tm_ndpsi(self, l_s, l_c, k_s, k_c, ieo):
+        _ck(self.lib.tmhip_H_eo_tm_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h, ieo), "H_eo_tm_ndpsi")
+
+    def cg_her_nd(self, P_up, P_dn, Q_up, Q_dn, max_iter, eps_sq, rel_prec, N):
+        """solver/cg_her_nd.c with f = Qtm_pm_ndpsi; returns the reference's return value (iterations or -1)."""
+        it = C.c_int()
+        _ck(self.lib.tmhip_cg_her_nd(self.h, P_up.h, P_dn.h, Q_up.h, Q_dn.h, max_iter, eps_sq, rel_prec, N, C.byref(it)), "cg_her_nd")
+        return it.value
+
+    def cg_mms_tm_nd(self, Q_up, Q_dn, shifts, max_iter, eps_sq, rel_prec, P=None):
+        """solver/cg_mms_tm_nd.c with M_ndpsi = Qtm_pm_ndpsi: (iterations, [(Pup_i, Pdn_i) ...]), one pair per shift; P: pairs to
+        reuse as the solution fields (allocated otherwise).  Shifts still active at the end: nd_active_shifts()."""
+        n = len(shifts)
+        if P is None:
+            P = [(self.field(), self.field()) for _ in range(n)]
+        vp = C.c_void_p
+        up = (vp * n)(*[p[0].h for p in P])
+        dn = (vp * n)(*[p[1].h for p in P])
+        sh = (C.c_double * n)(*shifts)
+        it = C.c_int()
+        _ck(self.lib.tmhip_cg_mms_tm_nd(self.h, up, dn, Q_up.h, Q_dn.h, sh, n, max_iter, eps_sq, rel_prec, C.byref(it)), "cg_mms_tm_nd")
+        return it.value, P
+
+    def nd_active_shifts(self):
+        return self.lib.tmhip_nd_active_shifts(self.h)
 
     # --- multi-GPU --------------------------------------------------------
     def comm_unique_id(self):
