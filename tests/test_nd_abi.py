@@ -2,8 +2,8 @@
 
 * every tmhip_*nd* entry point is exported by libtmlqcd_hip.so, every reference-named doublet symbol is declared in
   include/tmlqcd_dropin.h and exported by libtmlqcd_dropin.so;
-* tests/golden/ref_nd_4x4.npz is self-consistent: a NumPy restatement of M_ee_inv_ndpsi / M_oo_sub_g5_ndpsi
-  (operator/tm_operators_nd.c:639-757), composed with the reference's own Hopping_Matrix (oracle/_ref/libtmref.so,
+* tests/golden/ref_nd_4x4.npz is self-consistent: the NumPy restatement of M_ee_inv_ndpsi / M_oo_sub_g5_ndpsi
+  (operator/tm_operators_nd.c:639-757, oracle/nd_restate.py), composed with the reference's own Hopping_Matrix (oracle/_ref/libtmref.so,
   through oracle/refbind.py), reproduces the fixture's Qtm_pm_ndpsi, Qtm_ndpsi and Qtm_dagger_ndpsi.
 """
 import json
@@ -14,6 +14,8 @@ import sys
 
 import numpy as np
 import pytest
+
+from oracle.nd_restate import cplx as _c, m_ee_inv, m_oo_sub_g5, real as _r
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "tmlqcd_amd", "lib")
@@ -61,32 +63,6 @@ def test_fixture_scalars_describe_the_runs():
     assert m["drops"], "the fixture must exercise the shift drop of cg_mms_tm_nd.c:158-167"
     s8 = json.load(open(os.path.join(GOLD, "ref_nd_scalars_8x8.json")))
     assert s8["cg_her_nd"]["iters"] > 0 and s8["cg_mms_tm_nd"]["iters"] > 0
-
-
-# ---- NumPy restatement of the site-local doublet blocks ------------------------------------------------------------
-def _c(a):
-    return a[..., 0] + 1j * a[..., 1]          # [N][4][3][2] -> complex [N][4][3]
-
-
-def _r(z):
-    return np.ascontiguousarray(np.stack([z.real, z.imag], axis=-1))
-
-
-_UP = np.array([1, 1, 0, 0], dtype=bool)[None, :, None]   # spins 0, 1
-
-
-def m_ee_inv(ks, kc, mu, eps):
-    """tm_operators_nd.c:639-696"""
-    zs = np.where(_UP, 1 - 1j * mu, 1 + 1j * mu)
-    nrm = 1. / (1. + mu * mu - eps * eps)
-    return nrm * (zs * ks + eps * kc), nrm * (np.conj(zs) * kc + eps * ks)
-
-
-def m_oo_sub_g5(ks, kc, js, jc, mu, eps):
-    """tm_operators_nd.c:698-757"""
-    zs = np.where(_UP, 1 - 1j * mu, 1 + 1j * mu)
-    p1, p2 = zs * ks + eps * kc, np.conj(zs) * kc + eps * ks
-    return np.where(_UP, p1 - js, js - p1), np.where(_UP, p2 - jc, jc - p2)
 
 
 def _child():

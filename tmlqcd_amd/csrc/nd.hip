@@ -504,7 +504,7 @@ static int nd_solve(tmhip_ctx *ctx, bool her, tmhip_field **x_up, tmhip_field **
       if (tmhip_assign(ctx, n->ps[2 * s - 2], q_up, N) || tmhip_assign(ctx, n->ps[2 * s - 1], q_dn, N)) return 1;
     }
     h.normsq = squarenorm;
-    h.target = rel_prec > 0 ? eps_sq * squarenorm : eps_sq;
+    h.target = rel_prec > 0 ? eps_sq * squarenorm : (rel_prec == 0 ? eps_sq : -1.0);   // :186-188: rel_prec < 0 runs to max_iter
   }
   if (tmhip_assign(ctx, p_up, r_up, N) || tmhip_assign(ctx, p_dn, r_dn, N)) return 1;
   h.alphas[0] = 1.0; h.betas[0] = 0.0;
