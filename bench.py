@@ -6,15 +6,22 @@ A "step" is one iteration of the reference's timed loop (benchmark.c:291-300):
 on fields resident in HBM.  `value` follows benchmark.c:318,327: Mflop/s = nranks * 1608 / (us per
 site-update).  N=1 workload: 32^4 fp64 (BASELINE.json configs[2]); N>1: weak scaling, every rank
 holds a 32^4 slab of a 32^3 x (32 N) lattice split in T, half-spinor faces exchanged over RCCL
-and overlapped with the stencil; the same run also measures BASELINE configs[3] (32^3 x 64 split
-N ways, the `strong` object) and north_star's literal "32^4 at 1/2/4/8 GPUs" (32^4 split N ways,
-`strong_32`), each after checking it slab by slab against the unsplit lattice computed on rank 0
-BEFORE the split operations start (`rank_check`).  Every leg is a sequence of steps the ranks
-agree on (class Phase): if any rank fails a step, all ranks leave that leg at that step -- nobody
-goes on into a halo exchange or a collective the others will not reach -- and the line is still
-printed.
+and overlapped with the stencil.  Every leg is a sequence of steps the ranks agree on (class
+Phase): if any rank fails a step, all ranks leave that leg at that step -- nobody goes on into a
+halo exchange or a collective the others will not reach -- and the line is still printed.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs: set-up, the calibration pass and the warm-up, the K timed
+steps, the cg_her iterations/s of the metric, --dump-outputs, the line (N > 1 with the default
+TMLQCD_BENCH_FACES=auto: also the direct face carrier, checked against the communicator's output,
+since the faster verified carrier gives `value`).  --full adds everything else: N = 1 the CPU
+baseline on the reference's objects and the informational legs (hermiticity, solves to 1e-10, the
+12-real gauge read, stream kernels, 16^4, MD step and ILDG record); N > 1 BASELINE configs[3]
+(32^3 x 64 split N ways, the `strong` object) and north_star's literal "32^4 at 1/2/4/8 GPUs"
+(32^4 split N ways, `strong_32`), each after checking it slab by slab against the unsplit lattice
+computed on rank 0 BEFORE the split operations start (`rank_check`), and the loop with
+communication switched off (`nocom`).
 
 Launch: one process per GPU.  Under torchrun (WORLD_SIZE set) this process IS one rank.  Started
 plainly with --gpus N > 1 it becomes a parent that never touches the GPU: it starts
@@ -46,22 +53,28 @@ def parse(argv=None):
     ap.add_argument("--T", type=int, default=0, help="local time extent (default = L)")
     ap.add_argument("--strong", type=int, default=0, metavar="TGLOBAL",
                     help="make the HEADLINE a strong-scaling run: fixed global lattice TGLOBAL x L^3 split in T over the ranks "
-                         "(default headline: weak scaling with L^4 per GPU; configs[3] is always reported in the `strong` object when N > 1)")
+                         "(default headline: weak scaling with L^4 per GPU; with --full, configs[3] is reported in the `strong` object when N > 1)")
     ap.add_argument("--cg-iters", type=int, default=200, help="cg_her iterations timed for the CG part of the metric")
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="wall budget of the timed loops of the CPU-baseline leg (all thread counts together)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = sweep {16, 64, all physical cores}; n = that thread count only")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-rows", action="store_true", help="skip the informational next-row legs (MD step, ILDG record)")
-    ap.add_argument("--no-rank-check", action="store_true", help="N > 1: skip the multi-rank parity check and the configs[3] leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: CPU baseline, informational legs, nocom, and N > 1 the rank check "
+                         "against the unsplit lattice with configs[3] and 32^4 / N (default: the headline alone)")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="--full: wall budget of the timed loops of the CPU-baseline leg (all thread counts together)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: 0 = sweep {16, 64, all physical cores}; n = that thread count only")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-rows", action="store_true", help="--full: skip the informational next-row legs (MD step, ILDG record)")
+    ap.add_argument("--no-rank-check", action="store_true", help="--full, N > 1: skip the multi-rank parity check and the configs[3] leg")
     ap.add_argument("--rehearse-split", action="store_true",
-                    help="one GPU, with --loopback: run the multi-rank legs (rank check against the unsplit lattice, configs[3], 32^4 / N) as a world of one rank "
+                    help="--full on one GPU, with --loopback: run the multi-rank legs (rank check against the unsplit lattice, configs[3], 32^4 / N) as a world of one rank "
                          "exchanging with itself -- the code path the N > 1 run takes, minus the rendezvous")
     ap.add_argument("--opt", action="append", default=[], help="library option name=value (A/B runs)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--loopback", type=int, default=0,
                     help="1-GPU rehearsal of the multi-GPU path: 1 = faces exchanged with self by a D2D copy, 2 = through a one-rank RCCL communicator")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.rehearse_split and not args.full:
+        ap.error("--rehearse-split rehearses legs of --full: add --full")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------- launcher (parent, never touches the GPU)
@@ -730,7 +743,7 @@ def rank_main(args, world, rank, local_rank):
     if Tg % world or (Tg // world) % 2 or Tg // world < 2:
         Tg = 8 * world                                      # odd rank counts: any even split serves the check
     steps_s = max(args.steps, 20)
-    split_legs = (world > 1 or (args.rehearse_split and args.loopback)) and not args.no_rank_check
+    split_legs = args.full and (world > 1 or (args.rehearse_split and args.loopback)) and not args.no_rank_check
     if split_legs:
         chk, tim = split_leg(R, args, L, Tg, "configs[3]", steps_s, faces_a)
         extra["rank_check"] = chk
@@ -774,7 +787,7 @@ def rank_main(args, world, rank, local_rank):
         src = box["src"]
         f0, f1, f2 = box["f"]
         dt, ev_ms = time_hopping(hl, R, lat, f0, f1, f2, args.steps, args.warmup)
-        gpu_out = f2.download() if (rank == 0 and world == 1 and not args.no_cpu) else None
+        gpu_out = f2.download() if (args.full and rank == 0 and world == 1 and not args.no_cpu) else None
         try_direct = (world > 1 or (args.rehearse_split and args.loopback == 2)) and R.faces_mode == "auto"
         f2_ref = f2.download() if try_direct else None         # this rank's slab of H_oe H_eo f0: what the other carrier has to reproduce
         # --- CG part of the metric: cg_her on Qtm_pm_psi (solver/cg_her.c:91-126)
@@ -797,6 +810,7 @@ def rank_main(args, world, rank, local_rank):
         R.close()
         return 1
     t_info = time.perf_counter()
+    # --- the legs below run with --full only: a plain run goes from the headline straight to its line
 
     def leg(name, body):
         """An informational leg as a phase of its own: a failure (on any rank) costs this leg, never the headline line, and every
@@ -818,7 +832,7 @@ def rank_main(args, world, rank, local_rank):
                 f.free()
             return abs(s1 - s2) / max(abs(s1), 1e-300)
         return ph.step("Q_plus = Q_minus^dagger", fn)
-    extra["hermiticity_rel_dev"] = leg("hermiticity", herm)
+    extra["hermiticity_rel_dev"] = leg("hermiticity", herm) if args.full else None
 
     # --- time to solution: cg_her vs mixed_cg_her (fp32 inner / fp64 restart) to |r|/|b| = 1e-10 (BASELINE configs[1])
     def solves(ph):
@@ -850,11 +864,11 @@ def rank_main(args, world, rank, local_rank):
             if outer is not None:
                 out[name]["outer_iters"] = outer
         return out
-    cg["solve_to_1e-10"] = leg("solve to 1e-10", solves)
+    cg["solve_to_1e-10"] = leg("solve to 1e-10", solves) if args.full else None
 
     # --- benchmark.c:336-374: on a split lattice the reference also times the loop with communication switched off
     nocom = None
-    if world > 1 or args.loopback:
+    if args.full and (world > 1 or args.loopback):
         def nocom_leg(ph):
             dtn = time_nocom(ph, R, lat, f0, f1, f2, args.steps)
             return {"value": world * 1608.0 / (1e6 * dtn / (args.steps * V)), "unit": "Mflop/s", "ms_per_step": 1e3 * dtn / args.steps,
@@ -865,7 +879,7 @@ def rank_main(args, world, rank, local_rank):
     # --- informational: the same loop with the opt-in 12-real gauge read (third row of each link rebuilt in registers;
     # exact for SU(3) links, guarded on the device).  Never part of `value`: the headline is the plain 18-real path.
     recon = None
-    if world == 1:                                      # keep the multi-rank run to the headline measurement
+    if args.full and world == 1:                        # keep the multi-rank run to the headline measurement
         def recon_leg(ph):
             lat.set_option("gauge_recon", 12)
             try:
@@ -883,7 +897,7 @@ def rank_main(args, world, rank, local_rank):
     # on the box and quote the fraction of THAT too"): copy R = S and triad P += c Q over several pairs of fields in turn, so that the
     # working set (8 x 101 MB at 32^4) is beyond the 256 MB Infinity Cache
     stream = None
-    if world == 1 and not args.loopback:
+    if args.full and world == 1 and not args.loopback:
         def stream_leg(ph):
             def fn():
                 Vh = V // 2
@@ -907,7 +921,7 @@ def rank_main(args, world, rank, local_rank):
 
     # --- BASELINE configs[1] (16^4, one GPU): the launch-bound end of the path
     cg16 = None
-    if world == 1 and not args.loopback and (T, L) == (32, 32):
+    if args.full and world == 1 and not args.loopback and (T, L) == (32, 32):
         def cg16_leg(ph):
             l16 = Lattice(16, 16, 16, 16, kappa=0.125, mu=0.01, device=R.device)
             l16.set_gauge(syn.gauge_field(7, 16, 16, 16, 16))
@@ -924,7 +938,7 @@ def rank_main(args, world, rank, local_rank):
     # molecular-dynamics step of the clover determinant without its solves (update_gauge.c, clover_term.c, clover_invert.c, deriv_Sb.c,
     # clover_deriv.c, clover_accumulate_deriv.c, update_momenta.c) and an ILDG record into / out of the resident links.
     rows = None
-    if world == 1 and not args.loopback and not args.no_rows:
+    if args.full and world == 1 and not args.loopback and not args.no_rows:
         try:
             kap, csw = 0.125, 1.5
             lat.momenta_upload(np.zeros((lat.V, 4, 8)))
@@ -985,6 +999,7 @@ def rank_main(args, world, rank, local_rank):
                                    % (T, L, T * world, L),
                        "local_lattice": [T, L, L, L], "global_lattice": [T * world, L, L, L],
                        "calibration_steps": CALIBRATION_STEPS,      # untimed, before the `warmup` steps: benchmark.c:262-281 (see time_hopping)
+                       "full": args.full,                           # False: the legs beyond the headline were not run (their objects are null)
                        "parallelism": ("T-split ring of %d, half-spinor faces %s" % (world, "as direct stores into the neighbours' memory (ring: %s)" % R.ring if faces_a == "direct" else "over " + R.transport) if world > 1 else
                                        ("single GPU, split-phase path rehearsed with self-exchange (loopback %d)" % args.loopback
                                         if args.loopback else "single GPU"))},

@@ -1,4 +1,4 @@
-"""TEST / MEASUREMENT INFRASTRUCTURE ONLY (see oracle/README.md): one leg of bench.py's `cpu_baseline`.
+"""TEST / MEASUREMENT INFRASTRUCTURE ONLY (see oracle/README.md): one leg of `bench.py --full`'s `cpu_baseline`.
 
 Times the reference's own loop {Hopping_Matrix(0); Hopping_Matrix(1)} (benchmark.c:291-300) on the host cores with ONE
 thread count, in a process of its own so that OMP_PROC_BIND / OMP_PLACES / OMP_NUM_THREADS (set by the caller) are seen

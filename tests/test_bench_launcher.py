@@ -131,3 +131,14 @@ def test_guardian_prints_the_saved_line_when_rank_0_dies():
 def test_guardian_stays_silent_when_rank_0_prints_its_own_line():
     r = _guardian_child("g.done(); print('{\"own\": 1}', flush=True)")
     assert r.returncode == 0 and [ln for ln in r.stdout.splitlines() if ln.startswith("{")] == ['{"own": 1}'], (r.stdout, r.stderr[-500:])
+
+
+def test_full_is_off_by_default_and_rehearse_split_asks_for_it():
+    """A plain run is the headline alone; --full adds the other legs.  --rehearse-split rehearses legs of --full and says so instead of
+    quietly rehearsing nothing."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    r = subprocess.run([sys.executable, BENCH, "--rehearse-split", "--loopback", "2"], env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=120)
+    assert r.returncode == 2 and "add --full" in r.stderr and not r.stdout.strip()

@@ -16,12 +16,13 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(nranks, extra=(), rc_ok=True, **more_env):
+def _bench(nranks, extra=(), rc_ok=True, full=True, **more_env):
+    # --cg-iters 100: five (t(25) - t(5)) samples per leg, not one -- with the ranks sharing one GPU a single sample can come out negative
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TMLQCD_BENCH_TRANSPORT="shm", HSA_ENABLE_IPC_MODE_LEGACY="0", TMLQCD_HIP_FLAG_TIMEOUT_S="60")
     env.update(more_env)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--L", "16", "--steps", "20", "--warmup", "2", "--cg-iters", "20",
-           "--no-cpu", "--no-rows"] + list(extra)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--L", "16", "--steps", "20", "--warmup", "2", "--cg-iters", "100",
+           "--no-cpu", "--no-rows"] + (["--full"] if full else []) + list(extra)
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert (r.returncode == 0) == (rc_ok is True), r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -52,6 +53,18 @@ def test_bench_runs_as_n_processes_and_agrees_with_the_unsplit_lattice(nranks):
         s32 = rec["strong_32"]
         assert s32["rank_check"]["ok"] is True, s32
     assert rec["cg"]["iters_per_s"] > 0 and abs(rec["hermiticity_rel_dev"]) < 1e-12
+
+
+def test_plain_bench_keeps_the_headline_and_its_carrier_check():
+    """Without --full the multi-rank run is the headline alone -- no rank check, no configs[3] or 32^4 / N legs, no nocom -- but the
+    direct carrier still runs after the communicator (the faster verified carrier gives `value`), checked against its output."""
+    rec, err = _bench(2, full=False)
+    assert rec["n_ranks"] == 2 and rec["value"] and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["cg"]["iters_per_s"] > 0
+    assert rec["config"]["full"] is False and rec["nocom"] is None and rec["hermiticity_rel_dev"] is None
+    assert not {"rank_check", "strong", "strong_32"} & set(rec) and not {"configs[3]", "strong_32"} & set(rec["wall_s"])
+    fd = rec["faces_direct"]
+    assert fd["ok"] is True and "strong" not in fd, fd
+    assert fd["headline"]["max_rel_dev_vs_communicator"] <= 1e-13 and fd["headline"]["faces"] == "direct"
 
 
 @pytest.mark.parametrize("who", ["abort_direct", "abort_direct_peer"])

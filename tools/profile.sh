@@ -9,10 +9,10 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $R/bench.py --steps 200 --warmup 20 --no-cpu > $OUT/${TAG}_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $R/bench.py --full --steps 200 --warmup 20 --no-cpu > $OUT/${TAG}_stats.log 2>&1
 echo "stats pass done"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_pmc_fetch -- python3 $R/bench.py --steps 20 --warmup 2 --no-cpu --cg-iters 5 > $OUT/${TAG}_pmc_fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_pmc_fetch -- python3 $R/bench.py --full --steps 20 --warmup 2 --no-cpu --cg-iters 5 > $OUT/${TAG}_pmc_fetch.log 2>&1
 echo "fetch pass done"
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_pmc_write -- python3 $R/bench.py --steps 20 --warmup 2 --no-cpu --cg-iters 5 > $OUT/${TAG}_pmc_write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_pmc_write -- python3 $R/bench.py --full --steps 20 --warmup 2 --no-cpu --cg-iters 5 > $OUT/${TAG}_pmc_write.log 2>&1
 echo "write pass done"
 python3 $R/tools/prof_summary.py $TAG

@@ -25,6 +25,6 @@ except Exception as e:
 PY
   grep -c "gave up" gpurun_out/r04_bench_${tag}.err | sed 's/^/  give-ups: /'
 }
-run 5ranks_default 5 --
-run 4ranks_events 4 -- --opt split_sync=1
-run 5ranks_ipc 5 TMLQCD_BENCH_TRANSPORT=ipc --
+run 5ranks_default 5 -- --full
+run 4ranks_events 4 -- --full --opt split_sync=1
+run 5ranks_ipc 5 TMLQCD_BENCH_TRANSPORT=ipc -- --full

@@ -1,7 +1,7 @@
 # split-path check of round 4: unsplit vs loopback 1 (copies) / 2 (one-rank RCCL) / 3 (direct carrier: one-kernel and two-kernel form) at
 # T_local = 4 .. 32 on one box (32^3 spatial, fp64); % of unsplit = same-box A/B
 mkdir -p gpurun_out
-RUN="timeout -k 10 90 python bench.py --no-cpu --no-rows --steps 300 --warmup 30 --cg-iters 30"
+RUN="timeout -k 10 90 python bench.py --full --no-cpu --no-rows --steps 300 --warmup 30 --cg-iters 30"
 export TMLQCD_HIP_FLAG_TIMEOUT_S=5
 for T in 4 8 16 32; do
   $RUN --T $T > gpurun_out/r04_unsplit_T$T.json 2>gpurun_out/r04_unsplit_T$T.err || { echo "unsplit T=$T failed"; exit 1; }
