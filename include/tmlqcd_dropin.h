@@ -195,6 +195,13 @@ int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *cons
               const int rel_prec, const int N, matrix_mult_nd f);
 int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *solver_params);
 
+/* ---- solver/cg_mms_tm.h:31: the single-flavour multi-shift CG (solver/cg_mms_tm.c:65-197) ----------------------------------
+ * Device-resident (tmhip_cg_mms_tm) for M_psi = Qtm_pm_psi / Qsw_pm_psi with sdim = VOLUME/2 and M_psi = Q_pm_psi (no clover term)
+ * with sdim = VOLUME, on unsplit lattices, up to 32 shifts.  Every other call (another M_psi, a T-split rank, more shifts) runs the
+ * reference loop verbatim on host-visible fields in coherent mode, as cg_her's generic path does.  Either way
+ * *cgmms_reached_prec receives the last err and g_sloppy_precision (when the host program has it) is reset to 0 (:175,192). */
+int cg_mms_tm(spinor **const P, spinor *const Q, tmlqcd_solver_params *solver_params, double *cgmms_reached_prec);
+
 /* ---- deriv_Sb.h: hopping part of the fermion force -------- */
 typedef struct { double d1, d2, d3, d4, d5, d6, d7, d8; } su3adj;           /* su3adj.h:23-26 */
 typedef struct {                                                             /* hamiltonian_field.h:26-32 */

@@ -136,7 +136,8 @@ int tmhip_mul_r(tmhip_ctx *ctx, tmhip_field *R, double c, tmhip_field *S, int N)
 
 /* ---- solver --------------------------------------------------------------- */
 enum { TMHIP_OP_QTM_PM = 0, TMHIP_OP_QTM_PLUS = 1, TMHIP_OP_QTM_MINUS = 2, TMHIP_OP_MTM_PLUS = 3, TMHIP_OP_MTM_MINUS = 4,
-       TMHIP_OP_QSW_PM = 5 /* clover: Qsw_pm_psi, needs tmhip_set_clover */ };
+       TMHIP_OP_QSW_PM = 5 /* clover: Qsw_pm_psi, needs tmhip_set_clover */,
+       TMHIP_OP_Q_PM_FULL = 6 /* Q_pm_psi on FULL fields (tm_operators.c:380-388): tmhip_cg_mms_tm only, tmhip_cg_her refuses it */ };
 /* cg_her(P,Q,max_iter,eps_sq,rel_prec,N,f)   solver/cg_her.c:62-141.
  * Device-resident: P, Q and the three work fields never leave HBM.  Returns the
  * iteration count in *iters (-1 if not converged); res_hist (may be NULL) gets
@@ -168,6 +169,24 @@ int tmhip_cg_mms_tm_nd(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmh
                        int nshifts, int max_iter, double eps_sq, int rel_prec, int *iters);
 /* shifts still active at the end of the last tmhip_cg_mms_tm_nd (the reference's local `shifts`, cg_mms_tm_nd.c:68,163) */
 int tmhip_nd_active_shifts(tmhip_ctx *ctx);
+
+/* ---- single-flavour multi-shift CG (solver/cg_mms_tm.c:65-197) ------------------------------------------------------------
+ * cg_mms_tm(P,Q,solver_params,&reached_prec) with M_psi = Qtm_pm_psi / Qsw_pm_psi on N = VOLUME/2 sites (op TMHIP_OP_QTM_PM /
+ * TMHIP_OP_QSW_PM, EO fields) or Q_pm_psi on N = VOLUME sites (op TMHIP_OP_Q_PM_FULL, FULL fields; g_mu as set by tmhip_set_mu).
+ * P[s] solves (M_psi + shifts[s]^2) P = Q for s = 0 .. nshifts-1, 1 <= nshifts <= 32: shifts[0]^2 is added to the operator of the
+ * CG (:88,115-118), the others are relative to it (:91); every P[s] starts at zero (any content is ignored, :85,94), Q is not
+ * modified.  The last active shift is dropped every 20 iterations once alphas^2 |ps|^2 <= eps_sq (:146-153).  Stopping test
+ * (:170-176): rel_prec == 0 err <= eps_sq, rel_prec > 0 err <= eps_sq |Q|^2, rel_prec < 0 none.  *iters = the reference's return
+ * value: -1 when the loop ended at iteration max_iter - 1, converged there or not, else the iteration count (:193-194);
+ * *reached_prec (may be NULL) = the last err (:175).  Device-resident, unsplit lattices only: a T-split context or its loopback
+ * rehearsal is refused, as are nshifts outside [1, 32] and an N that does not match op. */
+int tmhip_cg_mms_tm(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const double *shifts, int nshifts, int max_iter, double eps_sq,
+                    int rel_prec, int N, int op, int *iters, double *reached_prec);
+/* shifts still active at the end of the last tmhip_cg_mms_tm (the reference's local `no_shifts`, cg_mms_tm.c:67,148) */
+int tmhip_mms_active_shifts(tmhip_ctx *ctx);
+/* form the last tmhip_cg_mms_tm took: 0 fused e/o stencils (cg_her's fusable shapes), 1 unfused e/o (operator, then separate
+ * reductions), 2 the FULL composite Q_pm_psi; -1 before the first solve */
+int tmhip_mms_form(tmhip_ctx *ctx);
 
 /* ---- fermion force, hopping part (deriv_Sb.c:401-700) ------------------------------
  * deriv_Sb(ieo, l, k, hf, factor) accumulates 2 factor trlambda(...) of the one-hop terms into hf->derivative.  Here the

@@ -479,6 +479,7 @@ extern "C" int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int 
                             int op, int *iters, double *res_hist, int hist_len) {
   if (!P || !Q || P->kind != TMHIP_FIELD_EO || Q->kind != TMHIP_FIELD_EO) TMHIP_FAIL("cg_her needs one-parity (EO) fields");
   if (N != ctx->Vh) TMHIP_FAIL("cg_her: N must be VOLUME/2");
+  if (op == TMHIP_OP_Q_PM_FULL) TMHIP_FAIL("cg_her: Q_pm_psi acts on FULL fields; cg_her takes the e/o operators only");
   if (ctx->opt_cg_sync) return cg_her_sync(ctx, P, Q, max_iter, eps_sq, rel_prec, N, op, iters, res_hist, hist_len);
   TMHIP_CHECK(hipSetDevice(ctx->device));
   if (cg_state_alloc(ctx)) return 1;

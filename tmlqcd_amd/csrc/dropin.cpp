@@ -1582,6 +1582,98 @@ int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spin
   return iters;
 }
 
+/* solver/cg_mms_tm.c:65-197 */
+extern int g_sloppy_precision __attribute__((weak));   /* global.h:95 */
+int cg_mms_tm(spinor **const P, spinor *const Q, tmlqcd_solver_params *sp, double *cgmms_reached_prec) {
+  const int N = sp->sdim, n = sp->no_shifts, max_iter = sp->max_iter, rel_prec = sp->rel_prec;
+  const double eps_sq = sp->squared_solver_prec;
+  const bool clover_full = &g_c_sw && g_c_sw > 0.;   /* Q_pm_psi with a clover term goes through Msw_full (d_psi_core): not on the device here */
+  int op = -1;
+  if ((sp->M_psi == &Qtm_pm_psi || sp->M_psi == &Qsw_pm_psi) && N == VOLUME / 2) op = sp->M_psi == &Qsw_pm_psi ? TMHIP_OP_QSW_PM : TMHIP_OP_QTM_PM;
+  else if (sp->M_psi == &Q_pm_psi && N == VOLUME && !clover_full) op = TMHIP_OP_Q_PM_FULL;
+  int iters = -1;
+  if (op >= 0 && g_nproc_t == 1 && n >= 1 && n <= 32 && max_iter >= 1) {
+    tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? refresh_clover() : refresh(true);
+    const int kind = op == TMHIP_OP_Q_PM_FULL ? TMHIP_FIELD_FULL : TMHIP_FIELD_EO;
+    tmhip_field *fq = in(c, Q, kind), *fp[32];
+    for (int s = 0; s < n; s++) fp[s] = out(c, P[s], kind);
+    double reached = 0.0;
+    CK(tmhip_cg_mms_tm(c, fp, fq, sp->shifts, n, max_iter, eps_sq, rel_prec, N, op, &iters, &reached));
+    for (int s = 0; s < n; s++) done(c, P[s]);
+    *cgmms_reached_prec = reached;
+  } else {
+    // generic path: the reference loop verbatim on host-visible fields (assign_mul_add_mul_r inlined: the host program need not have it)
+    const int saved = g_mode;
+    tmlqcd_hip_set_residency(TMLQCD_HIP_COHERENT);
+    const size_t Vf = (size_t)(N == VOLUME ? VOLUMEPLUSRAND : VOLUMEPLUSRAND / 2);
+    const int ns = n > 1 ? n : 1;
+    spinor *blk = (spinor *)calloc((3 + (size_t)(ns - 1)) * Vf + 1, sizeof(spinor));   /* solver_field.c:31-71, init_mms_tm :207-228 */
+    double *co = (double *)calloc(5 * (size_t)ns, sizeof(double));
+    if (!blk || !co) die("cg_mms_tm: out of memory");
+    spinor *sf[3] = {blk, blk + Vf, blk + 2 * Vf};
+    spinor **ps = (spinor **)calloc(ns, sizeof(spinor *));
+    if (!ps) die("cg_mms_tm: out of memory");
+    for (int s = 1; s < ns; s++) ps[s] = blk + (2 + s) * Vf;
+    double *sigma = co, *zitam1 = co + ns, *zita = co + 2 * ns, *alphas = co + 3 * ns, *betas = co + 4 * ns;
+    int no_shifts = n, iteration;
+    double normsq, pro, err = 0.0, squarenorm, gamma, alpham1;
+    for (int i = 0; i < N; i++) P[0][i] = spinor{};
+    alphas[0] = 1.0; betas[0] = 0.0;
+    sigma[0] = sp->shifts[0] * sp->shifts[0];
+    for (int im = 1; im < no_shifts; im++) {
+      sigma[im] = sp->shifts[im] * sp->shifts[im] - sigma[0];
+      for (int i = 0; i < N; i++) P[im][i] = spinor{};
+      assign(ps[im], Q, N);
+      zitam1[im] = zita[im] = alphas[im] = 1.0; betas[im] = 0.0;
+    }
+    squarenorm = square_norm(Q, N, 1);
+    assign(sf[0], Q, N);
+    assign(sf[1], Q, N);
+    normsq = squarenorm;
+    for (iteration = 0; iteration < max_iter; iteration++) {
+      sp->M_psi(sf[2], sf[1]);
+      assign_add_mul_r(sf[2], sf[1], sigma[0], N);
+      pro = scalar_prod_r(sf[1], sf[2], N, 1);
+      alpham1 = alphas[0];
+      alphas[0] = normsq / pro;
+      for (int im = 1; im < no_shifts; im++) {
+        gamma = zita[im] * alpham1 / (alphas[0] * betas[0] * (1. - zita[im] / zitam1[im]) + alpham1 * (1. + sigma[im] * alphas[0]));
+        zitam1[im] = zita[im];
+        zita[im] = gamma;
+        alphas[im] = alphas[0] * zita[im] / zitam1[im];
+        assign_add_mul_r(P[im], ps[im], alphas[im], N);
+        if (iteration > 0 && (iteration % 20 == 0) && (im == no_shifts - 1)) {
+          const double sn = square_norm(ps[im], N, 1);
+          if (alphas[no_shifts - 1] * alphas[no_shifts - 1] * sn <= eps_sq) no_shifts--;
+        }
+      }
+      assign_add_mul_r(P[0], sf[1], alphas[0], N);
+      assign_add_mul_r(sf[0], sf[2], -alphas[0], N);
+      err = square_norm(sf[0], N, 1);
+      if (((err <= eps_sq) && (rel_prec == 0)) || ((err <= eps_sq * squarenorm) && (rel_prec > 0)) || (iteration == max_iter - 1)) {
+        *cgmms_reached_prec = err;
+        break;
+      }
+      betas[0] = err / normsq;
+      assign_mul_add_r(sf[1], betas[0], sf[0], N);
+      normsq = err;
+      for (int im = 1; im < no_shifts; im++) {
+        betas[im] = betas[0] * zita[im] * alphas[im] / (zitam1[im] * alphas[0]);
+        const double c1 = betas[im], c2 = zita[im];   /* assign_mul_add_mul_r(ps, sf0, c1, c2, N) */
+        double *r = (double *)ps[im];
+        const double *s = (const double *)sf[0];
+        for (size_t k = 0; k < (size_t)N * 24; k++) r[k] = c1 * r[k] + c2 * s[k];
+      }
+    }
+    for (int i = 0; i < 3 + ns - 1; i++) tmlqcd_hip_forget(blk + (size_t)i * Vf);   // addresses are about to be recycled
+    free(blk); free(co); free(ps);
+    g_mode = saved;
+    iters = iteration == max_iter - 1 ? -1 : iteration + 1;
+  }
+  if (&g_sloppy_precision) g_sloppy_precision = 0;   /* :192 */
+  return iters;
+}
+
 int mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params, const int max_iter, double eps_sq,
                  const int rel_prec, const int N, matrix_mult f, matrix_mult32) {
   if ((f != &Qtm_pm_psi && f != &Qsw_pm_psi) || N != VOLUME / 2) die("mixed_cg_her: only f = Qtm_pm_psi / Qsw_pm_psi on VOLUME/2 sites runs on the device");

@@ -108,8 +108,9 @@ __device__ __forceinline__ void su3_block_mac(V2T (&r)[3], const ET *__restrict_
 }
 
 // epilogues that end in a block reduction into a.partials[blockIdx.x]
-#define HOP_EPI_REDUCES(E) ((E) == EPI_TM_SUB_G5_DOT || (E) == EPI_TM_SUB_G5_NRM || (E) == EPI_TM_SUB_G5_RES || (E) == EPI_CLOVER_G5_NRM || (E) == EPI_CLOVER_G5_RES)
-#define HOP_EPI_CLOVER_G5(E) ((E) == EPI_CLOVER_G5 || (E) == EPI_CLOVER_G5_NRM || (E) == EPI_CLOVER_G5_RES)
+#define HOP_EPI_REDUCES(E) ((E) == EPI_TM_SUB_G5_DOT || (E) == EPI_TM_SUB_G5_NRM || (E) == EPI_TM_SUB_G5_RES || (E) == EPI_CLOVER_G5_NRM || (E) == EPI_CLOVER_G5_RES || \
+                            (E) == EPI_TM_SUB_G5_RSH || (E) == EPI_CLOVER_G5_RSH)
+#define HOP_EPI_CLOVER_G5(E) ((E) == EPI_CLOVER_G5 || (E) == EPI_CLOVER_G5_NRM || (E) == EPI_CLOVER_G5_RES || (E) == EPI_CLOVER_G5_RSH)
 
 // SM: where the neighbour spinor comes from in the LDS-staged variant (the wave has copied the input spinors of its own 64
 // consecutive sites to its LDS region):
@@ -475,10 +476,13 @@ __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
     // clover_gamma5 / clover (clovertm_operators.c:448-520, 535-600): l = [g5] ( (1 + T + i mu g5) p - H k ),
     // T = sw (6 blocks = [3][2]): psi1 = A s_a + B s_b, psi2 = B^dag s_a + C s_b
     // _NRM / _RES: the CG reductions of cg_enqueue_fused (cg.hip) on top, as for the twisted-mass epilogue below
+    // _RSH (multi-shift CG, mms.hip): resid -= alpha (out + sigma0 dotv), alpha = scal[0], sigma0 = scal[1]
+    constexpr bool CRES = EPI == EPI_CLOVER_G5_RES || EPI == EPI_CLOVER_G5_RSH;
     const ET *__restrict__ p = a.p;
     double d = 0.0;
-    V2T malpha = cbcast(0.0, 0.0);
-    if (EPI == EPI_CLOVER_G5_RES) malpha = cbcast(-*a.scal, 0.0);
+    V2T malpha = cbcast(0.0, 0.0), csig = cbcast(0.0, 0.0);
+    if (CRES) malpha = cbcast(-*a.scal, 0.0);
+    if (EPI == EPI_CLOVER_G5_RSH) csig = cbcast(a.scal[1], 0.0);
 #pragma unroll
     for (int b = 0; b < 2; b++) {
       V2T sab[6], r1[3], r2[3], o[6];
@@ -489,16 +493,18 @@ __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
       su3_block_mul(r2, a.cw, a.gs, i, 1 * 2 + b, sa, true);
       su3_block_mac(r2, a.cw, a.gs, i, 2 * 2 + b, sb, false);
       const V2T imu = cbcast(0.0, b == 0 ? a.cim : -a.cim);   // + i mu on the upper, - i mu on the lower components
-      V2T rs[6];
-      if (EPI == EPI_CLOVER_G5_RES) ld6<NTIO>(rs, a.resid, ns, i, b);
+      V2T rs[6], pw[6];
+      if (CRES) ld6<NTIO>(rs, a.resid, ns, i, b);
+      if (EPI == EPI_CLOVER_G5_RSH) ld6<NTIO>(pw, a.dotv, ns, i, b);
 #pragma unroll
       for (int c = 0; c < 3; c++) {
         r1[c] = cfma(imu, sa[c], r1[c]);
         r2[c] = cfma(imu, sb[c], r2[c]);
         const bool flip = HOP_EPI_CLOVER_G5(EPI) && b == 1;
-        const V2T v1 = flip ? acc[6 * b + c] - r1[c] : r1[c] - acc[6 * b + c];
-        const V2T v2 = flip ? acc[6 * b + 3 + c] - r2[c] : r2[c] - acc[6 * b + 3 + c];
-        if (EPI == EPI_CLOVER_G5_RES) {
+        V2T v1 = flip ? acc[6 * b + c] - r1[c] : r1[c] - acc[6 * b + c];
+        V2T v2 = flip ? acc[6 * b + 3 + c] - r2[c] : r2[c] - acc[6 * b + 3 + c];
+        if (EPI == EPI_CLOVER_G5_RSH) { v1 = cfma(csig, pw[c], v1); v2 = cfma(csig, pw[3 + c], v2); }
+        if (CRES) {
           const V2T n1 = cfma(malpha, v1, rs[c]);
           const V2T n2 = cfma(malpha, v2, rs[3 + c]);
           o[c] = n1; o[3 + c] = n2;
@@ -508,7 +514,7 @@ __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
           if (EPI == EPI_CLOVER_G5_NRM) d += cdotd(v1, v1) + cdotd(v2, v2);
         }
       }
-      if (EPI == EPI_CLOVER_G5_RES) put(a.resid, b, o);
+      if (CRES) put(a.resid, b, o);
       else put(out, b, o);
     }
     if (HOP_EPI_REDUCES(EPI)) {
@@ -519,15 +525,27 @@ __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
     }
   } else {
     // EPI_TM_SUB_G5[_DOT]: hopping.h:680-688  l = g5[(cf,cf*) p - H k];  EPI_TM_SUB: same without g5
+    // _RSH (multi-shift CG, mms.hip): resid -= alpha (out + sigma0 dotv), alpha = scal[0], sigma0 = scal[1]
+    constexpr bool TRES = EPI == EPI_TM_SUB_G5_RES || EPI == EPI_TM_SUB_G5_RSH;
     const ET *__restrict__ p = a.p;
     double d = 0.0;
-    V2T malpha = cbcast(0.0, 0.0);
-    if (EPI == EPI_TM_SUB_G5_RES) malpha = cbcast(-*a.scal, 0.0);
+    V2T malpha = cbcast(0.0, 0.0), msig = cbcast(0.0, 0.0);
+    if (TRES) malpha = cbcast(-*a.scal, 0.0);
+    if (EPI == EPI_TM_SUB_G5_RSH) msig = cbcast(-a.scal[0] * a.scal[1], 0.0);
 #pragma unroll
     for (int b = 0; b < 2; b++) {
+      // _RSH: one chirality at a time (its three input fields are 18 complex values; both at once do not fit three waves per SIMD)
+      if (EPI == EPI_TM_SUB_G5_RSH) __builtin_amdgcn_sched_barrier(0);
       V2T pv[6], o[6], ex[6];
       ld6<NTIO>(pv, p, ns, i, b);
-      if (EPI == EPI_TM_SUB_G5_RES) ld6<NTIO>(ex, a.resid, ns, i, b);
+      if (TRES) ld6<NTIO>(ex, a.resid, ns, i, b);
+      if (EPI == EPI_TM_SUB_G5_RSH) {
+        // the sigma0 term first (resid - alpha sigma0 dotv): dotv is dead before the stencil's own terms are combined
+        V2T pw[6];
+        ld6<NTIO>(pw, a.dotv, ns, i, b);
+#pragma unroll
+        for (int cc = 0; cc < 6; cc++) ex[cc] = cfma(msig, pw[cc], ex[cc]);
+      }
       if (EPI == EPI_TM_SUB_G5_DOT) ld6<NTIO>(ex, a.dotv, ns, i, b);
 #pragma unroll
       for (int cc = 0; cc < 6; cc++) {
@@ -535,7 +553,7 @@ __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
         V2T r;
         if (b == 0) r = cmul(cf, pv[cc]) - acc[c];
         else { const V2T zp = cmulc(cf, pv[cc]); r = (EPI == EPI_TM_SUB) ? zp - acc[c] : acc[c] - zp; }
-        if (EPI == EPI_TM_SUB_G5_RES) {
+        if (TRES) {
           // cg_her.c:95-101 fused behind the last stencil of Qtm_pm_psi: r <- r - alpha (A p), err = |r|^2; A p is never stored
           const V2T rn = cfma(malpha, r, ex[cc]);
           o[cc] = rn;
@@ -546,8 +564,9 @@ __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
           if (EPI == EPI_TM_SUB_G5_DOT) d += cdotd(ex[cc], r);   // fused scalar_prod_r(dotv, out), cg_her.c:93
         }
       }
-      if (EPI == EPI_TM_SUB_G5_RES) put(a.resid, b, o);
+      if (TRES) put(a.resid, b, o);
       else put(out, b, o);
+      if (EPI == EPI_TM_SUB_G5_RSH) __builtin_amdgcn_sched_barrier(0);
     }
     if (HOP_EPI_REDUCES(EPI)) {
       // one partial per WAVE (no LDS, no block barrier: a barrier here keeps the CU slots of the fast waves occupied
@@ -1020,6 +1039,9 @@ static void launch_epi(const HopArgs &a, int epi, hipStream_t st, const HopLaunc
     case EPI_TM_SUB_G5_RES: launch_variant<EPI_TM_SUB_G5_RES, TSKIP>(a, st, o); break;
     case EPI_CLOVER_G5_NRM: launch_variant<EPI_CLOVER_G5_NRM, TSKIP>(a, st, o); break;
     case EPI_CLOVER_G5_RES: launch_variant<EPI_CLOVER_G5_RES, TSKIP>(a, st, o); break;
+    // the shifted residual updates exist for unsplit fp64 lattices only (launch_hopping_dot refuses them elsewhere)
+    case EPI_TM_SUB_G5_RSH: if constexpr (!TSKIP && sizeof(ET) == 16) launch_variant<EPI_TM_SUB_G5_RSH, 0>(a, st, o); break;
+    case EPI_CLOVER_G5_RSH: if constexpr (!TSKIP && sizeof(ET) == 16) launch_variant<EPI_CLOVER_G5_RSH, 0>(a, st, o); break;
     case EPI_CLOVER_INV: launch_variant<EPI_CLOVER_INV, TSKIP>(a, st, o); break;
     case EPI_CLOVER_G5: launch_variant<EPI_CLOVER_G5, TSKIP>(a, st, o); break;
     case EPI_CLOVER: launch_variant<EPI_CLOVER, TSKIP>(a, st, o); break;
@@ -1121,16 +1143,20 @@ int launch_hopping(tmhip_ctx *ctx, int ieo, ET *out, const ET *in, const ET *p, 
 }
 
 // tm_sub_Hopping_Matrix / clover_gamma5 with a CG reduction accumulated in the epilogue (partials in ctx->partials, *npartials of them):
-// mode 0 <dotv, l> (unsplit lattices only), 1 |l|^2, 2 resid -= (*scal) l without storing l, |resid|^2.
+// mode 0 <dotv, l> (unsplit lattices only), 1 |l|^2, 2 resid -= (*scal) l without storing l, |resid|^2, 3 (unsplit fp64 only)
+// resid -= scal[0] (l + scal[1] dotv) without storing l, |resid|^2 (the shifted residual of the multi-shift CG, mms.hip).
 int launch_hopping_dot(tmhip_ctx *ctx, int ieo, ET *out, const ET *in, const ET *p, const ET *dotv,
                              double cre, double cim, int *npartials, int mode, ET *resid, const double *scal, const ET *cw, int chained = 0, const HopSelfAlpha *self = nullptr) {
   if (cw && mode == 0) TMHIP_FAIL("launch_hopping_dot: the clover epilogue has modes 1 and 2 only");
-  if (mode < 0 || mode > 2 || (mode == 0 && !dotv) || (mode == 2 && (!resid || !(scal || self))) || (mode != 2 && !out)) TMHIP_FAIL("launch_hopping_dot: bad arguments for mode %d", mode);
-  if (mode == 2 && (const ET *)resid == in) TMHIP_FAIL("launch_hopping_dot: the residual must not be the gathered field");
+  const bool rmode = mode == 2 || mode == 3;
+  if (mode < 0 || mode > 3 || (mode == 0 && !dotv) || (mode == 2 && (!resid || !(scal || self))) || (mode == 3 && (!resid || !scal || !dotv || self)) ||
+      (!rmode && !out)) TMHIP_FAIL("launch_hopping_dot: bad arguments for mode %d", mode);
+  if (rmode && (const ET *)resid == in) TMHIP_FAIL("launch_hopping_dot: the residual must not be the gathered field");
   if (!HOP_CTX_GAUGE_READY(ctx)) TMHIP_FAIL("Hopping_Matrix called before tmhip_set_gauge");
   const bool split = ctx->g.nproc_t > 1 || ctx->loopback;
+  if (mode == 3 && (split || sizeof(ET) != 16)) TMHIP_FAIL("launch_hopping_dot: mode 3 exists for unsplit fp64 lattices only");
   const int blk = split ? 256 : tmhip_hop_block(ctx);   // T-split ranks: the 256-thread kernels only
-  const bool s4 = use_split4(ctx) && mode != 0 && !cw && ctx->opt_recon != 12;   // (the hop-split kernel: 64 sites and four partials per block)
+  const bool s4 = use_split4(ctx) && mode != 0 && mode != 3 && !cw && ctx->opt_recon != 12;   // (the hop-split kernel: 64 sites and four partials per block)
   if (ctx->Vh % ((s4 ? 64 : blk) * HOP_SITES) != 0 || (split && mode == 0))
     TMHIP_FAIL("stencil with fused reduction: needs whole blocks (and mode 1 or 2 on a split lattice)");
   if (out == in) TMHIP_FAIL("Hopping_Matrix: l and k must differ");
@@ -1145,8 +1171,8 @@ int launch_hopping_dot(tmhip_ctx *ctx, int ieo, ET *out, const ET *in, const ET 
   }
   HopLaunch o = launch_opts(ctx, blk);
   o.minw = 0;
-  const int epi = cw ? (mode == 1 ? EPI_CLOVER_G5_NRM : EPI_CLOVER_G5_RES)
-                     : (mode == 0 ? EPI_TM_SUB_G5_DOT : (mode == 1 ? EPI_TM_SUB_G5_NRM : EPI_TM_SUB_G5_RES));
+  const int epi = cw ? (mode == 1 ? EPI_CLOVER_G5_NRM : (mode == 2 ? EPI_CLOVER_G5_RES : EPI_CLOVER_G5_RSH))
+                     : (mode == 0 ? EPI_TM_SUB_G5_DOT : (mode == 1 ? EPI_TM_SUB_G5_NRM : (mode == 2 ? EPI_TM_SUB_G5_RES : EPI_TM_SUB_G5_RSH)));
   const int nbnd = split ? exterior_partials(ctx) : 0;
   // one partial per wave of the grid launch_one chooses (padded by the block orders: at most 8 + 7 * T extra blocks)
   {

@@ -166,6 +166,7 @@ struct tmhip_ctx {
   // non-degenerate doublet (nd.hip): g_mubar, g_epsbar (global.h:202), phmc_invmaxev (phmc.h:31); work fields and solver state
   double mubar, epsbar, invmaxev;
   void *nd; int nd_active_shifts;
+  void *mms; int mms_active_shifts;   // single-flavour multi-shift CG (mms.hip): work fields and solver state
   double gauge_recon_dev;   // max |U_row2 - conj(row0 x row1)| over all links of the resident gauge field (-1: not measured)
 };
 
@@ -229,7 +230,9 @@ int tmhip_direct_allreduce(tmhip_ctx *ctx, double *x);   // sum of *x (device) o
 // ---- launch helpers implemented across the .hip files ----
 enum { EPI_STORE = 0, EPI_TM_TIMES = 1, EPI_TM_SUB_G5 = 2, EPI_TM_SUB = 3, EPI_TM_SUB_G5_DOT = 4, EPI_CLOVER_INV = 5, EPI_CLOVER_G5 = 6, EPI_CLOVER = 7,
        EPI_TM_SUB_G5_NRM = 8 /* + partials of |out|^2 */, EPI_TM_SUB_G5_RES = 9 /* resid -= alpha out, partials of |resid|^2; out not stored */,
-       EPI_CLOVER_G5_NRM = 10, EPI_CLOVER_G5_RES = 11 /* the same two on top of the clover_gamma5 epilogue */ };
+       EPI_CLOVER_G5_NRM = 10, EPI_CLOVER_G5_RES = 11 /* the same two on top of the clover_gamma5 epilogue */,
+       EPI_TM_SUB_G5_RSH = 12, EPI_CLOVER_G5_RSH = 13 /* resid -= scal[0] (out + scal[1] dotv), partials of |resid|^2: the shifted
+                                                        residual update of the multi-shift CG (mms.hip); unsplit fp64 only */ };
 // `comm`: 0 no halo exchange (Hopping_Matrix_nocom), HOP_COMM exchange the faces of `in` first, HOP_COMM | HOP_CHAINED additionally
 // promises that `in` is the output of this context's previous split-phase stencil and has not been written since (a composition
 // like Qtm_pm_psi, the stencils of a fused CG iteration): its faces were projected by that stencil's exterior kernel already
@@ -255,7 +258,8 @@ __device__ __forceinline__ double tmhip_block_sum256(const double *__restrict__ 
   __syncthreads();
   return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
-// mode 0: partials of <dotv, out>; 1: of |out|^2; 2: resid -= (*scal) * out without storing out, partials of |resid|^2
+// mode 0: partials of <dotv, out>; 1: of |out|^2; 2: resid -= (*scal) * out without storing out, partials of |resid|^2;
+// 3 (unsplit fp64 only): resid -= scal[0] * (out + scal[1] * dotv) without storing out, partials of |resid|^2
 int tmhip_launch_hopping_dot(tmhip_ctx *ctx, int ieo, v2d *out, const v2d *in, const v2d *p, const v2d *dotv,
                              double cre, double cim, int *npartials, int mode = 0, v2d *resid = nullptr, const double *scal = nullptr,
                              const v2d *cw = nullptr, int chained = 0, const HopSelfAlpha *self = nullptr);   // cw: clover blocks => clover_gamma5 epilogue (modes 1, 2 only); chained: HOP_CHAINED
@@ -280,6 +284,7 @@ int tmhip_exchange_gauge_halo(tmhip_ctx *ctx);   // md_update.hip: t = 0 / T-1 s
 int tmhip_resort_gauge(tmhip_ctx *ctx);   // md_update.hip: stencil gauge copy from the device-resident lexicographic links
 int tmhip_prepare_clover32(tmhip_ctx *ctx);  // fp32 gauge copy + fp32 scratch / solver fields
 void tmhip_nd_destroy(tmhip_ctx *ctx);   // nd.hip: work fields and state of the doublet
+void tmhip_mms_destroy(tmhip_ctx *ctx);  // mms.hip: work fields and state of the single-flavour multi-shift CG
 // launch geometry shared by linalg.hip and cg.hip
 #define LA_BS 256
 #define LA_UNROLL 4

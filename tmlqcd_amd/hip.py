@@ -11,6 +11,7 @@ import numpy as np
 EO, OE = 0, 1
 FIELD_EO, FIELD_FULL = 0, 1
 OPS = {"Qtm_pm_psi": 0, "Qtm_plus_psi": 1, "Qtm_minus_psi": 2, "Mtm_plus_psi": 3, "Mtm_minus_psi": 4, "Qsw_pm_psi": 5}
+MMS_OPS = {"Qtm_pm_psi": 0, "Qsw_pm_psi": 5, "Q_pm_psi": 6}   # cg_mms_tm's operators (Q_pm_psi: FULL fields, TMHIP_OP_Q_PM_FULL)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -158,6 +159,9 @@ def load_library():
         "tmhip_cg_her_nd": [vp, vp, vp, vp, vp, i, d, i, i, C.POINTER(i)],
         "tmhip_cg_mms_tm_nd": [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, i, d, i, C.POINTER(i)],
         "tmhip_nd_active_shifts": [vp],
+        "tmhip_cg_mms_tm": [vp, C.POINTER(vp), vp, pd, i, i, d, i, i, i, C.POINTER(i), pd],
+        "tmhip_mms_active_shifts": [vp],
+        "tmhip_mms_form": [vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -659,6 +663,29 @@ class Lattice:
 
     def nd_active_shifts(self):
         return self.lib.tmhip_nd_active_shifts(self.h)
+
+    # --- single-flavour multi-shift CG (solver/cg_mms_tm.c) ---------------------------------------------------------------
+    def cg_mms_tm(self, Q, shifts, max_iter, eps_sq, rel_prec, op="Qtm_pm_psi", P=None):
+        """solver/cg_mms_tm.c: (iterations, reached_prec, [P_0, P_1, ...]), one solution per shift; op Qtm_pm_psi / Qsw_pm_psi
+        (one-parity fields, N = VOLUME/2) or Q_pm_psi (FULL fields, N = VOLUME).  P: fields to reuse as the solutions (allocated
+        otherwise).  Shifts still active at the end: mms_active_shifts()."""
+        full = op == "Q_pm_psi"
+        n = len(shifts)
+        if P is None:
+            P = [self.field(kind=FIELD_FULL if full else FIELD_EO) for _ in range(n)]
+        arr = (C.c_void_p * max(n, 1))(*[p.h for p in P])
+        sh = (C.c_double * max(n, 1))(*shifts)
+        it, prec = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_cg_mms_tm(self.h, arr, Q.h, sh, n, max_iter, eps_sq, rel_prec, self.V if full else self.Vh, MMS_OPS[op],
+                                     C.byref(it), C.byref(prec)), "cg_mms_tm")
+        return it.value, prec.value, P
+
+    def mms_active_shifts(self):
+        return self.lib.tmhip_mms_active_shifts(self.h)
+
+    def mms_form(self):
+        """0: fused e/o stencils, 1: unfused e/o form, 2: FULL composite (the last cg_mms_tm)"""
+        return self.lib.tmhip_mms_form(self.h)
 
     # --- multi-GPU --------------------------------------------------------
     def comm_unique_id(self):

@@ -19,13 +19,16 @@ CXXFILT = "c++filt"
 # Instances the default dispatch reaches (launch_variant / launch_exterior / launch_pack in hopping_impl.inc), as regular
 # expressions on the demangled name, with the floor each must keep.  Template arguments of hop_kernel:
 #   <EPI, TSKIP, NTIO, BS, MINW, GAUX, STG>
-# EPI 5 / 6 / 7 / 10 / 11 are the clover epilogues (a 6x6 block product per chirality on top of the stencil, up to 256 VGPRs + a few
+# EPI 5 / 6 / 7 / 10 / 11 / 13 are the clover epilogues (a 6x6 block product per chirality on top of the stencil, up to 256 VGPRs + a few
 # AGPRs) and TSKIP 2 is the per-lane form of ragged test lattices: those are held to "no scratch"; everything else to "no scratch" and
 # three waves per SIMD.
-CLOVER_EPI = {5, 6, 7, 10, 11}
+CLOVER_EPI = {5, 6, 7, 10, 11, 13}
 RULES = [
     # fp64, large lattices: the LDS-staged kernel, __launch_bounds__(256, 3) for the twisted-mass epilogues, (256, 1) for the clover ones
     (r"^void hop64::hop_kernel<(\d+), ([013]), true, 256, (3|1), -1, 64>", "fp64 staged"),
+    # the shifted residual epilogue of the multi-shift CG (EPI 12, mms.hip) in the gather kernel: one more field than its sibling EPI 9
+    # (190 VGPRs, two waves per SIMD); its staged form above keeps three
+    (r"^void hop64::hop_kernel<12, 0, true, (64|256), 1, (-1|-2), 0>", "fp64 gather shifted res", 2),
     # fp64, small lattices and ragged shapes: the gather kernel
     (r"^void hop64::hop_kernel<(\d+), ([0123]), true, (64|256), (1|3), (-1|-2), 0>", "fp64 gather"),
     (r"^void hop64::hop_split4_kernel<(\d+), true>", "fp64 hop-split"),
