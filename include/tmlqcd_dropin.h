@@ -272,6 +272,18 @@ void tmlqcd_hip_forget(spinor *field);             /* host memory is being freed
 void tmlqcd_hip_set_device(int device);            /* before the first call; default: $TMLQCD_HIP_DEVICE or 0 */
 void tmlqcd_hip_comm_init(const char unique_id[128]); /* ranks along T: id from tmhip_comm_get_unique_id, MPI_Bcast by the host */
 void tmlqcd_hip_finalize(void);
+/* ---- gauge monomial (monomial/gauge_monomial.c): replaces measure_gauge_action.o and measure_rectangles.o ------------------------
+ * The three measures under the reference's names, on the device links: gf must be g_gauge_field (hf->gaugefield); it is uploaded by
+ * the rule of every other entry point (g_update_gauge_copy), and in resident mode the device's newer links are measured without any
+ * transfer.  measure_gauge_action also stores its result in GaugeInfo.plaquetteEnergy (measure_gauge_action.c:187).  On T-split ranks
+ * the measures return the sum over all ranks (the reference's MPI_Allreduce); rectangles are not available there and end the program.
+ * tmlqcd_hip_gauge_derivative is the body of gauge_derivative (glambda = 0) / gauge_EMderivative with the monomial's parameters as
+ * arguments (beta = g_beta, c0 / c1 / use_rectangles / glambda of monomial_list[id]); it accumulates like tmlqcd_hip_sw_all. */
+double measure_plaquette(const su3 **const gf);                                  /* measure_gauge_action.c:46 */
+double measure_gauge_action(const su3 **const gf, const double lambda);          /* measure_gauge_action.c:108 */
+double measure_rectangles(const su3 **const gf);                                 /* measure_rectangles.c:51 */
+void tmlqcd_hip_gauge_derivative(hamiltonian_field_t *const hf, const double beta, const double c0, const double c1, const int use_rectangles, const double glambda);
+
 /* ---- ILDG gauge configurations: replaces io/gauge_read.o and io/gauge_write.o of libio.a -- */
 typedef struct { unsigned int suma, sumb; } DML_Checksum;                        /* io/dml.h:34-37 */
 typedef struct {                                                                 /* io/params.h:98-104 */

@@ -290,6 +290,20 @@ int tmhip_update_gauge(tmhip_ctx *ctx, double step);     /* update_gauge.c:51-11
 int tmhip_multi_update_gauge(int n, tmhip_ctx **ctxs, double step);   /* the same for n contexts of one process holding a T-split lattice (peer copies) */
 int tmhip_gauge_download(tmhip_ctx *ctx, void *host_gauge);   /* [VOLUMEPLUSRAND][4] su3, e.g. at the end of a trajectory */
 
+/* ---- gauge monomial on the device-resident links (monomial/gauge_monomial.c; gauge.hip) --------------------------------
+ * tmhip_gauge_derivative ADDS gauge_derivative (glambda = 0) / gauge_EMderivative of the reference to the derivative accumulator of
+ * tmhip_deriv_Sb / tmhip_sw_all (created and zeroed if no force has done so yet): for every link factor trlambda(U staple^dagger) with
+ * the plaquette staples (get_staples.c; planes with direction 0 weighted 1 + glambda, spatial planes 1 - glambda) and, with
+ * use_rectangles, the rectangle staples (get_rectangle_staples.c) weighted factor c1 / c0; factor = -c0 beta / 3 with rectangles,
+ * -beta / 3 without.  The three measures return this rank's share (sites of the local VOLUME) of measure_plaquette /
+ * measure_gauge_action / measure_rectangles, i.e. the value before the reference's MPI_Allreduce (option "gauge_global_sums" 1: after it).  All four need the resident links
+ * (tmhip_set_gauge); two calls on the same links give bit-identical results.  T-split ranks (nproc_t > 1): the plaquette force and sums
+ * use the one-deep halo slabs tmhip_update_gauge keeps current; rectangles reach two slices deep and return non-zero there. */
+int tmhip_gauge_derivative(tmhip_ctx *ctx, double beta, double c0, double c1, int use_rectangles, double glambda);
+int tmhip_measure_plaquette(tmhip_ctx *ctx, double *out);
+int tmhip_measure_gauge_action(tmhip_ctx *ctx, double glambda, double *out);
+int tmhip_measure_rectangles(tmhip_ctx *ctx, double *out);
+
 /* ---- ILDG gauge configurations (io/gauge_read.c:28-198, io/gauge_read_binary.c:140-200, io/gauge_write.c:22-59,
  *      io/gauge_write_binary.c:150-175, io/dml.c:49-60).  The "ildg-binary-data" record travels to / from the device as it lies in
  *      the file; byte swap, 32 <-> 64 bit conversion, site and link re-ordering and the SciDAC checksum happen in HBM (ildg.hip). -- */
@@ -407,6 +421,8 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                (alpha) and the (P, p) kernel (stopping test, beta) instead of two one-block sum + scalar kernels in between
  *   "nd_fused" 1 (default) | 0: the doublet operators (tmhip_*_ndpsi, the nd solvers) -- 1: one stencil per hop for both flavours with the
  *                flavour mixing in its epilogue; 0: two single-flavour stencils per hop and a mixing pass
+ *   "gauge_global_sums" 0 (default) | 1: tmhip_measure_plaquette / _gauge_action / _rectangles return the rank's own share (0: the reference's value
+ *                before its MPI_Allreduce) or the sum over the ranks of a T split (1: its return value; needs the communicator, like parallel = 1)
  *   "cg_sync" 1: host-side scalars as in the reference loop;  "cg_batch" n: iterations enqueued between two polls of `done`
  *   "gauge_cache" -1 (automatic) / 0 / 1: the 64-thread stencil launches of small unsplit lattices, and the stencil launches of a T-split rank,
  *                  load the links with (0) or without (1) the streaming hint; automatic = without while the gauge copy is <= 200 MB (it then

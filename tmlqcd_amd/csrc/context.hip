@@ -322,6 +322,7 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "cg_self")) ctx->opt_cg_self = value != 0;
   else if (!strcmp(name, "cg_sync")) ctx->opt_cg_sync = value;
   else if (!strcmp(name, "nd_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_fused must be 0 (two single-flavour stencils + a mixing pass) or 1 (doublet stencil)"); ctx->opt_nd_fused = value; }
+  else if (!strcmp(name, "gauge_global_sums")) { if (value < 0 || value > 1) TMHIP_FAIL("gauge_global_sums must be 0 (the rank's share) or 1 (summed over the ranks)"); ctx->opt_gauge_global_sums = value; }
   else if (!strcmp(name, "cg_batch")) ctx->opt_cg_batch = value > 0 ? value : 1;
   else TMHIP_FAIL("unknown option %s", name);
   return 0;

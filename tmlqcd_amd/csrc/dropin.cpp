@@ -1737,6 +1737,50 @@ void tmlqcd_hip_flush_derivative(hamiltonian_field_t *const hf) {
   g_deriv_pending = false;
 }
 
+// ------------------------------------------------------------------ gauge monomial
+extern paramsGaugeInfo GaugeInfo;   /* defined with read_gauge_field below */
+/* measure_gauge_action.c:46-189, measure_rectangles.c:51-140 on the device links: gf must be the field this library mirrors
+ * (g_gauge_field, which hf->gaugefield points to); it goes up by the rules of every other entry point (refresh), and in resident mode
+ * the device's own, newer links are the ones measured.  T-split ranks: the three measures return the sum over all ranks, the same
+ * bits on every rank, as the reference does after its MPI_Allreduce (the core entry points return the rank's share unless told so);
+ * measure_rectangles and a rectangle force end the program there (the device holds a one-deep link halo). */
+static tmhip_ctx *gauge_links(const su3 **const gf, const char *who) {
+  if (!gf || &gf[0][0] != &g_gauge_field[0][0]) die(who);
+  tmhip_ctx *c = refresh(true);
+  CK(tmhip_set_option(c, "gauge_global_sums", 1));
+  return c;
+}
+double measure_plaquette(const su3 **const gf) {
+  tmhip_ctx *c = gauge_links(gf, "measure_plaquette: gf is not g_gauge_field");
+  double r = 0.0;
+  CK(tmhip_measure_plaquette(c, &r));
+  return r;
+}
+double measure_gauge_action(const su3 **const gf, const double lambda) {
+  tmhip_ctx *c = gauge_links(gf, "measure_gauge_action: gf is not g_gauge_field");
+  double r = 0.0;
+  CK(tmhip_measure_gauge_action(c, lambda, &r));
+  GaugeInfo.plaquetteEnergy = r;                                  /* measure_gauge_action.c:187 */
+  return r;
+}
+double measure_rectangles(const su3 **const gf) {
+  tmhip_ctx *c = gauge_links(gf, "measure_rectangles: gf is not g_gauge_field");
+  double r = 0.0;
+  CK(tmhip_measure_rectangles(c, &r));
+  return r;
+}
+/* gauge_derivative / gauge_EMderivative (monomial/gauge_monomial.c:48-162) with the monomial's parameters as arguments; accumulates
+ * like tmlqcd_hip_sw_all: into hf->derivative before returning (coherent), or held on the device until tmlqcd_hip_flush_derivative /
+ * tmlqcd_hip_update_momenta (resident) */
+void tmlqcd_hip_gauge_derivative(hamiltonian_field_t *const hf, const double beta, const double c0, const double c1, const int use_rectangles,
+                                 const double glambda) {
+  tmhip_ctx *c = gauge_links((const su3 **)hf->gaugefield, "tmlqcd_hip_gauge_derivative: hf->gaugefield is not g_gauge_field");
+  if (!g_deriv_pending) CK(tmhip_derivative_zero(c));
+  CK(tmhip_gauge_derivative(c, beta, c0, c1, use_rectangles, glambda));
+  g_deriv_pending = true;
+  if (g_mode != TMLQCD_HIP_RESIDENT) tmlqcd_hip_flush_derivative(hf);
+}
+
 // ------------------------------------------------------------------ molecular dynamics with the links in HBM
 /* update_gauge(step, hf) (update_gauge.c:51-110): U <- restoresu3(exposu3(step P)) U for every link, on the device-resident
  * links; the stencil's gauge copy is re-sorted there too (update_backward_gauge.c:185-242), so an MD step moves no gauge

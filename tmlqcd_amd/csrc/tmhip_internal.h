@@ -162,6 +162,7 @@ struct tmhip_ctx {
   int opt_cg_sync, opt_cg_batch, opt_cg_fused_dot, opt_cg_self;         // cg_her
   int opt_swall_order;                                                  // block order of the owner-computes sw_all: 0 one contiguous chunk per XCD, 1 slab order, 2 tile order (default; 4 / 8: x-planes per tile)
   int opt_swterm_order;                                                 // block order of sw_term: 0 one contiguous chunk per XCD, 1 (default) tiles walked through all time-slices
+  int opt_gauge_global_sums;                                            // 1: the gauge measures (gauge.hip) return the sum over all ranks of a T split instead of the rank's share (default 0)
   int opt_nd_fused;                                                     // 1 (default): doublet stencil with fused mixing (nd.hip); 0: two single-flavour stencils + a mixing pass
   // non-degenerate doublet (nd.hip): g_mubar, g_epsbar (global.h:202), phmc_invmaxev (phmc.h:31); work fields and solver state
   double mubar, epsbar, invmaxev;

@@ -95,6 +95,8 @@ def load_library():
         "tmhip_sw_term": [vp, vp, d, d],
         "tmhip_momenta_upload": [vp, vp], "tmhip_momenta_download": [vp, vp], "tmhip_update_momenta": [vp, d],
         "tmhip_update_gauge": [vp, d], "tmhip_gauge_download": [vp, vp],
+        "tmhip_gauge_derivative": [vp, d, d, d, i, d],
+        "tmhip_measure_plaquette": [vp, pd], "tmhip_measure_gauge_action": [vp, d, pd], "tmhip_measure_rectangles": [vp, pd],
         "tmhip_gauge_unpack_ildg": [vp, vp, i, C.POINTER(C.c_uint)], "tmhip_gauge_pack_ildg": [vp, vp, i, C.POINTER(C.c_uint)],
         "tmhip_read_gauge_field": [vp, C.c_char_p, i, i, vp, C.POINTER(GaugeInfo)],
         "tmhip_write_gauge_field": [vp, C.c_char_p, i, C.c_char_p, C.POINTER(C.c_uint)],
@@ -393,6 +395,26 @@ class Lattice:
         out = np.zeros((self.VPR, 4, 3, 3, 2))
         _ck(self.lib.tmhip_gauge_download(self.h, _hp(out)), "tmhip_gauge_download")
         return out
+
+    # --- gauge monomial on the resident links (monomial/gauge_monomial.c, measure_gauge_action.c, measure_rectangles.c) ---
+    def gauge_derivative(self, beta, c0=1.0, c1=0.0, use_rectangles=False, glambda=0.0):
+        """gauge_derivative / gauge_EMderivative (glambda != 0): added to the device-resident derivative field."""
+        _ck(self.lib.tmhip_gauge_derivative(self.h, beta, c0, c1, 1 if use_rectangles else 0, glambda), "gauge_derivative")
+
+    def measure_plaquette(self):
+        out = C.c_double(0.0)
+        _ck(self.lib.tmhip_measure_plaquette(self.h, C.byref(out)), "measure_plaquette")
+        return out.value
+
+    def measure_gauge_action(self, glambda=0.0):
+        out = C.c_double(0.0)
+        _ck(self.lib.tmhip_measure_gauge_action(self.h, glambda, C.byref(out)), "measure_gauge_action")
+        return out.value
+
+    def measure_rectangles(self):
+        out = C.c_double(0.0)
+        _ck(self.lib.tmhip_measure_rectangles(self.h, C.byref(out)), "measure_rectangles")
+        return out.value
 
     # ---- ILDG gauge configurations (io/gauge_read.c, io/gauge_write.c; ildg.hip)
     def gauge_unpack_ildg(self, file_bytes, prec):

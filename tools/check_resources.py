@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt
+    check_resources.py [--table OUT.txt] lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt
 """
 import re
 import subprocess
@@ -41,6 +41,9 @@ RULES = [
     # the two plaquette-leaf kernels of the clover rows (interior instances): 230 - 254 VGPRs by design, two waves per SIMD, no scratch
     (r"^void sw_term_kernel<SwFastLd>", "sw_term", 2),
     (r"^void sw_all_gather_kernel<SwFastLd>", "sw_all gather", 2),
+    # the gauge monomial (gauge.hip): four to five 3x3 complex matrices live per link, no scratch, two waves per SIMD
+    (r"^void gaugehip::gauge_force_kernel<(true|false)>", "gauge force", 2),
+    (r"^(void )?gaugehip::(plaquette|rectangle)_sum_kernel", "gauge action", 2),
 ]
 
 
