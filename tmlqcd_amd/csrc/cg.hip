@@ -6,6 +6,10 @@
 // host only enqueues kernels.  Exactness is preserved by a device-side `done` flag: once the test of
 // cg_her.c:108 fires, all later updates of P / sf0 / sf2 are skipped, so P and the iteration count
 // are those of the sequential algorithm even though the host polls `done` only every few iterations.
+//
+// Shared by the three solvers of this file (cg_her, mixed_cg_her, rg_mixed_cg_her): the polling loop (tmhip_poll_loop,
+// tmhip_internal.h -- also the loop of nd.hip and mms.hip), the iteration with the vector updates in kernels of their own
+// (cg_enqueue_iteration) and the iteration with everything in stencil epilogues (cg_enqueue_fused_qtm).
 #include "tmhip_internal.h"
 
 static inline v4f *F4(tmhip_field *f) { return reinterpret_cast<v4f *>(f->d32); }   // fp32 field as six float4 planes
@@ -31,16 +35,9 @@ static int cg_state_alloc(tmhip_ctx *ctx) {
   return 0;
 }
 
-
-__device__ __forceinline__ double cg_wave_reduce(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __device__ __forceinline__ void cg_block_reduce_store(double v, double *partials) {
   __shared__ double wsum[LA_BS / 64];
-  v = cg_wave_reduce(v);
+  v = tmhip_wave_sum(v);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) wsum[w] = v;
   __syncthreads();
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(CG_SUM_BS) void cg_sum_kernel(const double *__restr
   __shared__ double sm[CG_SUM_BS / 64];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += CG_SUM_BS) acc += partials[i];
-  acc = cg_wave_reduce(acc);
+  acc = tmhip_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -289,7 +286,7 @@ __global__ __launch_bounds__(CG_SUM_BS) void cg_sum_scalar_kernel(const double *
   if (lw >= 0 && lw < NW) reinterpret_cast<double *>(&ls)[lw] = reinterpret_cast<const double *>(st)[lw];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += CG_SUM_BS) acc += partials[i];
-  acc = cg_wave_reduce(acc);                       // fixed order: strided per-lane sums, butterfly per wave, then the 16 wave sums
+  acc = tmhip_wave_sum(acc);                       // fixed order: strided per-lane sums, butterfly per wave, then the 16 wave sums
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (ls.done) { if (WHICH == 0 && threadIdx.x == 0) st->x_pending = 0; return; }   // block-uniform
@@ -316,7 +313,7 @@ __global__ __launch_bounds__(CG_SUM_BS) void cg_sum_xsum_scalar_kernel(const dou
   if (lw >= 0 && lw < NW) reinterpret_cast<double *>(&ls)[lw] = reinterpret_cast<const double *>(st)[lw];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += CG_SUM_BS) acc += partials[i];
-  acc = cg_wave_reduce(acc);
+  acc = tmhip_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
   __syncthreads();
   // `done` is a function of global sums: the same on every rank, so a reduction that is skipped is skipped by everybody (its number with it)
@@ -475,6 +472,65 @@ static int cg_enqueue_fused_qtm(tmhip_ctx *ctx, bool fp32, tmhip_field *x, tmhip
   return 0;
 }
 
+// One CG iteration with the vector updates in kernels of their own, enqueued on ctx->stream, fp32 or fp64 fields:
+// q = A p ; alpha ; x += alpha p ; r -= alpha q ; rho ; beta ; p = beta p + r   (cg_her.c:91-126).  f.q and f.r swap roles each
+// iteration as sf[0] / sf[1] do in the reference.  The single enqueue of this iteration: cg_her (every form but its default
+// cg_enqueue_fused_qtm), the inner loop of mixed_cg_her and both inner loops of rg_mixed_cg_her.
+//   fp32, fused, cg_fused_dot >= 2 : cg_enqueue_fused_qtm
+//   fused (Qtm_pm_psi)             : <p, A p> accumulated by the last stencil's epilogue (cg_fused_dot = 1; fp64: unsplit only)
+//   otherwise                      : the operator, then cg_dot_kernel
+// hist / hist_len: the residual history of cg_her (nullptr, 0: none).
+struct CgFields { tmhip_field *x, *p, *q, *r; };
+
+static int cg_enqueue_iteration(tmhip_ctx *ctx, int op, bool fp32, bool fused, CgFields &f, CgState *st, int N, double *hist = nullptr,
+                                int hist_len = 0) {
+  const dim3 g = fp32 ? la_grid32(N) : la_grid(N);
+  const int nblk = g.x * g.y;
+  const double mu = ctx->mu, nrm = 1. / (1. + mu * mu);
+  int ndot = nblk;
+  if (fp32 && fused && ctx->opt_cg_fused_dot >= 2) return cg_enqueue_fused_qtm(ctx, true, f.x, f.p, f.r, st, hist, hist_len, N, op == TMHIP_OP_QSW_PM);
+  if (fp32) {
+    if (op == TMHIP_OP_QSW_PM) {
+      if (tmhip_Qsw_pm_psi_32(ctx, f.q, f.p)) return 1;
+      hipLaunchKernelGGL(cg_dot_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, (const v4f *)F4(f.p), (const v4f *)F4(f.q), f.p->ns, N, ctx->partials, st);
+    } else {
+      v2f *s0 = ctx->scratch32[0]->d32, *s1 = ctx->scratch32[1]->d32;
+      if (tmhip_launch_hopping32(ctx, TMHIP_EO, s1, f.p->d32, nullptr, EPI_TM_TIMES, nrm, nrm * mu, true)) return 1;
+      if (tmhip_launch_hopping32(ctx, TMHIP_OE, s0, s1, f.p->d32, EPI_TM_SUB_G5, 1., -mu, true)) return 1;
+      if (tmhip_launch_hopping32(ctx, TMHIP_EO, s1, s0, nullptr, EPI_TM_TIMES, nrm, -nrm * mu, true)) return 1;
+      if (fused) {
+        if (tmhip_launch_hopping_dot32(ctx, TMHIP_OE, f.q->d32, s1, s0, f.p->d32, 1., mu, &ndot)) return 1;
+      } else {
+        if (tmhip_launch_hopping32(ctx, TMHIP_OE, f.q->d32, s1, s0, EPI_TM_SUB_G5, 1., mu, true)) return 1;
+        hipLaunchKernelGGL(cg_dot_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, (const v4f *)F4(f.p), (const v4f *)F4(f.q), f.p->ns, N, ctx->partials, st);
+      }
+    }
+  } else if (fused) {   // Qtm_pm_psi (tm_operators.c:338-345) with pro = <p, Q p> accumulated by the last stencil's epilogue
+    v2d *s0 = ctx->scratch[0]->d, *s1 = ctx->scratch[1]->d;
+    if (tmhip_launch_hopping(ctx, TMHIP_EO, s1, f.p->d, nullptr, EPI_TM_TIMES, nrm, nrm * mu, true)) return 1;
+    if (tmhip_launch_hopping(ctx, TMHIP_OE, s0, s1, f.p->d, EPI_TM_SUB_G5, 1., -mu, true)) return 1;
+    if (tmhip_launch_hopping(ctx, TMHIP_EO, s1, s0, nullptr, EPI_TM_TIMES, nrm, -nrm * mu, true)) return 1;
+    if (tmhip_launch_hopping_dot(ctx, TMHIP_OE, f.q->d, s1, s0, f.p->d, 1., mu, &ndot)) return 1;
+  } else {
+    if (tmhip_apply_op(ctx, op, f.q, f.p)) return 1;
+    hipLaunchKernelGGL(cg_dot_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, f.p->d, f.q->d, f.p->ns, N, ctx->partials, st);
+  }
+  if (cg_reduce_update<0>(ctx, ndot, st, hist, hist_len)) return 1;
+  if (fp32)
+    hipLaunchKernelGGL(cg_update_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, F4(f.x), (const v4f *)F4(f.p), F4(f.q), (const v4f *)F4(f.r),
+                       f.x->ns, N, ctx->partials, st);
+  else
+    hipLaunchKernelGGL(cg_update_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, f.x->d, (const v2d *)f.p->d, f.q->d, (const v2d *)f.r->d, f.x->ns, N,
+                       ctx->partials, st);
+  if (cg_reduce_update<1>(ctx, nblk, st, hist, hist_len)) return 1;
+  if (fp32)
+    hipLaunchKernelGGL(cg_xpay_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, F4(f.p), (const v4f *)F4(f.q), f.p->ns, N, st);
+  else
+    hipLaunchKernelGGL(cg_xpay_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, f.p->d, (const v2d *)f.q->d, f.p->ns, N, st);
+  tmhip_field *t = f.q; f.q = f.r; f.r = t;   // the new residual now sits in the former q
+  return 0;
+}
+
 extern "C" int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec, int N,
                             int op, int *iters, double *res_hist, int hist_len) {
   if (!P || !Q || P->kind != TMHIP_FIELD_EO || Q->kind != TMHIP_FIELD_EO) TMHIP_FAIL("cg_her needs one-parity (EO) fields");
@@ -489,7 +545,7 @@ extern "C" int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int 
     ctx->cg_hist_len = max_iter;
   }
   CgState *st = (CgState *)ctx->cg_state;
-  tmhip_field *sf0 = ctx->sf[0], *sf1 = ctx->sf[1], *sf2 = ctx->sf[2], *stmp;
+  tmhip_field *sf0 = ctx->sf[0], *sf1 = ctx->sf[1], *sf2 = ctx->sf[2];
   // initial residual (cg_her.c:82-88): once per solve, host-visible scalars are fine here
   CgState h;
   memset(&h, 0, sizeof(h));
@@ -500,8 +556,6 @@ extern "C" int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int 
   if (tmhip_square_norm(ctx, sf1, N, 1, &h.normsq)) return 1;
   h.eps_sq = eps_sq; h.rel_prec = rel_prec;
   TMHIP_CHECK(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  const dim3 g = la_grid(N);
-  const int nblk = g.x * g.y;
   const int batch = ctx->opt_cg_batch > 0 ? ctx->opt_cg_batch : 4;
   const bool split = ctx->g.nproc_t > 1 || ctx->loopback;   // T-split rank (or its single-rank rehearsal): reductions fused into the interior + boundary kernels
   const bool fusable = ctx->opt_cg_fused_dot && ctx->Vh % (split ? 256 : tmhip_hop_block(ctx)) == 0 &&
@@ -512,50 +566,15 @@ extern "C" int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int 
   // read / written alternately: iteration j reads copy j & 1); "cg_self" 0 keeps the sum + scalar kernels
   const bool self = fused_full && !split && op == TMHIP_OP_QTM_PM && ctx->opt_cg_self && tmhip_hopping_self_alpha_ok(ctx);
   if (self) TMHIP_CHECK(hipMemcpyAsync(st + 1, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  int enq = 0, done = 0;
-  int *flag = (int *)(ctx->result_host + 2);
-  double *err_host = ctx->result_host + 3;
   const double target = rel_prec == 1 ? eps_sq * h.squarenorm : eps_sq;
-  bool near = false;   // within 10^3 of the target: poll every iteration so that no stencil is enqueued past convergence
-  while (enq < max_iter && !done) {
-    const int want = near ? 1 : batch;
-    const int nb = (max_iter - enq) < want ? (max_iter - enq) : want;
-    for (int b = 0; b < nb; b++) {
-      int ndot = nblk;
-      if (fused_full) {   // default: everything but the (P, p) update rides in stencil epilogues
-        if (cg_enqueue_fused_qtm(ctx, false, P, sf2, sf1, st, ctx->cg_hist, max_iter, N, op == TMHIP_OP_QSW_PM, self ? ((enq + b) & 1) : -1)) return 1;
-        continue;
-      }
-      if (fused) {
-        // Qtm_pm_psi (tm_operators.c:338-345) with pro = <sf2, Q sf2> accumulated by the last stencil's epilogue
-        const double mu = ctx->mu, nrm = 1. / (1. + mu * mu);
-        tmhip_field *s0 = ctx->scratch[0], *s1 = ctx->scratch[1];
-        if (tmhip_launch_hopping(ctx, TMHIP_EO, s1->d, sf2->d, nullptr, EPI_TM_TIMES, nrm, nrm * mu, true)) return 1;
-        if (tmhip_launch_hopping(ctx, TMHIP_OE, s0->d, s1->d, sf2->d, EPI_TM_SUB_G5, 1., -mu, true)) return 1;
-        if (tmhip_launch_hopping(ctx, TMHIP_EO, s1->d, s0->d, nullptr, EPI_TM_TIMES, nrm, -nrm * mu, true)) return 1;
-        if (tmhip_launch_hopping_dot(ctx, TMHIP_OE, sf0->d, s1->d, s0->d, sf2->d, 1., mu, &ndot)) return 1;
-      } else {
-        if (tmhip_apply_op(ctx, op, sf0, sf2)) return 1;
-        hipLaunchKernelGGL(cg_dot_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, sf2->d, sf0->d, sf2->ns, N, ctx->partials, st);
-      }
-      if (cg_reduce_update<0>(ctx, ndot, st, ctx->cg_hist, max_iter)) return 1;
-      hipLaunchKernelGGL(cg_update_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, P->d, sf2->d, sf0->d, sf1->d, P->ns, N, ctx->partials, st);
-      if (cg_reduce_update<1>(ctx, nblk, st, ctx->cg_hist, max_iter)) return 1;
-      hipLaunchKernelGGL(cg_xpay_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, sf2->d, sf0->d, sf2->ns, N, st);
-      stmp = sf0; sf0 = sf1; sf1 = stmp;
-    }
-    enq += nb;
-    if (self) st = (CgState *)ctx->cg_state + (enq & 1);   // the copy the last enqueued iteration wrote
-    TMHIP_CHECK(hipGetLastError());
-    TMHIP_CHECK(hipMemcpyAsync(flag, &st->done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipMemcpyAsync(err_host, &st->err, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    done = *flag;
-    if (tmhip_check_async_error(ctx)) return 1;   // T-split rank: a halo exchange that never completed must not yield a result
-    near = *err_host <= 1.0e3 * target;
-    if (self) st = (CgState *)ctx->cg_state;       // (cg_enqueue_fused_qtm takes the base of the pair)
-  }
-  if (self) st = (CgState *)ctx->cg_state + (enq & 1);
+  CgFields f = {P, sf2, sf0, sf1};
+  int enq = 0;
+  if (tmhip_poll_loop(ctx, max_iter, true, batch, 1.0e3 * target, &st->done, &st->err, self ? sizeof(CgState) : 0, true, [&](int k) {
+        // default: everything but the (P, p) update rides in stencil epilogues
+        if (fused_full) return cg_enqueue_fused_qtm(ctx, false, P, sf2, sf1, st, ctx->cg_hist, max_iter, N, op == TMHIP_OP_QSW_PM, self ? (k & 1) : -1);
+        return cg_enqueue_iteration(ctx, op, false, fused, f, st, N, ctx->cg_hist, max_iter);
+      }, &enq)) return 1;
+  if (self) st += enq & 1;   // the copy the last enqueued iteration wrote
   TMHIP_CHECK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   *iters = h.done ? h.iters : -1;
@@ -590,71 +609,27 @@ extern "C" int tmhip_mixed_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q
   sqnrm_d = sourcesquarenorm;
   if (tmhip_assign(ctx, delta, Q, N)) return 1;
   if (tmhip_field_zero(ctx, P)) return 1;
-  const dim3 g = la_grid32(N);   // every field kernel of the inner loop works on fp32 fields
-  const int nblk = g.x * g.y;
-  int *flag = (int *)(ctx->result_host + 2);
   const int batch = ctx->opt_cg_batch > 0 ? ctx->opt_cg_batch : 4;
   const bool split = ctx->g.nproc_t > 1 || ctx->loopback;
   const bool fused = ctx->opt_cg_fused_dot && tmhip_fused_dot32_ok(ctx) && (!split || ctx->opt_cg_fused_dot >= 2);   // the older mode-0 fusion is unsplit only
-  const double mu = ctx->mu, nrm = 1. / (1. + mu * mu);
   int iter = 0;
   ctx->mixed_trace_n = 0;
   for (int i = 0; i < N_outer; i++) {
-    tmhip_field *sf0 = ctx->sf32[0], *sf1 = ctx->sf32[1], *sf2 = ctx->sf32[2], *stmp;
     if (tmhip_field_zero(ctx, x)) return 1;
-    if (tmhip_assign_to_32(ctx, sf1, delta, N)) return 1;
-    if (tmhip_assign_to_32(ctx, sf2, delta, N)) return 1;
+    if (tmhip_assign_to_32(ctx, ctx->sf32[1], delta, N)) return 1;
+    if (tmhip_assign_to_32(ctx, ctx->sf32[2], delta, N)) return 1;
     CgState h;
     memset(&h, 0, sizeof(h));
     h.normsq = (double)(float)sqnrm_d; h.sqnrm_outer = h.normsq; h.squarenorm = sourcesquarenorm;
     h.eps_sq = eps_sq; h.rel_prec = rel_prec; h.inner = 1; h.max_inner = max_inner_it; h.innereps = innereps;
     TMHIP_CHECK(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-    int done = 0, enq = 0;
     // the inner loops are short (a handful of iterations each): poll every iteration once the residual is within 10^3 of
     // whichever stopping rule of mixed_cg_her.c:141 is closer, so that no stencil is enqueued past the restart
-    double *err_host = ctx->result_host + 3;
     const double t_outer = (rel_prec == 1 ? eps_sq * sourcesquarenorm : eps_sq) / 1.3, t_inner = innereps * h.sqnrm_outer;
     const double tgt = t_inner > t_outer ? t_inner : t_outer;
-    bool near = false;
-    while (!done && enq <= max_inner_it) {
-      const int want = near ? 1 : batch;
-      for (int b = 0; b < want; b++) {
-        int ndot = nblk;
-        v2f *s0 = ctx->scratch32[0]->d32, *s1 = ctx->scratch32[1]->d32;
-        if (fused && ctx->opt_cg_fused_dot >= 2) {
-          if (cg_enqueue_fused_qtm(ctx, true, x, sf2, sf1, st, (double *)nullptr, 0, N, clover)) return 1;
-          continue;
-        }
-        if (clover) {
-          if (tmhip_Qsw_pm_psi_32(ctx, sf0, sf2)) return 1;
-          hipLaunchKernelGGL(cg_dot_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, (const v4f *)F4(sf2), (const v4f *)F4(sf0), sf2->ns, N, ctx->partials, st);
-        } else {
-        if (tmhip_launch_hopping32(ctx, TMHIP_EO, s1, sf2->d32, nullptr, EPI_TM_TIMES, nrm, nrm * mu, true)) return 1;
-        if (tmhip_launch_hopping32(ctx, TMHIP_OE, s0, s1, sf2->d32, EPI_TM_SUB_G5, 1., -mu, true)) return 1;
-        if (tmhip_launch_hopping32(ctx, TMHIP_EO, s1, s0, nullptr, EPI_TM_TIMES, nrm, -nrm * mu, true)) return 1;
-        if (fused) {
-          if (tmhip_launch_hopping_dot32(ctx, TMHIP_OE, sf0->d32, s1, s0, sf2->d32, 1., mu, &ndot)) return 1;
-        } else {
-          if (tmhip_launch_hopping32(ctx, TMHIP_OE, sf0->d32, s1, s0, EPI_TM_SUB_G5, 1., mu, true)) return 1;
-          hipLaunchKernelGGL(cg_dot_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, (const v4f *)F4(sf2), (const v4f *)F4(sf0), sf2->ns, N, ctx->partials, st);
-        }
-        }
-        if (cg_reduce_update<0>(ctx, ndot, st, (double *)nullptr, 0)) return 1;
-        hipLaunchKernelGGL(cg_update_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, F4(x), (const v4f *)F4(sf2), F4(sf0), (const v4f *)F4(sf1),
-                           x->ns, N, ctx->partials, st);
-        if (cg_reduce_update<1>(ctx, nblk, st, (double *)nullptr, 0)) return 1;
-        hipLaunchKernelGGL(cg_xpay_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, F4(sf2), (const v4f *)F4(sf0), sf2->ns, N, st);
-        stmp = sf0; sf0 = sf1; sf1 = stmp;
-      }
-      enq += want;
-      TMHIP_CHECK(hipGetLastError());
-      TMHIP_CHECK(hipMemcpyAsync(flag, &st->done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-      TMHIP_CHECK(hipMemcpyAsync(err_host, &st->err, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-      TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      done = *flag;
-    if (tmhip_check_async_error(ctx)) return 1;   // T-split rank: a halo exchange that never completed must not yield a result
-      near = *err_host <= 1.0e3 * tgt;
-    }
+    CgFields f = {x, ctx->sf32[2], ctx->sf32[0], ctx->sf32[1]};
+    if (tmhip_poll_loop(ctx, max_inner_it, false, batch, 1.0e3 * tgt, &st->done, &st->err, 0, true,
+                        [&](int) { return cg_enqueue_iteration(ctx, op, true, fused, f, st, N); })) return 1;
     TMHIP_CHECK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (!h.done) TMHIP_FAIL("mixed_cg_her: inner loop did not terminate");
@@ -686,54 +661,8 @@ extern "C" int tmhip_mixed_cg_restarts(tmhip_ctx *ctx, int *inner_iters, int cap
 }
 
 // ------------------------------------------------------------------ reliable-update mixed CG
-// One CG iteration enqueued on ctx->stream, fp32 or fp64 fields: q = A p ; alpha ; x += alpha p ; r -= alpha q ;
-// rho ; beta ; p = beta p + r.   f.q and f.r swap roles each iteration exactly as sf[0]/sf[1] do in tmhip_cg_her.
-struct RgFields { tmhip_field *x, *p, *q, *r; };
-
-static int rg_enqueue_iteration(tmhip_ctx *ctx, int op, bool fp32, bool fused, RgFields &f, CgState *st, int N) {
-  const dim3 g = fp32 ? la_grid32(N) : la_grid(N);
-  const int nblk = g.x * g.y;
-  const double mu = ctx->mu, nrm = 1. / (1. + mu * mu);
-  int ndot = nblk;
-  if (fp32 && fused && ctx->opt_cg_fused_dot >= 2) return cg_enqueue_fused_qtm(ctx, true, f.x, f.p, f.r, st, (double *)nullptr, 0, N, op == TMHIP_OP_QSW_PM);
-  if (fp32) {
-    if (op == TMHIP_OP_QSW_PM) {
-      if (tmhip_Qsw_pm_psi_32(ctx, f.q, f.p)) return 1;
-      hipLaunchKernelGGL(cg_dot_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, (const v4f *)F4(f.p), (const v4f *)F4(f.q), f.p->ns, N, ctx->partials, st);
-    } else {
-      v2f *s0 = ctx->scratch32[0]->d32, *s1 = ctx->scratch32[1]->d32;
-      if (tmhip_launch_hopping32(ctx, TMHIP_EO, s1, f.p->d32, nullptr, EPI_TM_TIMES, nrm, nrm * mu, true)) return 1;
-      if (tmhip_launch_hopping32(ctx, TMHIP_OE, s0, s1, f.p->d32, EPI_TM_SUB_G5, 1., -mu, true)) return 1;
-      if (tmhip_launch_hopping32(ctx, TMHIP_EO, s1, s0, nullptr, EPI_TM_TIMES, nrm, -nrm * mu, true)) return 1;
-      if (fused) {
-        if (tmhip_launch_hopping_dot32(ctx, TMHIP_OE, f.q->d32, s1, s0, f.p->d32, 1., mu, &ndot)) return 1;
-      } else {
-        if (tmhip_launch_hopping32(ctx, TMHIP_OE, f.q->d32, s1, s0, EPI_TM_SUB_G5, 1., mu, true)) return 1;
-        hipLaunchKernelGGL(cg_dot_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, (const v4f *)F4(f.p), (const v4f *)F4(f.q), f.p->ns, N, ctx->partials, st);
-      }
-    }
-  } else {
-    if (tmhip_apply_op(ctx, op, f.q, f.p)) return 1;
-    hipLaunchKernelGGL(cg_dot_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, f.p->d, f.q->d, f.p->ns, N, ctx->partials, st);
-  }
-  if (cg_reduce_update<0>(ctx, ndot, st, (double *)nullptr, 0)) return 1;
-  if (fp32)
-    hipLaunchKernelGGL(cg_update_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, F4(f.x), (const v4f *)F4(f.p), F4(f.q), (const v4f *)F4(f.r),
-                       f.x->ns, N, ctx->partials, st);
-  else
-    hipLaunchKernelGGL(cg_update_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, f.x->d, (const v2d *)f.p->d, f.q->d, (const v2d *)f.r->d, f.x->ns, N,
-                       ctx->partials, st);
-  if (cg_reduce_update<1>(ctx, nblk, st, (double *)nullptr, 0)) return 1;
-  if (fp32)
-    hipLaunchKernelGGL(cg_xpay_kernel<v4f>, g, dim3(LA_BS), 0, ctx->stream, F4(f.p), (const v4f *)F4(f.q), f.p->ns, N, st);
-  else
-    hipLaunchKernelGGL(cg_xpay_kernel<v2d>, g, dim3(LA_BS), 0, ctx->stream, f.p->d, (const v2d *)f.q->d, f.p->ns, N, st);
-  tmhip_field *t = f.q; f.q = f.r; f.r = t;   // the new residual now sits in the former q
-  return 0;
-}
-
 // inner_loop / inner_loop_high of rg_mixed_cg_her.c:74-176 (non-pipelined, Fletcher-Reeves beta): returns j, updates *rho1
-static int rg_inner_loop(tmhip_ctx *ctx, int op, bool fp32, bool fused, RgFields f, double *rho1, double delta, double eps_sq, int N,
+static int rg_inner_loop(tmhip_ctx *ctx, int op, bool fp32, bool fused, CgFields f, double *rho1, double delta, double eps_sq, int N,
                          int iter_base, int max_iter, int *j_out) {
   CgState *st = (CgState *)ctx->cg_state;
   CgState h;
@@ -745,29 +674,15 @@ static int rg_inner_loop(tmhip_ctx *ctx, int op, bool fp32, bool fused, RgFields
   const bool enter = fp32 ? ((float)*rho1 > (float)delta * (float)*rho1) : (*rho1 > delta * *rho1);
   if (!enter || iter_base > max_iter) return 0;
   TMHIP_CHECK(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  int *flag = (int *)(ctx->result_host + 2);
   const int batch = ctx->opt_cg_batch > 0 ? ctx->opt_cg_batch : 4;
-  int done = 0, enq = 0;
-  double *err_host = ctx->result_host + 3;
   const double t_rel = delta * *rho1, t_abs = eps_sq / 1.3;      // the two exits of rg_mixed_cg_her.c:122-145 (rhomax >= rho1)
-  const double tgt = t_rel > t_abs ? t_rel : t_abs;
-  bool near = false;                                             // as in tmhip_mixed_cg_her: poll every iteration close to the restart
-  while (!done) {
-    const int want = near ? 1 : batch;
-    for (int b = 0; b < want; b++)
-      if (rg_enqueue_iteration(ctx, op, fp32, fused, f, st, N)) return 1;
-    enq += want;
-    TMHIP_CHECK(hipGetLastError());
-    TMHIP_CHECK(hipMemcpyAsync(flag, &st->done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipMemcpyAsync(err_host, &st->err, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    done = *flag;
-    if (tmhip_check_async_error(ctx)) return 1;   // T-split rank: a halo exchange that never completed must not yield a result
-    near = *err_host <= 1.0e3 * tgt;
-    if (!done && enq > max_iter + batch) TMHIP_FAIL("rg_mixed_cg_her: inner loop did not terminate");
-  }
+  const double tgt = t_rel > t_abs ? t_rel : t_abs;              // as in tmhip_mixed_cg_her: poll every iteration close to the restart
+  // runs until `done`; the device-side test counts against max_iter itself, so more than max_iter + batch enqueued iterations is a failure
+  if (tmhip_poll_loop(ctx, max_iter + batch, false, batch, 1.0e3 * tgt, &st->done, &st->err, 0, true,
+                      [&](int) { return cg_enqueue_iteration(ctx, op, fp32, fused, f, st, N); })) return 1;
   TMHIP_CHECK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (!h.done) TMHIP_FAIL("rg_mixed_cg_her: inner loop did not terminate");
   *j_out = h.iters;
   *rho1 = h.normsq;
   return 0;
@@ -808,7 +723,7 @@ extern "C" int tmhip_rg_mixed_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field
 #define RG_SP_LOOP()                                                                                                   \
   do {                                                                                                                 \
     double rho1 = rho_sp;                                                                                              \
-    RgFields f = {x, p, q, r};                                                                                         \
+    CgFields f = {x, p, q, r};                                                                                         \
     if (rg_inner_loop(ctx, op, true, fused, f, &rho1, delta, (double)(float)target_eps_sq, N,                          \
                       iter_out + iter_in_sp + iter_in_dp, max_iter, &j)) return 1;                                     \
     rho_sp = (float)rho1; iter_in_sp += j;                                                                             \
@@ -831,7 +746,7 @@ extern "C" int tmhip_rg_mixed_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field
     }
     if (high_control == 1) {                                           /* :272-286 double precision fail-safe */
       if (tmhip_assign(ctx, phigh, rhigh, N) || tmhip_field_zero(ctx, xhigh)) return 1;
-      RgFields f = {xhigh, phigh, qhigh, rhigh};
+      CgFields f = {xhigh, phigh, qhigh, rhigh};
       if (rg_inner_loop(ctx, op, false, false, f, &rho_dp, delta, target_eps_sq, N, iter_out + iter_in_sp + iter_in_dp, max_iter, &j)) return 1;
       iter_in_dp += j;
       rho_sp = (float)rho_dp;

@@ -201,8 +201,7 @@ __global__ __launch_bounds__(256, 2) void gauge_force_kernel(const v2d *__restri
 // the library's reproducible reduction (linalg.hip): butterfly within the wave, the four wave sums added in order, one partial per block
 __device__ __forceinline__ void g_block_reduce_store(double v, double *partials) {
   __shared__ double wsum[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  v = tmhip_wave_sum(v);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];

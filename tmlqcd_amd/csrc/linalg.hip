@@ -13,16 +13,9 @@
 // sequential one, so no compensation is needed to stay within 1e-13 relative.
 #include "tmhip_internal.h"
 
-
-__device__ __forceinline__ double wave_reduce(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __device__ __forceinline__ void block_reduce_store(double v, double *partials) {
   __shared__ double wsum[LA_BS / 64];
-  v = wave_reduce(v);
+  v = tmhip_wave_sum(v);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) wsum[w] = v;
   __syncthreads();

@@ -52,8 +52,7 @@ __global__ void gauge_to32_kernel(v2f *__restrict__ d, const v2d *__restrict__ s
 
 __device__ __forceinline__ void block_reduce_store32(double v, double *partials) {
   __shared__ double wsum[LA_BS / 64];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  v = tmhip_wave_sum(v);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {

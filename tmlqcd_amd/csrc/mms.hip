@@ -15,79 +15,40 @@
 // between, and the pass knows which shifts were active when the reference updated them (`pact`: the dropped shift's P
 // HAS been updated in its last iteration, :146-153).  Other shapes take the unfused form (operator, then <p, A p> in a kernel
 // of its own, then the residual update in a kernel of its own), and Q_pm_psi on FULL fields is the composite of
-// tm_operators.c:380-388 over D_psi and gamma5 with the same passes over both halves.  All coefficients live in MmsState;
-// the host polls `done` between batches only.  Every sum is in fixed order (per-wave partials, one-block sums): bitwise
-// reproducible from run to run.
-#include "tmhip_internal.h"
-
-#define MMS_MAX_SHIFTS 32
-struct MmsState {
-  double alpha0, sigma0;                 // adjacent: the _RSH epilogue reads {alpha0, sigma0} through one pointer
-  double normsq, err, target, eps_sq, beta0;
-  int it, done, done_it, active, pact, max_iter;
-  double sigma[MMS_MAX_SHIFTS], zita[MMS_MAX_SHIFTS], zitam1[MMS_MAX_SHIFTS], alphas[MMS_MAX_SHIFTS], betas[MMS_MAX_SHIFTS];
-};
+// tm_operators.c:380-388 over D_psi and gamma5 with the same passes over both halves.  All coefficients live in a MshiftState
+// (mshift.h: the state and the recurrences, shared with nd.hip); the host polls `done` between batches only (tmhip_poll_loop,
+// tmhip_internal.h).  Every sum is in fixed order (per-wave partials, one-block sums): bitwise reproducible from run to run.
+#include "mshift.h"
 
 namespace {
 
 __device__ __forceinline__ double mms_dot(v2d a, v2d b) { return a.x * b.x + a.y * b.y; }
 
-// fixed-order sum of n values by one block of 256 threads (every thread gets the total)
-__device__ __forceinline__ double mms_block_sum(const double *__restrict__ v, int n) {
+// pro = <p, M p> + sigma0 |p|^2 (cg_mms_tm.c:115-118), then the alpha step
+__global__ __launch_bounds__(256) void mms_alpha_kernel(MshiftState *st, const double *part_pro, int n_pro, const double *part_pp, int n_pp) {
   __shared__ double ws[4];
-  return tmhip_block_sum256(v, n, ws);
-}
-
-__device__ __forceinline__ void mms_wave_partial(double d, double *partials, int slot) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
-  if ((threadIdx.x & 63) == 0) partials[slot] = d;
-}
-
-// pro = <p, M p> + sigma0 |p|^2 (cg_mms_tm.c:115-118), alphas[0] (:125) and the recurrences of the active shifts (:127-140)
-__global__ __launch_bounds__(256) void mms_alpha_kernel(MmsState *st, const double *part_pro, int n_pro, const double *part_pp, int n_pp) {
-  const double pro_m = mms_block_sum(part_pro, n_pro);
+  const double pro_m = tmhip_block_sum256(part_pro, n_pro, ws);
   __syncthreads();
-  const double pp = mms_block_sum(part_pp, n_pp);
+  const double pp = tmhip_block_sum256(part_pp, n_pp, ws);
   if (threadIdx.x != 0 || st->done) return;
-  const double pro = pro_m + st->sigma0 * pp;
-  const double alpham1 = st->alpha0;
-  const double a0 = st->normsq / pro;
-  st->alpha0 = a0;
-  const double b0 = st->beta0;   // the previous iteration's beta (0 at the start)
-  for (int im = 1; im < st->active; im++) {
-    const double gamma = st->zita[im] * alpham1 / (a0 * b0 * (1. - st->zita[im] / st->zitam1[im]) + alpham1 * (1. + st->sigma[im] * a0));
-    st->zitam1[im] = st->zita[im];
-    st->zita[im] = gamma;
-    st->alphas[im] = a0 * st->zita[im] / st->zitam1[im];
-  }
+  mshift_alpha_step(st, pro_m + st->sigma0 * pp);
 }
 
-// shift drop (cg_mms_tm.c:146-153: new alphas, not yet updated ps), stopping test (:170-176), betas (:180-189)
-__global__ __launch_bounds__(256) void mms_beta_kernel(MmsState *st, const double *part_r, int n_r, const double *part_sn, int n_sn, int check,
+// |r|^2 and, on a check iteration, |ps_last|^2, then the beta step
+__global__ __launch_bounds__(256) void mms_beta_kernel(MshiftState *st, const double *part_r, int n_r, const double *part_sn, int n_sn, int check,
                                                        int iteration) {
-  const double err = mms_block_sum(part_r, n_r);
+  __shared__ double ws[4];
+  const double err = tmhip_block_sum256(part_r, n_r, ws);
   __syncthreads();
-  const double sn = check ? mms_block_sum(part_sn, n_sn) : 0.0;
+  const double sn = check ? tmhip_block_sum256(part_sn, n_sn, ws) : 0.0;
   if (threadIdx.x != 0 || st->done) return;
-  st->pact = st->active;
-  if (check && st->active > 1) {
-    const double al = st->alphas[st->active - 1];
-    if (al * al * sn <= st->eps_sq) st->active -= 1;
-  }
-  st->err = err;
-  st->it = iteration + 1;
-  if (err <= st->target || iteration == st->max_iter - 1) { st->done = 1; st->done_it = iteration; return; }
-  const double b0 = err / st->normsq;
-  st->beta0 = b0;
-  st->normsq = err;
-  for (int im = 1; im < st->active; im++) st->betas[im] = b0 * st->zita[im] * st->alphas[im] / (st->zitam1[im] * st->alpha0);
+  mshift_beta_step(st, err, sn, check, iteration);
 }
 
 // The vector pass.  tab[2 s] = P_s, tab[2 s + 1] = ps_s (s >= 1).  Runs in the iteration that set `done` (then only the P updates,
 // :164-165 and :141 of the last iteration) and never after it.  blockIdx.y: the half of a FULL field (one-parity fields: 0 only).
 // One partial per wave of |p|^2 (the next alpha kernel's sigma0 |p|^2) and, when sn_next, of |ps_last|^2 (the next drop check).
-__global__ __launch_bounds__(256) void mms_vec_kernel(const MmsState *st, v2d *const *tab, v2d *__restrict__ P0, v2d *__restrict__ p,
+__global__ __launch_bounds__(256) void mms_vec_kernel(const MshiftState *st, v2d *const *tab, v2d *__restrict__ P0, v2d *__restrict__ p,
                                                       const v2d *__restrict__ r, int ns, int N, double *part_pp, double *part_sn, int sn_next,
                                                       int iteration) {
   const int done = st->done;
@@ -98,7 +59,7 @@ __global__ __launch_bounds__(256) void mms_vec_kernel(const MmsState *st, v2d *c
   const int pact = st->pact, act = st->active;
   double dpp = 0.0, dsn = 0.0;
   if (i < N) {
-    const double a0 = st->alpha0, b0 = st->beta0;
+    const double a0 = st->alpha0, b0 = st->betas[0];
     v2d rv[12];
     if (!fin) {
 #pragma unroll
@@ -141,12 +102,12 @@ __global__ __launch_bounds__(256) void mms_vec_kernel(const MmsState *st, v2d *c
   }
   if (fin) return;
   const int slot = (blockIdx.y * gridDim.x + blockIdx.x) * 4 + (int)(threadIdx.x >> 6);
-  mms_wave_partial(dpp, part_pp, slot);
-  if (sn_next) mms_wave_partial(dsn, part_sn, slot);
+  tmhip_wave_partial(dpp, part_pp, slot);
+  if (sn_next) tmhip_wave_partial(dsn, part_sn, slot);
 }
 
 // unfused forms: partials of <p, A p> (the operator's part of pro) ...
-__global__ __launch_bounds__(256) void mms_dot_kernel(const MmsState *st, const v2d *__restrict__ p, const v2d *__restrict__ ap, int ns, int N,
+__global__ __launch_bounds__(256) void mms_dot_kernel(const MshiftState *st, const v2d *__restrict__ p, const v2d *__restrict__ ap, int ns, int N,
                                                       double *partials) {
   if (st->done) return;
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
@@ -156,11 +117,11 @@ __global__ __launch_bounds__(256) void mms_dot_kernel(const MmsState *st, const 
 #pragma unroll
     for (int c = 0; c < 12; c++) { const size_t o = off + (size_t)c * ns + i; d += mms_dot(p[o], ap[o]); }
   }
-  mms_wave_partial(d, partials, (blockIdx.y * gridDim.x + blockIdx.x) * 4 + (int)(threadIdx.x >> 6));
+  tmhip_wave_partial(d, partials, (blockIdx.y * gridDim.x + blockIdx.x) * 4 + (int)(threadIdx.x >> 6));
 }
 
 // ... and r -= alpha0 (A p + sigma0 p) with the partials of |r|^2 (cg_mms_tm.c:115-118,166)
-__global__ __launch_bounds__(256) void mms_res_kernel(const MmsState *st, v2d *__restrict__ r, const v2d *__restrict__ ap, const v2d *__restrict__ p,
+__global__ __launch_bounds__(256) void mms_res_kernel(const MshiftState *st, v2d *__restrict__ r, const v2d *__restrict__ ap, const v2d *__restrict__ p,
                                                       int ns, int N, double *partials) {
   if (st->done) return;
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
@@ -176,18 +137,18 @@ __global__ __launch_bounds__(256) void mms_res_kernel(const MmsState *st, v2d *_
       d += mms_dot(rn, rn);
     }
   }
-  mms_wave_partial(d, partials, (blockIdx.y * gridDim.x + blockIdx.x) * 4 + (int)(threadIdx.x >> 6));
+  tmhip_wave_partial(d, partials, (blockIdx.y * gridDim.x + blockIdx.x) * 4 + (int)(threadIdx.x >> 6));
 }
 }  // namespace
 
 // ---------------------------------------------------------------- host side
 struct TmhipMms {
   tmhip_field *w[2][3];                      // [kind][r, p, A p]
-  tmhip_field *ps[2][MMS_MAX_SHIFTS];        // [kind][s - 1]: shifted directions (allocated as needed)
+  tmhip_field *ps[2][MSHIFT_MAX_SHIFTS];     // [kind][s - 1]: shifted directions (allocated as needed)
   tmhip_field *full_tmp;                     // FULL scratch of Q_pm_psi (g_spinor_field[DUM_MATRIX] of tm_operators.c:383)
   int nps[2];
   double *partials; int max_partials;        // [4][max_partials]: pro, |r|^2, |p|^2, |ps_last|^2
-  MmsState *st;
+  MshiftState *st;
   v2d **tab;
   int form;                                  // form of the last solve: 0 fused e/o, 1 unfused e/o, 2 FULL composite
 };
@@ -214,8 +175,8 @@ static int mms_prepare(tmhip_ctx *ctx) {
   m->max_partials = 4 * ((2 * ctx->Vh + 255) / 256) + 64;   // one per wave of a vector-pass grid over a FULL field
   TMHIP_CHECK(hipMalloc((void **)&m->partials, (size_t)4 * m->max_partials * sizeof(double)));
   TMHIP_CHECK(hipMemsetAsync(m->partials, 0, (size_t)4 * m->max_partials * sizeof(double), ctx->stream));
-  TMHIP_CHECK(hipMalloc((void **)&m->st, sizeof(MmsState)));
-  TMHIP_CHECK(hipMalloc((void **)&m->tab, (size_t)2 * MMS_MAX_SHIFTS * sizeof(v2d *)));
+  TMHIP_CHECK(hipMalloc((void **)&m->st, sizeof(MshiftState)));
+  TMHIP_CHECK(hipMalloc((void **)&m->tab, (size_t)2 * MSHIFT_MAX_SHIFTS * sizeof(v2d *)));
   return 0;
 }
 
@@ -275,7 +236,7 @@ static int mms_solve(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const doub
   m->form = form;
 
   // start (cg_mms_tm.c:84-112): P_s = 0, ps_s = Q, r = p = Q, normsq = |Q|^2
-  MmsState h;
+  MshiftState h;
   memset(&h, 0, sizeof(h));
   double squarenorm;
   if (mms_norm(ctx, Q, &squarenorm)) return 1;
@@ -288,10 +249,10 @@ static int mms_solve(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const doub
     if (mms_copy(ctx, m->ps[kind][s - 1], Q)) return 1;
   }
   if (mms_copy(ctx, r, Q) || mms_copy(ctx, p, Q)) return 1;
-  h.alpha0 = 1.0; h.beta0 = 0.0; h.normsq = squarenorm;
+  h.alpha0 = h.alphas[0] = 1.0; h.betas[0] = 0.0; h.normsq = squarenorm;
   h.target = rel_prec > 0 ? eps_sq * squarenorm : (rel_prec == 0 ? eps_sq : -1.0);   // :170-172: rel_prec < 0 runs to max_iter - 1
   h.eps_sq = eps_sq; h.active = h.pact = nsh; h.max_iter = max_iter; h.done_it = -1;
-  v2d *tab[2 * MMS_MAX_SHIFTS] = {};
+  v2d *tab[2 * MSHIFT_MAX_SHIFTS] = {};
   for (int s = 1; s < nsh; s++) { tab[2 * s] = P[s]->d; tab[2 * s + 1] = m->ps[kind][s - 1]->d; }
   TMHIP_CHECK(hipMemcpyAsync(m->tab, tab, sizeof(v2d *) * 2 * nsh, hipMemcpyHostToDevice, ctx->stream));
   TMHIP_CHECK(hipMemcpyAsync(m->st, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
@@ -307,15 +268,7 @@ static int mms_solve(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const doub
   TMHIP_CHECK(hipMemcpyAsync(ppp, &squarenorm, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 
   const int batch = ctx->opt_cg_batch > 0 ? ctx->opt_cg_batch : 4;
-  int *flag = (int *)(ctx->result_host + 2);
-  double *err_host = ctx->result_host + 3;
-  int enq = 0, done = 0;
-  bool near = false;   // within 10^3 of the target: poll every iteration so that no stencil is enqueued past convergence
-  while (enq < max_iter && !done) {
-    const int want = near ? 1 : batch;
-    const int nb = (max_iter - enq) < want ? (max_iter - enq) : want;
-    for (int b = 0; b < nb; b++) {
-      const int iteration = enq + b;
+  if (tmhip_poll_loop(ctx, max_iter, true, batch, 1.0e3 * (h.target > 0 ? h.target : eps_sq), &m->st->done, &m->st->err, 0, false, [&](int iteration) {
       const int check = nsh > 1 && iteration > 0 && iteration % 20 == 0;
       const int sn_next = nsh > 1 && (iteration + 1) % 20 == 0;
       int n1 = 0, n2 = nvec;
@@ -343,23 +296,16 @@ static int mms_solve(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const doub
         } else if (tmhip_apply_op(ctx, op, ap, p)) {
           return 1;
         }
-        hipLaunchKernelGGL(mms_dot_kernel, vg, dim3(256), 0, ctx->stream, (const MmsState *)m->st, (const v2d *)p->d, (const v2d *)ap->d, ctx->ns, ctx->Vh, ppro);
+        hipLaunchKernelGGL(mms_dot_kernel, vg, dim3(256), 0, ctx->stream, (const MshiftState *)m->st, (const v2d *)p->d, (const v2d *)ap->d, ctx->ns, ctx->Vh, ppro);
         hipLaunchKernelGGL(mms_alpha_kernel, dim3(1), dim3(256), 0, ctx->stream, m->st, (const double *)ppro, nvec, (const double *)ppp, nvec);
-        hipLaunchKernelGGL(mms_res_kernel, vg, dim3(256), 0, ctx->stream, (const MmsState *)m->st, r->d, (const v2d *)ap->d, (const v2d *)p->d,
+        hipLaunchKernelGGL(mms_res_kernel, vg, dim3(256), 0, ctx->stream, (const MshiftState *)m->st, r->d, (const v2d *)ap->d, (const v2d *)p->d,
                            ctx->ns, ctx->Vh, pr);
       }
       hipLaunchKernelGGL(mms_beta_kernel, dim3(1), dim3(256), 0, ctx->stream, m->st, r_parts, n2, (const double *)psn, nvec, check, iteration);
-      hipLaunchKernelGGL(mms_vec_kernel, vg, dim3(256), 0, ctx->stream, (const MmsState *)m->st, (v2d *const *)m->tab, P[0]->d, p->d,
+      hipLaunchKernelGGL(mms_vec_kernel, vg, dim3(256), 0, ctx->stream, (const MshiftState *)m->st, (v2d *const *)m->tab, P[0]->d, p->d,
                          (const v2d *)r->d, ctx->ns, ctx->Vh, ppp, psn, sn_next, iteration);
-    }
-    enq += nb;
-    TMHIP_CHECK(hipGetLastError());
-    TMHIP_CHECK(hipMemcpyAsync(flag, &m->st->done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipMemcpyAsync(err_host, &m->st->err, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    done = *flag;
-    near = *err_host <= 1.0e3 * (h.target > 0 ? h.target : eps_sq);
-  }
+      return 0;
+    })) return 1;
   TMHIP_CHECK(hipMemcpyAsync(&h, m->st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (!h.done) TMHIP_FAIL("cg_mms_tm: the solve ended without its last iteration");
@@ -373,7 +319,7 @@ extern "C" {
 
 int tmhip_cg_mms_tm(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const double *shifts, int nshifts, int max_iter, double eps_sq,
                     int rel_prec, int N, int op, int *iters, double *reached_prec) {
-  if (nshifts < 1 || nshifts > MMS_MAX_SHIFTS) TMHIP_FAIL("cg_mms_tm: nshifts = %d is outside [1, %d]", nshifts, MMS_MAX_SHIFTS);
+  if (nshifts < 1 || nshifts > MSHIFT_MAX_SHIFTS) TMHIP_FAIL("cg_mms_tm: nshifts = %d is outside [1, %d]", nshifts, MSHIFT_MAX_SHIFTS);
   if (!P || !Q || !shifts || !iters) TMHIP_FAIL("cg_mms_tm: null argument");
   if (op != TMHIP_OP_QTM_PM && op != TMHIP_OP_QSW_PM && op != TMHIP_OP_Q_PM_FULL)
     TMHIP_FAIL("cg_mms_tm: operator id %d is not Qtm_pm_psi, Qsw_pm_psi or Q_pm_psi", op);

@@ -10,11 +10,12 @@
 // pointer choices here.  Option "nd_fused" 0 builds the same operator from two single-flavour stencil launches (EPI_STORE)
 // per hop plus one mixing pass (nd_mix_kernel) -- the A/B of DESIGN.md section 4.
 //
-// The solvers share one device-resident engine (nd_solve): the coefficients of the multi-shift recurrences
-// (cg_mms_tm_nd.c:116-194) live in NdState and are updated by one-block kernels, the field updates read them from there,
-// and the host polls `done` at batch boundaries only.  cg_her_nd is the one-shift, sigma = 0 case with its own start
-// (P != 0 allowed) and return convention.
+// The solvers share one device-resident engine (nd_solve): the coefficients of the multi-shift recurrences live in a
+// MshiftState and are updated by one-block kernels (the recurrences themselves: mshift.h, shared with mms.hip), the field
+// updates read them from there, and the host polls `done` at batch boundaries only (tmhip_poll_loop, tmhip_internal.h).
+// cg_her_nd is the one-shift, sigma = 0 case with its own start (P != 0 allowed) and return convention.
 #include "hopping_common.h"
+#include "mshift.h"
 
 namespace {
 TMHIP_SCALAR_COMPLEX_OPS(v2d, double)
@@ -162,12 +163,6 @@ __device__ __forceinline__ double nd_epilogue(const NdArgs &a, int i, const v2d 
   return d;
 }
 
-__device__ __forceinline__ void nd_wave_partial(double d, double *partials, int slot) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
-  if ((threadIdx.x & 63) == 0) partials[slot] = d;
-}
-
 // One thread per output site, both flavours.  Every thread reaches the end (inactive ones with d = 0), so the reducing form
 // writes one partial per wave of the grid, padding blocks included: the sum never depends on the block order.
 template <int EPI, int BS, bool NT>
@@ -210,7 +205,7 @@ __global__ __launch_bounds__(BS) void nd_hop_kernel(const NdArgs a) {
     nd_hop_dir<7, NT>(aa, ab, a.in_a, a.in_b, ns, jzm, a.gauge, gs, i, ka3);
     d = nd_epilogue<EPI>(a, i, aa, ab);
   }
-  if (EPI == ND_OO_DOT) nd_wave_partial(d, a.partials, blockIdx.x * (BS / 64) + (int)(threadIdx.x >> 6));
+  if (EPI == ND_OO_DOT) tmhip_wave_partial(d, a.partials, blockIdx.x * (BS / 64) + (int)(threadIdx.x >> 6));
 }
 
 // The mixing alone, a and b read at the site: the standalone M_ee_inv_ndpsi / M_oo_sub_g5_ndpsi and the second half of the
@@ -226,49 +221,22 @@ __global__ __launch_bounds__(256) void nd_mix_kernel(const NdArgs a, int N) {
     ld6<false>(vb, a.in_b, ns, i, 0); ld6<false>(vb + 6, a.in_b, ns, i, 1);
     d = nd_epilogue<EPI>(a, i, va, vb);
   }
-  if (EPI == ND_OO_DOT) nd_wave_partial(d, a.partials, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+  if (EPI == ND_OO_DOT) tmhip_wave_partial(d, a.partials, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
 }
 
 // ---------------------------------------------------------------- solver state and kernels
-#define ND_MAX_SHIFTS 32
-struct NdState {
-  double normsq, err, target, eps_sq;                  // eps_sq: the absolute threshold of the shift drop (cg_mms_tm_nd.c:162)
-  int it, done, conv, active, max_iter, pad;
-  double sigma[ND_MAX_SHIFTS], zita[ND_MAX_SHIFTS], zitam1[ND_MAX_SHIFTS], alphas[ND_MAX_SHIFTS], betas[ND_MAX_SHIFTS];
-};
-
-// fixed-order sum of n partials by one block of 256 threads (every thread gets the total)
-__device__ __forceinline__ double nd_block_sum(const double *__restrict__ v, int n) {
+// pro = <p, (A + sigma0) p> over both flavours (the stencil's ND_OO_DOT partials), then the alpha step
+__global__ __launch_bounds__(256) void nd_alpha_kernel(MshiftState *st, const double *partials, int n) {
   __shared__ double ws[4];
-  double acc = 0.0;
-  for (int j = threadIdx.x; j < n; j += 256) acc += v[j];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  return (ws[0] + ws[1]) + (ws[2] + ws[3]);
-}
-
-// alphas[0] = normsq / pro and the zita / alphas recurrences of the shifts still active (cg_mms_tm_nd.c:126-146)
-__global__ __launch_bounds__(256) void nd_alpha_kernel(NdState *st, const double *partials, int n) {
-  const double pro = nd_block_sum(partials, n);
+  const double pro = tmhip_block_sum256(partials, n, ws);
   if (threadIdx.x != 0 || st->done) return;
-  const double alpham1 = st->alphas[0];
-  const double a0 = st->normsq / pro;
-  st->alphas[0] = a0;
-  const double b0 = st->betas[0];
-  for (int im = 1; im < st->active; im++) {
-    const double gamma = st->zita[im] * alpham1 / (a0 * b0 * (1. - st->zita[im] / st->zitam1[im]) + alpham1 * (1. + st->sigma[im] * a0));
-    st->zitam1[im] = st->zita[im];
-    st->zita[im] = gamma;
-    st->alphas[im] = a0 * st->zita[im] / st->zitam1[im];
-  }
+  mshift_alpha_step(st, pro);
 }
 
 // field table of the shifts: tab[4 s + 0 / 1] = P_up[s] / P_dn[s], tab[4 s + 2 / 3] = ps_up[s] / ps_dn[s] (shift 0: the x and p of the CG)
 // blockIdx.y = s.  s = 0: x += alphas[0] p, r -= alphas[0] A p, partials of |r|^2 (cg_mms_tm_nd.c:170-180);
 // s >= 1 (active): P[s] += alphas[s] ps[s] (:149-150), and on a check iteration the last active shift adds up |ps|^2 (:158-160)
-__global__ __launch_bounds__(256) void nd_x_kernel(NdState *st, v2d *const *tab, v2d *r_up, v2d *r_dn, const v2d *ap_up, const v2d *ap_dn,
+__global__ __launch_bounds__(256) void nd_x_kernel(MshiftState *st, v2d *const *tab, v2d *r_up, v2d *r_dn, const v2d *ap_up, const v2d *ap_dn,
                                                    int ns, int N, double *part_r, double *part_sn, int check) {
   const int s = blockIdx.y;
   if (st->done || s >= st->active) return;   // block-uniform
@@ -294,32 +262,22 @@ __global__ __launch_bounds__(256) void nd_x_kernel(NdState *st, v2d *const *tab,
       }
     }
   }
-  if (s == 0) nd_wave_partial(d, part_r, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
-  else if (sn) nd_wave_partial(d, part_sn, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+  if (s == 0) tmhip_wave_partial(d, part_r, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+  else if (sn) tmhip_wave_partial(d, part_sn, blockIdx.x * 4 + (int)(threadIdx.x >> 6));
 }
 
-// shift drop (cg_mms_tm_nd.c:158-167), stopping test (:186-190), betas (:195-201)
-__global__ __launch_bounds__(256) void nd_beta_kernel(NdState *st, const double *part_r, const double *part_sn, int n, int check) {
-  const double err = nd_block_sum(part_r, n);
+// |r|^2 and, on a check iteration, |ps_last|^2, then the beta step
+__global__ __launch_bounds__(256) void nd_beta_kernel(MshiftState *st, const double *part_r, const double *part_sn, int n, int check, int iteration) {
+  __shared__ double ws[4];
+  const double err = tmhip_block_sum256(part_r, n, ws);
   __syncthreads();
-  const double sn = check ? nd_block_sum(part_sn, n) : 0.0;
+  const double sn = check ? tmhip_block_sum256(part_sn, n, ws) : 0.0;
   if (threadIdx.x != 0 || st->done) return;
-  if (check && st->active > 1) {
-    const double al = st->alphas[st->active - 1];
-    if (al * al * sn <= st->eps_sq) st->active -= 1;
-  }
-  st->err = err;
-  st->it += 1;
-  if (err <= st->target) { st->done = 1; st->conv = 1; return; }
-  if (st->it >= st->max_iter) { st->done = 1; return; }
-  const double b0 = err / st->normsq;
-  st->betas[0] = b0;
-  st->normsq = err;
-  for (int im = 1; im < st->active; im++) st->betas[im] = b0 * st->zita[im] * st->alphas[im] / (st->zitam1[im] * st->alphas[0]);
+  mshift_beta_step(st, err, sn, check, iteration);
 }
 
 // p = beta p + r (s = 0, :193-194), ps[s] = betas[s] ps[s] + zita[s] r (:199-200)
-__global__ __launch_bounds__(256) void nd_p_kernel(const NdState *st, v2d *const *tab, const v2d *r_up, const v2d *r_dn, int ns, int N) {
+__global__ __launch_bounds__(256) void nd_p_kernel(const MshiftState *st, v2d *const *tab, const v2d *r_up, const v2d *r_dn, int ns, int N) {
   const int s = blockIdx.y;
   if (st->done || s >= st->active) return;
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
@@ -339,10 +297,10 @@ __global__ __launch_bounds__(256) void nd_p_kernel(const NdState *st, v2d *const
 struct TmhipNd {
   tmhip_field *s[6];           // operator scratch: [0, 1] EE outputs, [2, 3] first OO output of Qtm_pm_ndpsi, [4, 5] single-flavour hops (two-stencil form)
   tmhip_field *w[6];           // solver: r_up, r_dn, p_up, p_dn, Ap_up, Ap_dn
-  tmhip_field *ps[2 * ND_MAX_SHIFTS];   // shifted directions (allocated as needed)
+  tmhip_field *ps[2 * MSHIFT_MAX_SHIFTS];   // shifted directions (allocated as needed)
   int nps;
   double *partials; int max_partials;   // [3][max_partials]: pro, |r|^2, |ps|^2
-  NdState *st;
+  MshiftState *st;
   v2d **tab;
 };
 
@@ -370,8 +328,8 @@ static int nd_prepare(tmhip_ctx *ctx, const char *who) {
   // stencil: one partial per wave of the padded grid (64-thread blocks, rounded up to a multiple of 8); mix / x kernels: 4 per block
   n->max_partials = ctx->Vh / 64 + 64;
   TMHIP_CHECK(hipMalloc((void **)&n->partials, (size_t)3 * n->max_partials * sizeof(double)));
-  TMHIP_CHECK(hipMalloc((void **)&n->st, sizeof(NdState)));
-  TMHIP_CHECK(hipMalloc((void **)&n->tab, (size_t)4 * ND_MAX_SHIFTS * sizeof(v2d *)));
+  TMHIP_CHECK(hipMalloc((void **)&n->st, sizeof(MshiftState)));
+  TMHIP_CHECK(hipMalloc((void **)&n->tab, (size_t)4 * MSHIFT_MAX_SHIFTS * sizeof(v2d *)));
   return 0;
 }
 
@@ -474,7 +432,7 @@ static int nd_solve(tmhip_ctx *ctx, bool her, tmhip_field **x_up, tmhip_field **
   tmhip_field *r_up = n->w[0], *r_dn = n->w[1], *p_up = n->w[2], *p_dn = n->w[3], *ap_up = n->w[4], *ap_dn = n->w[5];
   for (; n->nps < 2 * (nsh - 1); n->nps++)
     if (tmhip_field_alloc(ctx, TMHIP_FIELD_EO, &n->ps[n->nps])) return 1;
-  NdState h;
+  MshiftState h;
   memset(&h, 0, sizeof(h));
   double qa, qb;
   if (tmhip_square_norm(ctx, q_up, N, 0, &qa) || tmhip_square_norm(ctx, q_dn, N, 0, &qb)) return 1;
@@ -492,14 +450,13 @@ static int nd_solve(tmhip_ctx *ctx, bool her, tmhip_field **x_up, tmhip_field **
       h.normsq = pa + pb;
     }
     h.target = rel_prec == 0 ? eps_sq : (rel_prec == 1 ? eps_sq * squarenorm : -1.0);   // :108: rel_prec other than 0 / 1 never converges
-    h.sigma[0] = 0.0;
   } else {
     if (tmhip_assign(ctx, r_up, q_up, N) || tmhip_assign(ctx, r_dn, q_dn, N)) return 1;
     for (int s = 0; s < nsh; s++)
       if (tmhip_field_zero(ctx, x_up[s]) || tmhip_field_zero(ctx, x_dn[s])) return 1;
-    h.sigma[0] = shifts[0] * shifts[0];
+    h.sigma0 = shifts[0] * shifts[0];
     for (int s = 1; s < nsh; s++) {
-      h.sigma[s] = shifts[s] * shifts[s] - h.sigma[0];
+      h.sigma[s] = shifts[s] * shifts[s] - h.sigma0;
       h.zita[s] = h.zitam1[s] = h.alphas[s] = 1.0;
       if (tmhip_assign(ctx, n->ps[2 * s - 2], q_up, N) || tmhip_assign(ctx, n->ps[2 * s - 1], q_dn, N)) return 1;
     }
@@ -507,9 +464,9 @@ static int nd_solve(tmhip_ctx *ctx, bool her, tmhip_field **x_up, tmhip_field **
     h.target = rel_prec > 0 ? eps_sq * squarenorm : (rel_prec == 0 ? eps_sq : -1.0);   // :186-188: rel_prec < 0 runs to max_iter
   }
   if (tmhip_assign(ctx, p_up, r_up, N) || tmhip_assign(ctx, p_dn, r_dn, N)) return 1;
-  h.alphas[0] = 1.0; h.betas[0] = 0.0;
-  h.eps_sq = eps_sq; h.active = nsh; h.max_iter = max_iter;
-  v2d *tab[4 * ND_MAX_SHIFTS];
+  h.alpha0 = h.alphas[0] = 1.0; h.betas[0] = 0.0;
+  h.eps_sq = eps_sq; h.active = h.pact = nsh; h.max_iter = max_iter; h.done_it = -1;
+  v2d *tab[4 * MSHIFT_MAX_SHIFTS];
   tab[0] = x_up[0]->d; tab[1] = x_dn[0]->d; tab[2] = p_up->d; tab[3] = p_dn->d;
   for (int s = 1; s < nsh; s++) { tab[4 * s] = x_up[s]->d; tab[4 * s + 1] = x_dn[s]->d; tab[4 * s + 2] = n->ps[2 * s - 2]->d; tab[4 * s + 3] = n->ps[2 * s - 1]->d; }
   TMHIP_CHECK(hipMemcpyAsync(n->tab, tab, sizeof(v2d *) * 4 * nsh, hipMemcpyHostToDevice, ctx->stream));
@@ -518,33 +475,18 @@ static int nd_solve(tmhip_ctx *ctx, bool her, tmhip_field **x_up, tmhip_field **
   double *pa = n->partials, *pr = n->partials + n->max_partials, *psn = n->partials + 2 * n->max_partials;
   if (4 * nbl > n->max_partials) TMHIP_FAIL("nd: partials buffer too small");
   const int batch = ctx->opt_cg_batch > 0 ? ctx->opt_cg_batch : 4;
-  int *flag = (int *)(ctx->result_host + 2);
-  double *err_host = ctx->result_host + 3;
-  int enq = 0, done = 0;
-  bool near = false;
-  while (enq < max_iter && !done) {
-    const int want = near ? 1 : batch;
-    const int nb = (max_iter - enq) < want ? (max_iter - enq) : want;
-    for (int b = 0; b < nb; b++) {
-      const int iteration = enq + b;
-      const int check = !her && nsh > 1 && iteration > 0 && iteration % 20 == 0;
-      int np = 0;
-      if (nd_qpm(ctx, ap_up->d, ap_dn->d, p_up->d, p_dn->d, s2, p_up->d, p_dn->d, h.sigma[0], &np)) return 1;
-      hipLaunchKernelGGL(nd_alpha_kernel, dim3(1), dim3(256), 0, ctx->stream, n->st, (const double *)pa, np);
-      hipLaunchKernelGGL(nd_x_kernel, dim3(nbl, nsh), dim3(256), 0, ctx->stream, n->st, (v2d *const *)n->tab, r_up->d, r_dn->d,
-                         (const v2d *)ap_up->d, (const v2d *)ap_dn->d, ctx->ns, N, pr, psn, check);
-      hipLaunchKernelGGL(nd_beta_kernel, dim3(1), dim3(256), 0, ctx->stream, n->st, (const double *)pr, (const double *)psn, 4 * nbl, check);
-      hipLaunchKernelGGL(nd_p_kernel, dim3(nbl, nsh), dim3(256), 0, ctx->stream, (const NdState *)n->st, (v2d *const *)n->tab,
-                         (const v2d *)r_up->d, (const v2d *)r_dn->d, ctx->ns, N);
-    }
-    enq += nb;
-    TMHIP_CHECK(hipGetLastError());
-    TMHIP_CHECK(hipMemcpyAsync(flag, &n->st->done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipMemcpyAsync(err_host, &n->st->err, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    done = *flag;
-    near = *err_host <= 1.0e3 * (h.target > 0 ? h.target : eps_sq);
-  }
+  if (tmhip_poll_loop(ctx, max_iter, true, batch, 1.0e3 * (h.target > 0 ? h.target : eps_sq), &n->st->done, &n->st->err, 0, false, [&](int iteration) {
+        const int check = !her && nsh > 1 && iteration > 0 && iteration % 20 == 0;
+        int np = 0;
+        if (nd_qpm(ctx, ap_up->d, ap_dn->d, p_up->d, p_dn->d, s2, p_up->d, p_dn->d, h.sigma0, &np)) return 1;
+        hipLaunchKernelGGL(nd_alpha_kernel, dim3(1), dim3(256), 0, ctx->stream, n->st, (const double *)pa, np);
+        hipLaunchKernelGGL(nd_x_kernel, dim3(nbl, nsh), dim3(256), 0, ctx->stream, n->st, (v2d *const *)n->tab, r_up->d, r_dn->d,
+                           (const v2d *)ap_up->d, (const v2d *)ap_dn->d, ctx->ns, N, pr, psn, check);
+        hipLaunchKernelGGL(nd_beta_kernel, dim3(1), dim3(256), 0, ctx->stream, n->st, (const double *)pr, (const double *)psn, 4 * nbl, check, iteration);
+        hipLaunchKernelGGL(nd_p_kernel, dim3(nbl, nsh), dim3(256), 0, ctx->stream, (const MshiftState *)n->st, (v2d *const *)n->tab,
+                           (const v2d *)r_up->d, (const v2d *)r_dn->d, ctx->ns, N);
+        return 0;
+      })) return 1;
   TMHIP_CHECK(hipMemcpyAsync(&h, n->st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   ctx->nd_active_shifts = h.active;
@@ -634,7 +576,7 @@ int tmhip_cg_her_nd(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_
 
 int tmhip_cg_mms_tm_nd(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmhip_field *Qup, tmhip_field *Qdn, const double *shifts,
                        int nshifts, int max_iter, double eps_sq, int rel_prec, int *iters) {
-  if (nshifts < 1 || nshifts > ND_MAX_SHIFTS) TMHIP_FAIL("cg_mms_tm_nd: nshifts = %d is outside [1, %d]", nshifts, ND_MAX_SHIFTS);
+  if (nshifts < 1 || nshifts > MSHIFT_MAX_SHIFTS) TMHIP_FAIL("cg_mms_tm_nd: nshifts = %d is outside [1, %d]", nshifts, MSHIFT_MAX_SHIFTS);
   if (!Pup || !Pdn || !shifts) TMHIP_FAIL("cg_mms_tm_nd: null argument");
   if (nd_check4(ctx, "cg_mms_tm_nd", Pup[0], Pdn[0], Qup, Qdn)) return 1;
   for (int s = 0; s < nshifts; s++) {

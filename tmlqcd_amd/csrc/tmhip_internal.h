@@ -248,13 +248,23 @@ int tmhip_launch_hopping(tmhip_ctx *ctx, int ieo, v2d *out, const v2d *in, const
 // (a ~4.7 us floor each at any size: the difference between 14.8k and 17k CG iterations per second at 16^4).
 struct HopSelfAlpha { const double *partials; int n; const double *normsq; double *out2; };
 bool tmhip_hopping_self_alpha_ok(const tmhip_ctx *ctx);   // the launch below would take the hop-split kernel
+// The library's reductions, written once.  tmhip_wave_sum: the 64-lane butterfly (every lane returns the wave's total);
+// tmhip_wave_partial: one partial per wave, stored by lane 0 into partials[slot].
+__device__ __forceinline__ double tmhip_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ void tmhip_wave_partial(double d, double *partials, int slot) {
+  d = tmhip_wave_sum(d);
+  if ((threadIdx.x & 63) == 0) partials[slot] = d;
+}
 // fixed-order sum of n doubles by a 256-thread block (every thread returns the total); wsum: 4 doubles of shared memory.  Shared by
-// the stencil above and cg_xp_self_kernel (cg.hip): both must add in exactly the same order.
+// the stencil above, cg_xp_self_kernel (cg.hip) and the one-block kernels of the multi-shift solvers: all add in exactly the same order.
 __device__ __forceinline__ double tmhip_block_sum256(const double *__restrict__ v, int n, double *wsum) {
   double acc = 0.0;
   for (int j = threadIdx.x; j < n; j += 256) acc += v[j];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = tmhip_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
   __syncthreads();
   return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
@@ -276,6 +286,41 @@ int tmhip_reduce_finish(tmhip_ctx *ctx, int nblocks, int parallel, double *out);
 // synchronised cannot be trusted.  Reported once per occurrence -- the error word is cleared, the next call starts clean.
 int tmhip_check_async_error(tmhip_ctx *ctx);
 extern "C" int tmhip_check_gauge_recon(tmhip_ctx *ctx);   // context.hip: unitarity guard of the gauge_recon=12 option
+// The polling loop of every device-resident solver.  enqueue(k) puts iteration number k on ctx->stream; the host enqueues `batch`
+// of them, reads `done` and `err` of the solver's device state into result_host[2..3], synchronises, and polls after every single
+// iteration once err <= near_below (within 10^3 of the target: no stencil is enqueued far past convergence; exactness never depends
+// on it, the kernels skip their work once `done` is set).
+//   clamp true : at most `cap` iterations are enqueued, the last batch is cut to fit          (while !done && enq <  cap)
+//   clamp false: whole batches while the count has not passed `cap`                            (while !done && enq <= cap)
+// done_dev / err_dev name the state the last enqueued iteration wrote; alt_stride != 0: a second copy of the state that many bytes
+// further on holds it after an odd number of iterations (cg_her's self-summing form).  check_async: tmhip_check_async_error after
+// every synchronisation -- it costs a copy and a wait of its own once the context has run a split-phase stencil, so the solvers
+// whose poll never had it (nd.hip, mms.hip) leave it out.  *enq_out: the number of iterations enqueued.
+template <class Enqueue>
+static int tmhip_poll_loop(tmhip_ctx *ctx, int cap, bool clamp, int batch, double near_below, const int *done_dev, const double *err_dev,
+                           size_t alt_stride, bool check_async, Enqueue enqueue, int *enq_out = nullptr) {
+  int *flag = (int *)(ctx->result_host + 2);
+  double *err_host = ctx->result_host + 3;
+  int enq = 0, done = 0;
+  bool near = false;
+  while (!done && (clamp ? enq < cap : enq <= cap)) {
+    const int want = near ? 1 : batch;
+    const int nb = clamp && cap - enq < want ? cap - enq : want;
+    for (int b = 0; b < nb; b++)
+      if (enqueue(enq + b)) return 1;
+    enq += nb;
+    const size_t off = (size_t)(enq & 1) * alt_stride;
+    TMHIP_CHECK(hipGetLastError());
+    TMHIP_CHECK(hipMemcpyAsync(flag, (const char *)done_dev + off, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    TMHIP_CHECK(hipMemcpyAsync(err_host, (const char *)err_dev + off, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    done = *flag;
+    if (check_async && tmhip_check_async_error(ctx)) return 1;   // T-split rank: a halo exchange that never completed must not yield a result
+    near = *err_host <= near_below;
+  }
+  if (enq_out) *enq_out = enq;
+  return 0;
+}
 int tmhip_stage_reserve(tmhip_ctx *ctx, size_t bytes);
 int tmhip_field_alloc_prec(tmhip_ctx *ctx, int kind, int prec, tmhip_field **out);
 int tmhip_halo_exchange(tmhip_ctx *ctx);
