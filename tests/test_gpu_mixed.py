@@ -69,7 +69,8 @@ def test_fp32_stencil_and_operator(setup, lds, recon):
 
 @pytest.mark.parametrize("dims", [(4, 4, 4, 6), (2, 2, 2, 4), (4, 6, 2, 12), (2, 2, 2, 2)])
 def test_fp32_stencil_ragged(dims):
-    """LZ/2 odd (6, 2) falls back to one site per thread; LZ/2 even (4, 12) uses site pairs with every row wrap."""
+    """The fp32 stencil takes one site per thread (HOP_SITES is 1 in hopping32.hip) on every shape: LZ/2 odd (3, 1) and even
+    (2, 6), single blocks with a partial wave, and the 2-site extents where the +mu and -mu neighbours coincide."""
     from oracle.oraclebind import Oracle
     from tmlqcd_amd import Lattice
     T, LX, LY, LZ = dims
