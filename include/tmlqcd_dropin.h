@@ -114,6 +114,7 @@ int tmlqcd_hip_comm_init_ipc(void);                      /* after either: the ha
 double square_norm(const spinor *const P, const int N, const int parallel);
 double scalar_prod_r(const spinor *const S, const spinor *const R, const int N, const int parallel);
 void assign_add_mul_r(spinor *const P, spinor *const Q, const double c, const int N);
+void assign_add_mul(spinor *const P, spinor *const Q, const _Complex double c, const int N);                 /* linalg/assign_add_mul.h: P += c Q */
 void assign_mul_add_r(spinor *const R, const double c, const spinor *const S, const int N);
 double assign_mul_add_r_and_square(spinor *const R, const double c, const spinor *const S, const int N, const int parallel);
 void diff(spinor *const Q, const spinor *const R, const spinor *const S, const int N);
@@ -189,6 +190,9 @@ void Qtm_pm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const 
 void M_ee_inv_ndpsi(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c, const double mu, const double eps);  /* :639-696 */
 void H_eo_tm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm, const int ieo);   /* :508-519 */
 void mul_one_pm_itau2(spinor *const p, spinor *const q, spinor *const r, spinor *const s, const double sign, const int N);        /* :582-597 */
+/* :311-380; l must not be k (the reference hops into l before it reads k) */
+void Q_tau1_sub_const_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm,
+                            const _Complex double z, const double Cpol, const double invev);
 /* solver/cg_her_nd.c:57-160 and solver/cg_mms_tm_nd.c:64-215 run on the device for f / M_ndpsi = Qtm_pm_ndpsi on N = VOLUME/2
  * sites (up to 32 shifts); anything else ends the program with a message */
 int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *const Q_dn, const int max_iter, double eps_sq,
@@ -283,6 +287,29 @@ double measure_plaquette(const su3 **const gf);                                 
 double measure_gauge_action(const su3 **const gf, const double lambda);          /* measure_gauge_action.c:108 */
 double measure_rectangles(const su3 **const gf);                                 /* measure_rectangles.c:51 */
 void tmlqcd_hip_gauge_derivative(hamiltonian_field_t *const hf, const double beta, const double c0, const double c1, const int use_rectangles, const double glambda);
+
+/* ---- rational monomials (monomial/ndrat_monomial.c type NDRAT, monomial/rat_monomial.c type RAT) --------------------------------------
+ * The bodies of the three monomial functions with the monomial's parameters as arguments (rational_t::mu / rmu / nu / rnu with np entries,
+ * EVMaxInv, maxiter, forceprec or accprec, g_relative_precision_flag), as tmlqcd_hip_gauge_derivative does for the gauge monomial; the
+ * shifted solutions and work fields stay in HBM.  pf / pf2 are host pseudofermion fields, registered like any other field.  Unsplit
+ * lattices only.  ndrat reads g_mubar, g_epsbar and phmc_invmaxev as the doublet operators do; rat runs at g_mu = 0 and leaves g_mu alone.
+ *   *_derivative  ndrat_monomial.c:96-160 / rat_monomial.c:83-132: accumulates like deriv_Sb (added to hf->derivative before returning in
+ *                 coherent mode, held on the device until tmlqcd_hip_flush_derivative / tmlqcd_hip_update_momenta in resident mode)
+ *   *_heatbath    :212-254 / :175-199: pf (pf2) hold the Gaussian field on entry and the pseudofermion field on exit; *energy0 = |eta|^2
+ *   *_acc         :281-309 / :232-250: *energy1; the caller forms energy1 - energy0
+ * All return the solver's iteration count (what the reference adds to mnl->iter0 / iter1). */
+int tmlqcd_hip_ndrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np,
+                                const double EVMaxInv, const int max_iter, const double eps_sq, const int rel_prec);
+int tmlqcd_hip_ndrat_heatbath(spinor *const pf, spinor *const pf2, const double *nu, const double *rnu, const int np, const double EVMaxInv,
+                              const int max_iter, const double eps_sq, const int rel_prec, double *energy0);
+int tmlqcd_hip_ndrat_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np, const int max_iter,
+                         const double eps_sq, const int rel_prec, double *energy1);
+int tmlqcd_hip_rat_derivative(hamiltonian_field_t *const hf, spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter,
+                              const double eps_sq, const int rel_prec);
+int tmlqcd_hip_rat_heatbath(spinor *const pf, const double *nu, const double *rnu, const int np, const int max_iter, const double eps_sq,
+                            const int rel_prec, double *energy0);
+int tmlqcd_hip_rat_acc(spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter, const double eps_sq,
+                       const int rel_prec, double *energy1);
 
 /* ---- ILDG gauge configurations: replaces io/gauge_read.o and io/gauge_write.o of libio.a -- */
 typedef struct { unsigned int suma, sumb; } DML_Checksum;                        /* io/dml.h:34-37 */

@@ -127,6 +127,7 @@ int tmhip_square_norm(tmhip_ctx *ctx, tmhip_field *P, int N, int parallel, doubl
 int tmhip_scalar_prod_r(tmhip_ctx *ctx, tmhip_field *S, tmhip_field *R, int N, int parallel, double *out);     /* scalar_prod_r.c:135 */
 int tmhip_assign_add_mul_r(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, double c, int N);                   /* assign_add_mul_r.c:346 */
 int tmhip_assign_mul_add_r(tmhip_ctx *ctx, tmhip_field *R, double c, tmhip_field *S, int N);                   /* assign_mul_add_r.c:340 */
+int tmhip_assign_add_mul(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, double c_re, double c_im, int N);     /* linalg/assign_add_mul.c: P += c Q, complex c; P may be Q */
 int tmhip_assign_mul_add_r_and_square(tmhip_ctx *ctx, tmhip_field *R, double c, tmhip_field *S, int N,
                                       int parallel, double *out);                                             /* assign_mul_add_r_and_square.c:145 */
 int tmhip_diff(tmhip_ctx *ctx, tmhip_field *Q, tmhip_field *R, tmhip_field *S, int N);                         /* diff.c:270 */
@@ -159,6 +160,10 @@ int tmhip_Qtm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_fi
 int tmhip_Qtm_dagger_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);   /* :130-152 */
 int tmhip_Qtm_pm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);       /* :195-238; l may be k */
 int tmhip_H_eo_tm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, int ieo);   /* :508-519 */
+/* Q_tau1_sub_const_ndpsi(l_s,l_c,k_s,k_c,z,Cpol,invev)   :311-380: l = Cpol invev Qhat tau^1 k - Cpol z k with g_mubar, g_epsbar of
+ * tmhip_set_nd (invev is the argument, as in the reference); two stencil launches, the constant in the epilogue of the second; l != k */
+int tmhip_Q_tau1_sub_const_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, double z_re, double z_im,
+                                 double Cpol, double invev);
 /* cg_her_nd(P_up,P_dn,Q_up,Q_dn,max_iter,eps_sq,rel_prec,N,Qtm_pm_ndpsi)   solver/cg_her_nd.c:57-160; *iters = its return value */
 int tmhip_cg_her_nd(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_field *Q_up, tmhip_field *Q_dn, int max_iter, double eps_sq,
                     int rel_prec, int N, int *iters);
@@ -198,6 +203,41 @@ int tmhip_derivative_zero(tmhip_ctx *ctx);
 int tmhip_deriv_Sb(tmhip_ctx *ctx, int ieo, tmhip_field *l, tmhip_field *k, double factor);
 int tmhip_derivative_download(tmhip_ctx *ctx, void *df, int accumulate);
 int tmhip_multi_deriv_Sb(int n, tmhip_ctx **ctxs, int ieo, tmhip_field **l, tmhip_field **k, double factor);
+
+/* sum_j deriv_Sb(ieo, l[j], k[j], hf, factor[j]) for j = 0 .. n-1, 1 <= n <= 64, added to the same accumulator (created and zeroed if
+ * absent) in ONE kernel launch: the links are read and the derivative is written once, whatever n is.  The fields are only read; one field
+ * may appear in several pairs and on both sides.  fp64 one-parity fields of one stride, unsplit lattices only (a T-split context and the
+ * loopback rehearsal are refused); every refusal happens before the launch and leaves the accumulator untouched.  The sum over j is formed
+ * before the projection onto the generators: the result differs from n tmhip_deriv_Sb calls by rounding. */
+int tmhip_deriv_Sb_batch(tmhip_ctx *ctx, int ieo, int n, tmhip_field **l, tmhip_field **k, const double *factor);
+
+/* ---- rational monomials (monomial/rat_monomial.c type RAT, monomial/ndrat_monomial.c type NDRAT) ---------------------------------
+ * The three bodies of each monomial with the shifted solutions resident in HBM.  fp64 one-parity fields, unsplit lattices only (a T-split
+ * context or its loopback rehearsal is refused).  mu / rmu / nu / rnu: the np entries (1 <= np <= 32) of the monomial's rational
+ * approximation (rational_t::mu, rmu, nu, rnu); max_iter, eps_sq, rel_prec and *iters as in tmhip_cg_mms_tm_nd / tmhip_cg_mms_tm, which do
+ * the solves into fields the context owns.  ndrat reads g_mubar, g_epsbar and the solver's phmc_invmaxev from tmhip_set_nd; `invmaxev` is
+ * the monomial's EVMaxInv that the reference passes to Q_tau1_sub_const_ndpsi and uses as forcefactor (the same number in a run).
+ * rat runs at twisted mass 0 as the reference sets g_mu = 0 (rat_monomial.c:62,156,222); the context's mu is back on return, errors included.
+ *   *_force       the loop over the shifts given the solutions (ndrat_monomial.c:114-160, forcefactor = invmaxev; rat_monomial.c:95-132,
+ *                 forcefactor = 1), ADDED to the derivative accumulator of tmhip_deriv_Sb: work fields for groups of "rat_batch" shifts
+ *                 (tmhip_set_option), then two tmhip_deriv_Sb_batch launches per group
+ *   *_derivative  solve, then the force (ndrat_monomial.c:96-160, rat_monomial.c:83-132)
+ *   *_heatbath    pf (and pf_dn) hold the Gaussian field on entry and C eta on exit; *energy0 = |eta|^2 (:212-254, rat :175-199)
+ *   *_acc         *energy1 = pf . (pf + sum_j rmu_j chi_j) (:281-309, rat :232-250); the caller forms energy1 - energy0 */
+int tmhip_ndrat_force(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev);
+int tmhip_ndrat_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                           int max_iter, double eps_sq, int rel_prec, int *iters);
+int tmhip_ndrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *nu, const double *rnu, int np, double invmaxev,
+                         int max_iter, double eps_sq, int rel_prec, double *energy0, int *iters);
+int tmhip_ndrat_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, int max_iter,
+                    double eps_sq, int rel_prec, double *energy1, int *iters);
+int tmhip_rat_force(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np);
+int tmhip_rat_derivative(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                         int *iters);
+int tmhip_rat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, const double *rnu, int np, int max_iter, double eps_sq, int rel_prec,
+                       double *energy0, int *iters);
+int tmhip_rat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                  double *energy1, int *iters);
 
 /* Clover part of the force (monomial/cloverdet_monomial.c:110-147): the insertion matrices swm / swp (clover_leaf.c:141) are
  * device-resident; zero them, accumulate the spinor outer products (operator/clover_deriv.c:252) and the tr-log term
@@ -421,6 +461,8 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                (alpha) and the (P, p) kernel (stopping test, beta) instead of two one-block sum + scalar kernels in between
  *   "nd_fused" 1 (default) | 0: the doublet operators (tmhip_*_ndpsi, the nd solvers) -- 1: one stencil per hop for both flavours with the
  *                flavour mixing in its epilogue; 0: two single-flavour stencils per hop and a mixing pass
+ *   "rat_batch" shifts per group of the rat / ndrat force (clamped to [1, 32], default 12, the fastest of 1 / 2 / 4 / 12
+ *                measured at 16^4 and 32^4 with np = 12, profiles/r08_rat_speed.log): one tmhip_deriv_Sb_batch launch per parity and group
  *   "gauge_global_sums" 0 (default) | 1: tmhip_measure_plaquette / _gauge_action / _rectangles return the rank's own share (0: the reference's value
  *                before its MPI_Allreduce) or the sum over the ranks of a T split (1: its return value; needs the communicator, like parallel = 1)
  *   "cg_sync" 1: host-side scalars as in the reference loop;  "cg_batch" n: iterations enqueued between two polls of `done`

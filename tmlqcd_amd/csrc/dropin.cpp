@@ -905,6 +905,14 @@ static tmhip_ctx *refresh_nd(const char *who) {
 ND_OP(Qtm_ndpsi, tmhip_Qtm_ndpsi)                /* tm_operators_nd.c:68-89 */
 ND_OP(Qtm_dagger_ndpsi, tmhip_Qtm_dagger_ndpsi)  /* :130-152 */
 ND_OP(Qtm_pm_ndpsi, tmhip_Qtm_pm_ndpsi)          /* :195-238 */
+void Q_tau1_sub_const_ndpsi(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c, const _Complex double z, const double Cpol,
+                            const double invev) {   /* :311-380 */
+  tmhip_ctx *c = refresh_nd("Q_tau1_sub_const_ndpsi");
+  tmhip_field *fks = in(c, k_s, TMHIP_FIELD_EO), *fkc = in(c, k_c, TMHIP_FIELD_EO);
+  tmhip_field *fls = out(c, l_s, TMHIP_FIELD_EO), *flc = out(c, l_c, TMHIP_FIELD_EO);
+  CK(tmhip_Q_tau1_sub_const_ndpsi(c, fls, flc, fks, fkc, __real__ z, __imag__ z, Cpol, invev));
+  done(c, l_s); done(c, l_c);
+}
 void M_ee_inv_ndpsi(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c, const double mu, const double eps) {   /* :639-696 */
   tmhip_ctx *c = refresh_nd("M_ee_inv_ndpsi");
   tmhip_field *fks = in(c, k_s, TMHIP_FIELD_EO), *fkc = in(c, k_c, TMHIP_FIELD_EO);
@@ -1306,6 +1314,16 @@ void assign_add_mul_r(spinor *const P, spinor *const Q, const double cc, const i
   const Parts pt = parts_of(kind, N);
   tmhip_field *fp = in(c, P, kind, N), *fq = in(c, Q, kind, N);
   for (int p = 0; p < pt.n; p++) CK(tmhip_assign_add_mul_r(c, half(fp, kind, p), half(fq, kind, p), cc, pt.cnt[p]));
+  done(c, P);
+}
+/* linalg/assign_add_mul.c: P += c Q, complex c */
+void assign_add_mul(spinor *const P, spinor *const Q, const _Complex double cc, const int N) {
+  tmhip_ctx *c = refresh(false);
+  if (N == 0) return;   /* an empty loop in the reference */
+  const int kind = kind_of_N(N);
+  const Parts pt = parts_of(kind, N);
+  tmhip_field *fp = in(c, P, kind, N), *fq = in(c, Q, kind, N);
+  for (int p = 0; p < pt.n; p++) CK(tmhip_assign_add_mul(c, half(fp, kind, p), half(fq, kind, p), __real__ cc, __imag__ cc, pt.cnt[p]));
   done(c, P);
 }
 /* linalg/assign_mul_add_r.c:340-377 */
@@ -1779,6 +1797,80 @@ void tmlqcd_hip_gauge_derivative(hamiltonian_field_t *const hf, const double bet
   CK(tmhip_gauge_derivative(c, beta, c0, c1, use_rectangles, glambda));
   g_deriv_pending = true;
   if (g_mode != TMLQCD_HIP_RESIDENT) tmlqcd_hip_flush_derivative(hf);
+}
+
+// ------------------------------------------------------------------ rational monomials (rational.hip)
+static tmhip_ctx *refresh_rat(const char *who) {
+  if (g_nproc_t > 1) {
+    char m[160];
+    snprintf(m, sizeof(m), "%s: the rational monomials run on unsplit lattices only", who);
+    die(m);
+  }
+  return refresh(true);
+}
+static void rat_force_done(hamiltonian_field_t *const hf) {
+  g_deriv_pending = true;
+  if (g_mode != TMLQCD_HIP_RESIDENT) tmlqcd_hip_flush_derivative(hf);
+}
+/* ndrat_monomial.c:96-160 */
+int tmlqcd_hip_ndrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np,
+                                const double EVMaxInv, const int max_iter, const double eps_sq, const int rel_prec) {
+  tmhip_ctx *c = refresh_nd("tmlqcd_hip_ndrat_derivative");
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  if (!g_deriv_pending) CK(tmhip_derivative_zero(c));
+  int iters = -1;
+  CK(tmhip_ndrat_derivative(c, fu, fd, mu, rmu, np, EVMaxInv, max_iter, eps_sq, rel_prec, &iters));
+  rat_force_done(hf);
+  return iters;
+}
+/* ndrat_monomial.c:212-254 */
+int tmlqcd_hip_ndrat_heatbath(spinor *const pf, spinor *const pf2, const double *nu, const double *rnu, const int np, const double EVMaxInv,
+                              const int max_iter, const double eps_sq, const int rel_prec, double *energy0) {
+  tmhip_ctx *c = refresh_nd("tmlqcd_hip_ndrat_heatbath");
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_ndrat_heatbath(c, fu, fd, nu, rnu, np, EVMaxInv, max_iter, eps_sq, rel_prec, energy0, &iters));
+  done(c, pf); done(c, pf2);
+  return iters;
+}
+/* ndrat_monomial.c:281-309 */
+int tmlqcd_hip_ndrat_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np, const int max_iter,
+                         const double eps_sq, const int rel_prec, double *energy1) {
+  tmhip_ctx *c = refresh_nd("tmlqcd_hip_ndrat_acc");
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_ndrat_acc(c, fu, fd, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, &iters));
+  return iters;
+}
+/* rat_monomial.c:83-132 (type RAT) */
+int tmlqcd_hip_rat_derivative(hamiltonian_field_t *const hf, spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter,
+                              const double eps_sq, const int rel_prec) {
+  tmhip_ctx *c = refresh_rat("tmlqcd_hip_rat_derivative");
+  tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
+  if (!g_deriv_pending) CK(tmhip_derivative_zero(c));
+  int iters = -1;
+  CK(tmhip_rat_derivative(c, f, mu, rmu, np, max_iter, eps_sq, rel_prec, &iters));
+  rat_force_done(hf);
+  return iters;
+}
+/* rat_monomial.c:175-199 */
+int tmlqcd_hip_rat_heatbath(spinor *const pf, const double *nu, const double *rnu, const int np, const int max_iter, const double eps_sq,
+                            const int rel_prec, double *energy0) {
+  tmhip_ctx *c = refresh_rat("tmlqcd_hip_rat_heatbath");
+  tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_rat_heatbath(c, f, nu, rnu, np, max_iter, eps_sq, rel_prec, energy0, &iters));
+  done(c, pf);
+  return iters;
+}
+/* rat_monomial.c:232-250 */
+int tmlqcd_hip_rat_acc(spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter, const double eps_sq,
+                       const int rel_prec, double *energy1) {
+  tmhip_ctx *c = refresh_rat("tmlqcd_hip_rat_acc");
+  tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_rat_acc(c, f, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, &iters));
+  return iters;
 }
 
 // ------------------------------------------------------------------ molecular dynamics with the links in HBM

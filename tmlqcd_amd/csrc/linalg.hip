@@ -109,6 +109,18 @@ __global__ __launch_bounds__(LA_BS) void stream_kernel(v2d *__restrict__ X, cons
   }
 }
 
+// P += c Q with complex c   (linalg/assign_add_mul.c); element-wise, so P may be Q
+__global__ __launch_bounds__(LA_BS) void caxpy_kernel(v2d *P, const v2d *Q, double cre, double cim, int ns, int N) {
+  v2d *p = P + (size_t)blockIdx.y * ns;
+  const v2d *q = Q + (size_t)blockIdx.y * ns;
+  const int base = blockIdx.x * LA_BS * LA_UNROLL + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < LA_UNROLL; u++) {
+    const int i = base + u * LA_BS;
+    if (i < N) { const v2d a = p[i], b = q[i]; p[i] = v2d{a.x + cre * b.x - cim * b.y, a.y + cre * b.y + cim * b.x}; }
+  }
+}
+
 // l = sigma_c * ( zc (.) k - beta * j ),  zc = z for spin 0,1 and conj(z) for spin 2,3,
 // sigma_c = -1 on spin 2,3 when g5 is set.  Covers mul_one_pm_imu_inv, assign_mul_one_pm_imu[_inv],
 // mul_one_pm_imu_sub_mul[_gamma5], gamma5.  Element-wise => alias-safe for l==k, l==j.
@@ -187,6 +199,14 @@ int tmhip_assign_add_mul_r(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, doubl
   if (check_eo(P, "assign_add_mul_r") || check_eo(Q, "assign_add_mul_r")) return 1;
   LA_CHECK_N("assign_add_mul_r", (void)0);
   hipLaunchKernelGGL(stream_kernel<0>, la_grid(N), dim3(LA_BS), 0, ctx->stream, P->d, Q->d, (const v2d *)nullptr, c, P->ns, N);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_assign_add_mul(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, double c_re, double c_im, int N) {
+  if (check_eo(P, "assign_add_mul") || check_eo(Q, "assign_add_mul")) return 1;
+  LA_CHECK_N("assign_add_mul", (void)0);
+  hipLaunchKernelGGL(caxpy_kernel, la_grid(N), dim3(LA_BS), 0, ctx->stream, P->d, (const v2d *)Q->d, c_re, c_im, P->ns, N);
   TMHIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -32,7 +32,7 @@ __device__ __forceinline__ v2d cfmac(v2d a, v2d b, v2d c) {  // c + conj(a)*b
 __device__ __forceinline__ v2d cmul(v2d a, v2d b) { return __builtin_elementwise_fma(v2d{-a.y, a.y}, v2d{b.y, b.x}, v2d{a.x, a.x} * b); }
 __device__ __forceinline__ v2d cmulc(v2d a, v2d b) { return __builtin_elementwise_fma(v2d{a.y, -a.y}, v2d{b.y, b.x}, v2d{a.x, a.x} * b); }
 
-enum { ND_EE_INV = 0, ND_OO = 1, ND_OO_DOT = 2 };
+enum { ND_EE_INV = 0, ND_OO = 1, ND_OO_DOT = 2, ND_OO_SUBC = 3 };
 
 struct NdArgs {
   v2d *out_s, *out_c;
@@ -45,6 +45,7 @@ struct NdArgs {
   int nxcd_chunk, map_nb;     // > 0: blocks b, b+8, .. share an XCD and take a contiguous chunk of the lattice
   double ka[4][2];
   double mu, eps, nrm, scale, sigma;
+  double cz[2];              // ND_OO_SUBC: out -= cz (.) the OTHER flavour's k (Q_tau1_sub_const_ndpsi: its k arrive swapped)
 };
 
 // projection (1 -+ gamma_mu) of one spinor for hop D = 2 mu + (0: +mu, 1: -mu); the same lines as hop_dir (hopping_impl.inc)
@@ -146,6 +147,11 @@ __device__ __forceinline__ double nd_epilogue(const NdArgs &a, int i, const v2d 
         os[c] = a.scale * (b == 0 ? phi1 - js : js - phi1);   // then mul_r(l, phmc_invmaxev, ..)
         oc[c] = a.scale * (b == 0 ? phi2 - jc : jc - phi2);
       }
+    }
+    if (EPI == ND_OO_SUBC) {          // l_strange -= Cpol z k_strange, l_charm -= Cpol z k_charm (tm_operators_nd.c:349-374); k_s, k_c hold (k_charm, k_strange)
+      const v2d cz = v2d{a.cz[0], a.cz[1]};
+#pragma unroll
+      for (int c = 0; c < 6; c++) { os[c] = os[c] - cmul(cz, kc[c]); oc[c] = oc[c] - cmul(cz, ks[c]); }
     }
     if (EPI == ND_OO_DOT) {           // the shifted operator of cg_mms_tm_nd.c:120-124 and its (p, A p) over both flavours
       v2d ps[6], pc[6];
@@ -369,10 +375,11 @@ static void nd_launch_mix(tmhip_ctx *ctx, const NdArgs &a, int N, int *npart) {
 // ND_EE_INV: mix(a, b; mu, eps) * nrm.  ND_OO[_DOT]: scale * [mix(k_s, k_c; mu, eps) -/+ (a, b)] (+ sigma p, partials of <p, out>).
 static int nd_stage(tmhip_ctx *ctx, int epi, int ieo, v2d *out_s, v2d *out_c, const v2d *in_a, const v2d *in_b, const v2d *k_s,
                     const v2d *k_c, double mu, double eps, double scale, const v2d *p_s = nullptr, const v2d *p_c = nullptr,
-                    double sigma = 0.0, int *npart = nullptr) {
+                    double sigma = 0.0, int *npart = nullptr, double cz_re = 0.0, double cz_im = 0.0) {
   TmhipNd *n = (TmhipNd *)ctx->nd;
   NdArgs a;
   nd_fill(a, ctx, ieo);
+  a.cz[0] = cz_re; a.cz[1] = cz_im;
   a.out_s = out_s; a.out_c = out_c; a.k_s = k_s; a.k_c = k_c; a.p_s = p_s; a.p_c = p_c;
   a.mu = mu; a.eps = eps; a.nrm = 1. / (1. + mu * mu - eps * eps); a.scale = scale; a.sigma = sigma;
   a.partials = n->partials;
@@ -383,6 +390,7 @@ static int nd_stage(tmhip_ctx *ctx, int epi, int ieo, v2d *out_s, v2d *out_c, co
 #define ND_HOP(E) (b64 ? nd_launch_hop<E, 64>(ctx, a, npart) : nd_launch_hop<E, 256>(ctx, a, npart))
     if (epi == ND_EE_INV) ND_HOP(ND_EE_INV);
     else if (epi == ND_OO) ND_HOP(ND_OO);
+    else if (epi == ND_OO_SUBC) ND_HOP(ND_OO_SUBC);
     else ND_HOP(ND_OO_DOT);
 #undef ND_HOP
   } else {
@@ -392,6 +400,7 @@ static int nd_stage(tmhip_ctx *ctx, int epi, int ieo, v2d *out_s, v2d *out_c, co
     a.in_a = ha; a.in_b = hb;
     if (epi == ND_EE_INV) nd_launch_mix<ND_EE_INV>(ctx, a, ctx->Vh, npart);
     else if (epi == ND_OO) nd_launch_mix<ND_OO>(ctx, a, ctx->Vh, npart);
+    else if (epi == ND_OO_SUBC) nd_launch_mix<ND_OO_SUBC>(ctx, a, ctx->Vh, npart);
     else nd_launch_mix<ND_OO_DOT>(ctx, a, ctx->Vh, npart);
   }
   TMHIP_CHECK(hipGetLastError());
@@ -544,6 +553,23 @@ int tmhip_Qtm_dagger_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, t
   // M_ee_inv(D2, D3; H k_c, H k_s; mubar, eps) ; l = invmaxev M_oo_sub_g5(k_s, k_c; j = (H D3, H D2); mubar, -eps)   (:130-152)
   if (nd_stage(ctx, ND_EE_INV, TMHIP_EO, d0, d1, k_c->d, k_s->d, nullptr, nullptr, mb, eb, 1.0)) return 1;
   return nd_stage(ctx, ND_OO, TMHIP_OE, l_s->d, l_c->d, d1, d0, k_s->d, k_c->d, mb, -eb, ctx->invmaxev);
+}
+
+/* Q_tau1_sub_const_ndpsi (tm_operators_nd.c:311-380): l = Cpol invev Qhat tau^1 k - Cpol z k.  Two stencil launches; the scaling and the
+ * subtraction of the constant are the epilogue of the second.  l must not be k (the reference hops into l before it reads k). */
+int tmhip_Q_tau1_sub_const_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, double z_re, double z_im,
+                                 double Cpol, double invev) {
+  if (nd_check4(ctx, "Q_tau1_sub_const_ndpsi", l_s, l_c, k_s, k_c)) return 1;
+  if (ctx->loopback) TMHIP_FAIL("Q_tau1_sub_const_ndpsi: unsplit lattices only (loopback)");
+  if (l_s->d == k_s->d || l_s->d == k_c->d || l_c->d == k_s->d || l_c->d == k_c->d) TMHIP_FAIL("Q_tau1_sub_const_ndpsi: l must not be k");
+  TmhipNd *n = (TmhipNd *)ctx->nd;
+  const double mb = ctx->mubar, eb = ctx->epsbar;
+  v2d *d0 = n->s[0]->d, *d1 = n->s[1]->d;
+  // M_ee_inv(D3, D2; H k_c, H k_s; mubar, eps)   (:323-328)
+  if (nd_stage(ctx, ND_EE_INV, TMHIP_EO, d1, d0, k_c->d, k_s->d, nullptr, nullptr, mb, eb, 1.0)) return 1;
+  // l = Cpol invev M_oo_sub_g5(k_c, k_s; j = (H D3, H D2); -mubar, -eps) - Cpol z (k_s, k_c)   (:330-374)
+  return nd_stage(ctx, ND_OO_SUBC, TMHIP_OE, l_s->d, l_c->d, d1, d0, k_c->d, k_s->d, -mb, -eb, Cpol * invev, nullptr, nullptr, 0.0, nullptr,
+                  Cpol * z_re, Cpol * z_im);
 }
 
 int tmhip_Qtm_pm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c) {

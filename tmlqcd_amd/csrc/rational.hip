@@ -1,0 +1,360 @@
+// Rational monomials on the device: rat (monomial/rat_monomial.c, type RAT) and ndrat (monomial/ndrat_monomial.c, type NDRAT),
+// fp64, unsplit lattices.
+//
+// The hot path is the hopping force.  ndrat_derivative calls deriv_Sb four times per shift (ndrat_monomial.c:140-160), rat_derivative
+// twice (rat_monomial.c:124-131); every call reads the same four links per site and does a read-modify-write of the same 32
+// derivative reals.  deriv_Sb_batch_kernel sums n (l, k, factor) pairs in ONE launch with the ownership of deriv_Sb_kernel
+// (force.hip: one thread per site of either parity owns its four forward links, no atomics): per link it accumulates
+//   T = sum_j 2 factor_j (v_j (x) u_j^dagger + z_j (x) w_j^dagger)          (3x3 complex; the coefficient is folded into v_j, z_j)
+// over the pairs, then forms ka_mu U_mu T once and projects it with the su3adj.h rule into the derivative field: links are read
+// once and the derivative is written once per launch, whatever n is.
+//
+// The directions are the outer loop: one T is live and the own-site spinor of a pair is read again per direction (from cache):
+// 164 VGPRs, three waves per SIMD, no scratch.  The other order (pairs outermost, four T live, every spinor read once) needs
+// 144 registers for the accumulators alone and spills at the two waves per SIMD the kernel is held to (tools/check_resources.py).
+//
+// The monomial bodies below are the reference's loops with the solutions kept in HBM: force (given the solutions), derivative
+// (solve + force), heatbath and acceptance energy.
+#include "tmhip_internal.h"
+#include "mshift.h"
+
+#define RAT_MAX_PAIRS 64
+
+namespace rathip {
+
+struct BatchArgs {
+  const v2d *l[RAT_MAX_PAIRS], *k[RAT_MAX_PAIRS];
+  double fac[RAT_MAX_PAIRS];   // 2 * factor_j
+  const v2d *g;                // gauge [2][8][9][gs]
+  double *deriv;               // [2][4][8][Vh]
+  int n, ns, gs, Vh, T, LX, LY, LZ, ieo;
+  double ka[4][2];
+};
+
+__device__ __forceinline__ v2d b_cmul(v2d a, v2d b) { return v2d{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ v2d b_cmulc(v2d a, v2d b) { return v2d{a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y}; }   // a conj(b)
+__device__ __forceinline__ v2d b_itimes(v2d a) { return v2d{-a.y, a.x}; }
+
+// (1 +- gamma_mu) of a 4-spinor s[spin][colour] as two 3-vectors; the lines of f_project (force.hip), MU a compile-time constant
+template <int MU>
+__device__ __forceinline__ void b_project(const v2d (&s)[4][3], bool plus, v2d (&a)[3], v2d (&b)[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (MU == 0) { a[c] = plus ? s[0][c] + s[2][c] : s[0][c] - s[2][c]; b[c] = plus ? s[1][c] + s[3][c] : s[1][c] - s[3][c]; }
+    if (MU == 1) { a[c] = plus ? s[0][c] + b_itimes(s[3][c]) : s[0][c] - b_itimes(s[3][c]);
+                   b[c] = plus ? s[1][c] + b_itimes(s[2][c]) : s[1][c] - b_itimes(s[2][c]); }
+    if (MU == 2) { a[c] = plus ? s[0][c] + s[3][c] : s[0][c] - s[3][c]; b[c] = plus ? s[1][c] - s[2][c] : s[1][c] + s[2][c]; }
+    if (MU == 3) { a[c] = plus ? s[0][c] + b_itimes(s[2][c]) : s[0][c] - b_itimes(s[2][c]);
+                   b[c] = plus ? s[1][c] - b_itimes(s[3][c]) : s[1][c] + b_itimes(s[3][c]); }
+  }
+}
+
+// the fields are only read, and one field may serve several pairs on either side: no __restrict__ between them is claimed
+__device__ __forceinline__ void b_load(const v2d *f, int ns, int idx, bool g5, v2d (&s)[4][3]) {
+#pragma unroll
+  for (int sp = 0; sp < 4; sp++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      v2d v = f[(size_t)(3 * sp + c) * ns + idx];
+      if (g5 && sp >= 2) v = v2d{-v.x, -v.y};
+      s[sp][c] = v;
+    }
+}
+
+// T += fac (v (x) u^dagger + z (x) w^dagger) for direction MU of one pair; own / nb: the site's and the +mu neighbour's spinor.
+// "+" sites (parity == ieo) carry g5 l, the neighbour k: (v, z) = projections of k, (u, w) = of g5 l.  "-" sites the other way round.
+template <int MU>
+__device__ __forceinline__ void b_accum(v2d (&t)[9], const v2d (&own)[4][3], const v2d (&nb)[4][3], bool plus, double fac) {
+  v2d oa[3], ob[3], na[3], nb2[3];
+  b_project<MU>(own, plus, oa, ob);
+  b_project<MU>(nb, plus, na, nb2);
+  // deriv_Sb_kernel: plus: (v, z) = (psia, psib) = nb, (u, w) = (phia, phib) = own;  minus: (v, z) = (phia, phib) = nb, (u, w) = (psia, psib) = own
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const v2d v = fac * na[r], z = fac * nb2[r];
+#pragma unroll
+    for (int c = 0; c < 3; c++) t[3 * r + c] += b_cmulc(v, oa[c]) + b_cmulc(z, ob[c]);
+  }
+}
+
+// df(y, mu) += trlambda(ka_mu U_mu(y) T)   (su3adj.h:164-172)
+__device__ __forceinline__ void b_finish(const v2d (&t)[9], const v2d *gp, size_t gs, int mu, v2d ka, double *d, size_t st) {
+  v2d U[9];
+#pragma unroll
+  for (int e = 0; e < 9; e++) U[e] = gp[(size_t)((2 * mu) * 9 + e) * gs];
+  v2d m[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+      m[r][c] = b_cmul(ka, b_cmul(U[3 * r], t[c]) + b_cmul(U[3 * r + 1], t[3 + c]) + b_cmul(U[3 * r + 2], t[6 + c]));
+  d[0 * st] += (-m[1][0].y - m[0][1].y);
+  d[1 * st] += (+m[1][0].x - m[0][1].x);
+  d[2 * st] += (-m[0][0].y + m[1][1].y);
+  d[3 * st] += (-m[2][0].y - m[0][2].y);
+  d[4 * st] += (+m[2][0].x - m[0][2].x);
+  d[5 * st] += (-m[2][1].y - m[1][2].y);
+  d[6 * st] += (+m[2][1].x - m[1][2].x);
+  d[7 * st] += ((-m[0][0].y - m[1][1].y + 2.0 * m[2][2].y) * 0.577350269189625);
+}
+
+__global__ __launch_bounds__(128, 2) void deriv_Sb_batch_kernel(const BatchArgs a) {
+  const int i = blockIdx.x * 128 + threadIdx.x;
+  if (i >= a.Vh) return;
+  const int par = blockIdx.y;
+  const bool plus = par == a.ieo;         // this site carries the left vectors l_j
+  const int LZh = a.LZ / 2;
+  const int kz = i % LZh;
+  int r = i / LZh;
+  const int y = r % a.LY;
+  r /= a.LY;
+  const int x = r % a.LX, t = r / a.LX;
+  const int o = (t + x + y + par) & 1;
+  const int z = 2 * kz + o;
+  const int row = (t * a.LX + x) * a.LY + y;   // lexic = row * LZ + z
+  int up[4];
+  up[0] = ((((t + 1) % a.T) * a.LX + x) * a.LY + y) * LZh + kz;
+  up[1] = ((t * a.LX + (x + 1) % a.LX) * a.LY + y) * LZh + kz;
+  up[2] = ((t * a.LX + x) * a.LY + (y + 1) % a.LY) * LZh + kz;
+  up[3] = (row * a.LZ + (z + 1) % a.LZ) >> 1;
+  const v2d *gp = a.g + (size_t)par * 72 * a.gs + i;
+  double *dp = a.deriv + (size_t)par * 32 * a.Vh + i;
+  const size_t st = a.Vh;
+#pragma unroll
+  for (int mu = 0; mu < 4; mu++) {
+    v2d t1[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) t1[e] = v2d{0.0, 0.0};
+    for (int j = 0; j < a.n; j++) {
+      const v2d *fo = plus ? a.l[j] : a.k[j], *fn = plus ? a.k[j] : a.l[j];
+      v2d own[4][3], nb[4][3];
+      b_load(fo, a.ns, i, plus, own);
+      b_load(fn, a.ns, up[mu], !plus, nb);
+      if (mu == 0) b_accum<0>(t1, own, nb, plus, a.fac[j]);
+      if (mu == 1) b_accum<1>(t1, own, nb, plus, a.fac[j]);
+      if (mu == 2) b_accum<2>(t1, own, nb, plus, a.fac[j]);
+      if (mu == 3) b_accum<3>(t1, own, nb, plus, a.fac[j]);
+    }
+    b_finish(t1, gp, a.gs, mu, v2d{a.ka[mu][0], a.ka[mu][1]}, dp + (size_t)mu * 8 * st, st);
+  }
+}
+}  // namespace rathip
+using namespace rathip;
+
+// ---------------------------------------------------------------- host side
+struct TmhipRat {
+  tmhip_field *chi_up[MSHIFT_MAX_SHIFTS], *chi_dn[MSHIFT_MAX_SHIFTS];   // solutions of the drivers (allocated as needed)
+  tmhip_field *w[6 * MSHIFT_MAX_SHIFTS];                               // work fields of the force groups, heatbath and acceptance
+};
+
+void tmhip_rat_destroy(tmhip_ctx *ctx) {
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (!r) return;
+  for (int k = 0; k < MSHIFT_MAX_SHIFTS; k++) { tmhip_field_free(ctx, r->chi_up[k]); tmhip_field_free(ctx, r->chi_dn[k]); }
+  for (int k = 0; k < 6 * MSHIFT_MAX_SHIFTS; k++) tmhip_field_free(ctx, r->w[k]);
+  delete r;
+  ctx->rat = nullptr;
+}
+
+static int rat_prepare(tmhip_ctx *ctx, const char *who, int np) {
+  if (ctx->g.nproc_t > 1 || ctx->loopback) TMHIP_FAIL("%s: unsplit lattices only (nproc_t = %d%s)", who, ctx->g.nproc_t, ctx->loopback ? ", loopback" : "");
+  if (!ctx->gauge_set) TMHIP_FAIL("%s called before tmhip_set_gauge", who);
+  if (np < 1 || np > MSHIFT_MAX_SHIFTS) TMHIP_FAIL("%s: np = %d is outside [1, %d]", who, np, MSHIFT_MAX_SHIFTS);
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (!ctx->rat) ctx->rat = new TmhipRat();
+  return 0;
+}
+static int rat_need(tmhip_ctx *ctx, tmhip_field **slot, int n) {
+  for (int k = 0; k < n; k++)
+    if (!slot[k] && tmhip_field_alloc(ctx, TMHIP_FIELD_EO, &slot[k])) return 1;
+  return 0;
+}
+static bool rat_eo(const tmhip_field *f) { return f && f->kind == TMHIP_FIELD_EO && f->prec == 0; }
+static int rat_group(const tmhip_ctx *ctx) { return ctx->opt_rat_batch < 1 ? 1 : (ctx->opt_rat_batch > MSHIFT_MAX_SHIFTS ? MSHIFT_MAX_SHIFTS : ctx->opt_rat_batch); }
+
+// rat runs at twisted mass 0 (rat_monomial.c:62,156,222): the context's mu is put back on every path out
+struct RatMuZero {
+  tmhip_ctx *ctx; double mu;
+  explicit RatMuZero(tmhip_ctx *c) : ctx(c), mu(c->mu) { c->mu = 0.0; }
+  ~RatMuZero() { ctx->mu = mu; }
+};
+
+static int ndrat_force_body(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev) {
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  const int G = rat_group(ctx);
+  if (rat_need(ctx, r->w, 6 * (G < np ? G : np))) return 1;
+  for (int hi = np - 1; hi >= 0; hi -= G) {   // the reference walks j downwards (ndrat_monomial.c:114)
+    const int lo = hi - G + 1 > 0 ? hi - G + 1 : 0, g = hi - lo + 1;
+    tmhip_field *l0[RAT_MAX_PAIRS], *k0[RAT_MAX_PAIRS], *l1[RAT_MAX_PAIRS], *k1[RAT_MAX_PAIRS];
+    double f[RAT_MAX_PAIRS];
+    for (int q = 0; q < g; q++) {
+      const int j = hi - q;
+      tmhip_field **w = r->w + 6 * q;
+      // Y_j,o = (Q_h tau^1 + i mu_j) X_j,o (:130-132), X_j,e (:136-137), Y_j,e (:152-153)
+      if (tmhip_Q_tau1_sub_const_ndpsi(ctx, w[0], w[1], chi_up[j], chi_dn[j], 0.0, -mu[j], 1.0, invmaxev)) return 1;
+      if (tmhip_H_eo_tm_ndpsi(ctx, w[2], w[3], chi_up[j], chi_dn[j], TMHIP_EO)) return 1;
+      if (tmhip_H_eo_tm_ndpsi(ctx, w[4], w[5], w[0], w[1], TMHIP_EO)) return 1;
+      f[2 * q] = f[2 * q + 1] = rmu[j] * invmaxev;                                      // forcefactor = EVMaxInv (:94)
+      l0[2 * q] = w[2]; k0[2 * q] = w[0]; l0[2 * q + 1] = w[3]; k0[2 * q + 1] = w[1];   // deriv_Sb(EO, ..) (:140-143)
+      l1[2 * q] = chi_up[j]; k1[2 * q] = w[4]; l1[2 * q + 1] = chi_dn[j]; k1[2 * q + 1] = w[5];   // deriv_Sb(OE, ..) (:157-160)
+    }
+    if (tmhip_deriv_Sb_batch(ctx, TMHIP_EO, 2 * g, l0, k0, f) || tmhip_deriv_Sb_batch(ctx, TMHIP_OE, 2 * g, l1, k1, f)) return 1;
+  }
+  return 0;
+}
+
+static int rat_force_body(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np) {
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  const int G = rat_group(ctx);
+  if (rat_need(ctx, r->w, 3 * (G < np ? G : np))) return 1;
+  for (int hi = np - 1; hi >= 0; hi -= G) {   // rat_monomial.c:95
+    const int lo = hi - G + 1 > 0 ? hi - G + 1 : 0, g = hi - lo + 1;
+    tmhip_field *l0[RAT_MAX_PAIRS], *k0[RAT_MAX_PAIRS], *l1[RAT_MAX_PAIRS], *k1[RAT_MAX_PAIRS];
+    double f[RAT_MAX_PAIRS];
+    for (int q = 0; q < g; q++) {
+      const int j = hi - q;
+      tmhip_field *w0 = r->w[3 * q], *w2 = r->w[3 * q + 1], *w3 = r->w[3 * q + 2];
+      if (tmhip_Qtm_plus_psi(ctx, w0, chi[j])) return 1;                        // Y_o = Qp X_o (:96)
+      if (tmhip_H_eo_tm_inv_psi(ctx, w2, chi[j], TMHIP_EO, -1.0)) return 1;     // X_e (:122)
+      if (tmhip_H_eo_tm_inv_psi(ctx, w3, w0, TMHIP_EO, +1.0)) return 1;         // Y_e (:128)
+      f[q] = rmu[j];                                                            // forcefactor = 1 (:81)
+      l1[q] = w0; k1[q] = w2;                                                   // deriv_Sb(OE, w0, w2) (:124)
+      l0[q] = w3; k0[q] = chi[j];                                               // deriv_Sb(EO, w3, X_o) (:130)
+    }
+    if (tmhip_deriv_Sb_batch(ctx, TMHIP_OE, g, l1, k1, f) || tmhip_deriv_Sb_batch(ctx, TMHIP_EO, g, l0, k0, f)) return 1;
+  }
+  return 0;
+}
+
+static int rat_check_fields(const char *who, tmhip_field *const *a, tmhip_field *const *b, int n) {
+  for (int j = 0; j < n; j++)
+    if (!rat_eo(a[j]) || (b && !rat_eo(b[j]))) TMHIP_FAIL("%s needs fp64 one-parity (EO) fields", who);
+  return 0;
+}
+
+extern "C" {
+
+int tmhip_deriv_Sb_batch(tmhip_ctx *ctx, int ieo, int n, tmhip_field **l, tmhip_field **k, const double *factor) {
+  if (n < 1 || n > RAT_MAX_PAIRS) TMHIP_FAIL("deriv_Sb_batch: n = %d is outside [1, %d]", n, RAT_MAX_PAIRS);
+  if (!l || !k || !factor) TMHIP_FAIL("deriv_Sb_batch: null argument");
+  for (int j = 0; j < n; j++) {
+    if (!rat_eo(l[j]) || !rat_eo(k[j])) TMHIP_FAIL("deriv_Sb_batch needs fp64 one-parity fields (pair %d)", j);
+    if (l[j]->ns != l[0]->ns || k[j]->ns != l[0]->ns) TMHIP_FAIL("deriv_Sb_batch: fields with different strides (pair %d)", j);
+  }
+  if (!ctx->gauge_set) TMHIP_FAIL("deriv_Sb_batch called before tmhip_set_gauge");
+  if (ctx->g.nproc_t > 1 || ctx->loopback) TMHIP_FAIL("deriv_Sb_batch: unsplit lattices only (nproc_t = %d%s)", ctx->g.nproc_t, ctx->loopback ? ", loopback" : "");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (!ctx->deriv && tmhip_derivative_zero(ctx)) return 1;
+  BatchArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < n; j++) { a.l[j] = l[j]->d; a.k[j] = k[j]->d; a.fac[j] = 2. * factor[j]; }
+  a.g = ctx->gauge; a.deriv = ctx->deriv;
+  a.n = n; a.ns = l[0]->ns; a.gs = ctx->gs; a.Vh = ctx->Vh; a.T = ctx->g.T; a.LX = ctx->g.LX; a.LY = ctx->g.LY; a.LZ = ctx->g.LZ; a.ieo = ieo ? 1 : 0;
+  for (int mu = 0; mu < 4; mu++) { a.ka[mu][0] = ctx->ka[mu][0]; a.ka[mu][1] = ctx->ka[mu][1]; }
+  const dim3 grid((ctx->Vh + 127) / 128, 2);
+  hipLaunchKernelGGL(deriv_Sb_batch_kernel, grid, dim3(128), 0, ctx->stream, a);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_ndrat_force(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev) {
+  if (rat_prepare(ctx, "ndrat_force", np)) return 1;
+  if (!mu || !rmu || !chi_up || !chi_dn) TMHIP_FAIL("ndrat_force: null argument");
+  if (rat_check_fields("ndrat_force", chi_up, chi_dn, np)) return 1;
+  return ndrat_force_body(ctx, chi_up, chi_dn, mu, rmu, np, invmaxev);
+}
+
+int tmhip_ndrat_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                           int max_iter, double eps_sq, int rel_prec, int *iters) {
+  if (rat_prepare(ctx, "ndrat_derivative", np)) return 1;
+  if (!mu || !rmu || !iters || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndrat_derivative: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np)) return 1;
+  if (tmhip_cg_mms_tm_nd(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, iters)) return 1;   // :111
+  return ndrat_force_body(ctx, r->chi_up, r->chi_dn, mu, rmu, np, invmaxev);
+}
+
+int tmhip_ndrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *nu, const double *rnu, int np, double invmaxev,
+                         int max_iter, double eps_sq, int rel_prec, double *energy0, int *iters) {
+  if (rat_prepare(ctx, "ndrat_heatbath", np)) return 1;
+  if (!nu || !rnu || !iters || !energy0 || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndrat_heatbath: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np) || rat_need(ctx, r->w, 2)) return 1;
+  double ea, eb;
+  if (tmhip_square_norm(ctx, pf_up, ctx->Vh, 1, &ea) || tmhip_square_norm(ctx, pf_dn, ctx->Vh, 1, &eb)) return 1;   // :214,217
+  *energy0 = ea + eb;
+  if (tmhip_cg_mms_tm_nd(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, nu, np, max_iter, eps_sq, rel_prec, iters)) return 1;   // :232
+  for (int j = np - 1; j >= 0; j--) {   // pf += i rnu_j (Q_h tau^1 - i nu_j) chi_j   (:239-254)
+    if (tmhip_Q_tau1_sub_const_ndpsi(ctx, r->w[0], r->w[1], r->chi_up[j], r->chi_dn[j], 0.0, nu[j], 1.0, invmaxev)) return 1;
+    if (tmhip_assign_add_mul(ctx, pf_up, r->w[0], 0.0, rnu[j], ctx->Vh) || tmhip_assign_add_mul(ctx, pf_dn, r->w[1], 0.0, rnu[j], ctx->Vh)) return 1;
+  }
+  return 0;
+}
+
+int tmhip_ndrat_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, int max_iter,
+                    double eps_sq, int rel_prec, double *energy1, int *iters) {
+  if (rat_prepare(ctx, "ndrat_acc", np)) return 1;
+  if (!mu || !rmu || !iters || !energy1 || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndrat_acc: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np) || rat_need(ctx, r->w, 2)) return 1;
+  if (tmhip_cg_mms_tm_nd(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, iters)) return 1;   // :295
+  if (tmhip_assign(ctx, r->w[0], pf_up, ctx->Vh) || tmhip_assign(ctx, r->w[1], pf_dn, ctx->Vh)) return 1;                // :299-300
+  for (int j = np - 1; j >= 0; j--)                                                                                        // :301-306
+    if (tmhip_assign_add_mul_r(ctx, r->w[0], r->chi_up[j], rmu[j], ctx->Vh) || tmhip_assign_add_mul_r(ctx, r->w[1], r->chi_dn[j], rmu[j], ctx->Vh)) return 1;
+  double ea, eb;
+  if (tmhip_scalar_prod_r(ctx, pf_up, r->w[0], ctx->Vh, 1, &ea) || tmhip_scalar_prod_r(ctx, pf_dn, r->w[1], ctx->Vh, 1, &eb)) return 1;   // :308-309
+  *energy1 = ea + eb;
+  return 0;
+}
+
+int tmhip_rat_force(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np) {
+  if (rat_prepare(ctx, "rat_force", np)) return 1;
+  if (!rmu || !chi) TMHIP_FAIL("rat_force: null argument");
+  if (rat_check_fields("rat_force", chi, nullptr, np)) return 1;
+  RatMuZero z(ctx);
+  return rat_force_body(ctx, chi, rmu, np);
+}
+
+int tmhip_rat_derivative(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                         int *iters) {
+  if (rat_prepare(ctx, "rat_derivative", np)) return 1;
+  if (!mu || !rmu || !iters || !rat_eo(pf)) TMHIP_FAIL("rat_derivative: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np)) return 1;
+  RatMuZero z(ctx);
+  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, mu, np, max_iter, eps_sq, rel_prec, ctx->Vh, TMHIP_OP_QTM_PM, iters, nullptr)) return 1;   // :92
+  return rat_force_body(ctx, r->chi_up, rmu, np);
+}
+
+int tmhip_rat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, const double *rnu, int np, int max_iter, double eps_sq, int rel_prec,
+                       double *energy0, int *iters) {
+  if (rat_prepare(ctx, "rat_heatbath", np)) return 1;
+  if (!nu || !rnu || !iters || !energy0 || !rat_eo(pf)) TMHIP_FAIL("rat_heatbath: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->w, 1)) return 1;
+  RatMuZero z(ctx);
+  if (tmhip_square_norm(ctx, pf, ctx->Vh, 1, energy0)) return 1;                                                                      // :177
+  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, nu, np, max_iter, eps_sq, rel_prec, ctx->Vh, TMHIP_OP_QTM_PM, iters, nullptr)) return 1;   // :188
+  for (int j = np - 1; j >= 0; j--) {   // pf += i rnu_j (Q - i nu_j) chi_j   (:194-199)
+    if (tmhip_Qtm_plus_psi(ctx, r->w[0], r->chi_up[j])) return 1;
+    if (tmhip_assign_add_mul(ctx, r->w[0], r->chi_up[j], 0.0, -nu[j], ctx->Vh)) return 1;
+    if (tmhip_assign_add_mul(ctx, pf, r->w[0], 0.0, rnu[j], ctx->Vh)) return 1;
+  }
+  return 0;
+}
+
+int tmhip_rat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                  double *energy1, int *iters) {
+  if (rat_prepare(ctx, "rat_acc", np)) return 1;
+  if (!mu || !rmu || !iters || !energy1 || !rat_eo(pf)) TMHIP_FAIL("rat_acc: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->w, 1)) return 1;
+  RatMuZero z(ctx);
+  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, mu, np, max_iter, eps_sq, rel_prec, ctx->Vh, TMHIP_OP_QTM_PM, iters, nullptr)) return 1;   // :240
+  if (tmhip_assign(ctx, r->w[0], pf, ctx->Vh)) return 1;                                                                              // :244
+  for (int j = np - 1; j >= 0; j--)
+    if (tmhip_assign_add_mul_r(ctx, r->w[0], r->chi_up[j], rmu[j], ctx->Vh)) return 1;                                                // :245-248
+  return tmhip_scalar_prod_r(ctx, pf, r->w[0], ctx->Vh, 1, energy1);                                                                  // :250
+}
+
+}  // extern "C"

@@ -167,6 +167,8 @@ struct tmhip_ctx {
   // non-degenerate doublet (nd.hip): g_mubar, g_epsbar (global.h:202), phmc_invmaxev (phmc.h:31); work fields and solver state
   double mubar, epsbar, invmaxev;
   void *nd; int nd_active_shifts;
+  void *rat;                          // rational monomials (rational.hip): solution and work fields
+  int opt_rat_batch;                  // shifts per deriv_Sb_batch launch of the rat / ndrat force
   void *mms; int mms_active_shifts;   // single-flavour multi-shift CG (mms.hip): work fields and solver state
   double gauge_recon_dev;   // max |U_row2 - conj(row0 x row1)| over all links of the resident gauge field (-1: not measured)
 };
@@ -330,6 +332,7 @@ int tmhip_exchange_gauge_halo(tmhip_ctx *ctx);   // md_update.hip: t = 0 / T-1 s
 int tmhip_resort_gauge(tmhip_ctx *ctx);   // md_update.hip: stencil gauge copy from the device-resident lexicographic links
 int tmhip_prepare_clover32(tmhip_ctx *ctx);  // fp32 gauge copy + fp32 scratch / solver fields
 void tmhip_nd_destroy(tmhip_ctx *ctx);   // nd.hip: work fields and state of the doublet
+void tmhip_rat_destroy(tmhip_ctx *ctx);  // rational.hip: solution and work fields of the rational monomials
 void tmhip_mms_destroy(tmhip_ctx *ctx);  // mms.hip: work fields and state of the single-flavour multi-shift CG
 // launch geometry shared by linalg.hip and cg.hip
 #define LA_BS 256

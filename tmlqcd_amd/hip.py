@@ -164,6 +164,17 @@ def load_library():
         "tmhip_cg_mms_tm": [vp, C.POINTER(vp), vp, pd, i, i, d, i, i, i, C.POINTER(i), pd],
         "tmhip_mms_active_shifts": [vp],
         "tmhip_mms_form": [vp],
+        "tmhip_deriv_Sb_batch": [vp, i, i, C.POINTER(vp), C.POINTER(vp), pd],
+        "tmhip_Q_tau1_sub_const_ndpsi": [vp, vp, vp, vp, vp, d, d, d, d],
+        "tmhip_assign_add_mul": [vp, vp, vp, d, d, i],
+        "tmhip_ndrat_force": [vp, C.POINTER(vp), C.POINTER(vp), pd, pd, i, d],
+        "tmhip_ndrat_derivative": [vp, vp, vp, pd, pd, i, d, i, d, i, C.POINTER(i)],
+        "tmhip_ndrat_heatbath": [vp, vp, vp, pd, pd, i, d, i, d, i, pd, C.POINTER(i)],
+        "tmhip_ndrat_acc": [vp, vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
+        "tmhip_rat_force": [vp, C.POINTER(vp), pd, i],
+        "tmhip_rat_derivative": [vp, vp, pd, pd, i, i, d, i, C.POINTER(i)],
+        "tmhip_rat_heatbath": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
+        "tmhip_rat_acc": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -339,6 +350,15 @@ class Lattice:
     def deriv_Sb(self, ieo, l, k, factor):
         """deriv_Sb.c:401: accumulate the hopping part of the fermion force into the device-resident derivative field."""
         _ck(self.lib.tmhip_deriv_Sb(self.h, ieo, l.h, k.h, factor), "deriv_Sb")
+
+    def deriv_Sb_batch(self, ieo, ls, ks, factors):
+        """sum_j deriv_Sb(ieo, ls[j], ks[j], factors[j]) in one kernel launch (1 <= len <= 64 pairs; unsplit lattices)."""
+        n = len(ls)
+        if len(ks) != n or len(factors) != n:
+            raise TmHipError("deriv_Sb_batch: ls, ks and factors must have the same length")
+        m = max(n, 1)
+        _ck(self.lib.tmhip_deriv_Sb_batch(self.h, ieo, n, (C.c_void_p * m)(*[f.h for f in ls]), (C.c_void_p * m)(*[f.h for f in ks]),
+                                          (C.c_double * m)(*factors)), "deriv_Sb_batch")
 
     def derivative(self, into=None):
         """The accumulated derivative as su3adj df[V][4][8]; with `into`, added to that host array (accumulate)."""
@@ -610,6 +630,11 @@ class Lattice:
     def assign_add_mul_r(self, P, Q, c, N):
         _ck(self.lib.tmhip_assign_add_mul_r(self.h, P.h, Q.h, c, N), "assign_add_mul_r")
 
+    def assign_add_mul(self, P, Q, c, N):
+        """linalg/assign_add_mul.c: P += c Q with complex c"""
+        c = complex(c)
+        _ck(self.lib.tmhip_assign_add_mul(self.h, P.h, Q.h, c.real, c.imag, N), "assign_add_mul")
+
     def assign_mul_add_r(self, R, c, S, N):
         _ck(self.lib.tmhip_assign_mul_add_r(self.h, R.h, c, S.h, N), "assign_mul_add_r")
 
@@ -663,6 +688,11 @@ class Lattice:
     def H_eo_tm_ndpsi(self, l_s, l_c, k_s, k_c, ieo):
         _ck(self.lib.tmhip_H_eo_tm_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h, ieo), "H_eo_tm_ndpsi")
 
+    def Q_tau1_sub_const_ndpsi(self, l_s, l_c, k_s, k_c, z, Cpol, invev):
+        """tm_operators_nd.c:311-380: l = Cpol invev Qhat tau^1 k - Cpol z k (complex z)"""
+        z = complex(z)
+        _ck(self.lib.tmhip_Q_tau1_sub_const_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h, z.real, z.imag, Cpol, invev), "Q_tau1_sub_const_ndpsi")
+
     def cg_her_nd(self, P_up, P_dn, Q_up, Q_dn, max_iter, eps_sq, rel_prec, N):
         """solver/cg_her_nd.c with f = Qtm_pm_ndpsi; returns the reference's return value (iterations or -1)."""
         it = C.c_int()
@@ -708,6 +738,62 @@ class Lattice:
     def mms_form(self):
         """0: fused e/o stencils, 1: unfused e/o form, 2: FULL composite (the last cg_mms_tm)"""
         return self.lib.tmhip_mms_form(self.h)
+
+    # --- rational monomials (monomial/ndrat_monomial.c NDRAT, monomial/rat_monomial.c RAT; rational.hip) -----------------
+    @staticmethod
+    def _da(x):
+        x = [float(v) for v in x]
+        return (C.c_double * max(len(x), 1))(*x), len(x)
+
+    def ndrat_force(self, chi, mu, rmu, invmaxev):
+        """ndrat_monomial.c:114-160 given the solutions chi = [(up_j, dn_j) ...]; added to the derivative accumulator."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        vp = C.c_void_p * max(n, 1)
+        _ck(self.lib.tmhip_ndrat_force(self.h, vp(*[p[0].h for p in chi]), vp(*[p[1].h for p in chi]), m, r, n, invmaxev), "ndrat_force")
+
+    def ndrat_derivative(self, pf_up, pf_dn, mu, rmu, invmaxev, max_iter, eps_sq, rel_prec):
+        """ndrat_monomial.c:96-160 (solve + force); returns the solver's iteration count."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it = C.c_int()
+        _ck(self.lib.tmhip_ndrat_derivative(self.h, pf_up.h, pf_dn.h, m, r, n, invmaxev, max_iter, eps_sq, rel_prec, C.byref(it)), "ndrat_derivative")
+        return it.value
+
+    def ndrat_heatbath(self, pf_up, pf_dn, nu, rnu, invmaxev, max_iter, eps_sq, rel_prec):
+        """ndrat_monomial.c:212-254: pf holds eta on entry, C eta on exit; returns (energy0, iterations)."""
+        (m, n), (r, _) = self._da(nu), self._da(rnu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_ndrat_heatbath(self.h, pf_up.h, pf_dn.h, m, r, n, invmaxev, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "ndrat_heatbath")
+        return e.value, it.value
+
+    def ndrat_acc(self, pf_up, pf_dn, mu, rmu, max_iter, eps_sq, rel_prec):
+        """ndrat_monomial.c:281-309; returns (energy1, iterations)."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_ndrat_acc(self.h, pf_up.h, pf_dn.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "ndrat_acc")
+        return e.value, it.value
+
+    def rat_force(self, chi, rmu):
+        """rat_monomial.c:95-132 (type RAT) given the solutions chi = [chi_j ...]; runs at twisted mass 0."""
+        r, n = self._da(rmu)
+        _ck(self.lib.tmhip_rat_force(self.h, (C.c_void_p * max(n, 1))(*[f.h for f in chi]), r, n), "rat_force")
+
+    def rat_derivative(self, pf, mu, rmu, max_iter, eps_sq, rel_prec):
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it = C.c_int()
+        _ck(self.lib.tmhip_rat_derivative(self.h, pf.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(it)), "rat_derivative")
+        return it.value
+
+    def rat_heatbath(self, pf, nu, rnu, max_iter, eps_sq, rel_prec):
+        (m, n), (r, _) = self._da(nu), self._da(rnu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_rat_heatbath(self.h, pf.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "rat_heatbath")
+        return e.value, it.value
+
+    def rat_acc(self, pf, mu, rmu, max_iter, eps_sq, rel_prec):
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_rat_acc(self.h, pf.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "rat_acc")
+        return e.value, it.value
 
     # --- multi-GPU --------------------------------------------------------
     def comm_unique_id(self):
