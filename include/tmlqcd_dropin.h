@@ -182,7 +182,7 @@ int rg_mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params solve
  * g_mubar, g_epsbar (global.h:202) and phmc_invmaxev (phmc.h:31) are read at every call (weak references: a host program
  * without them gets 0, 0, 1).  Unsplit lattices only: with g_nproc_t > 1 every symbol below ends the program with a message.
  * The output pair may be the input pair where the reference allows it (Qtm_pm_ndpsi, M_ee_inv_ndpsi, H_eo_tm_ndpsi,
- * mul_one_pm_itau2).  The clover doublet and the polynomial helpers (Qsw_*_ndpsi, P_ndpsi, Qtau1_P_ndpsi, ...) are not here. */
+ * mul_one_pm_itau2).  The polynomial helpers (P_ndpsi, Qtau1_P_ndpsi, ...) are not here; the clover doublet follows below. */
 typedef void (*matrix_mult_nd)(spinor *const, spinor *const, spinor *const, spinor *const);   /* solver/matrix_mult_typedef.h:33 */
 void Qtm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);          /* :68-89 */
 void Qtm_dagger_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);   /* :130-152 */
@@ -193,11 +193,39 @@ void mul_one_pm_itau2(spinor *const p, spinor *const q, spinor *const r, spinor 
 /* :311-380; l must not be k (the reference hops into l before it reads k) */
 void Q_tau1_sub_const_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm,
                             const _Complex double z, const double Cpol, const double invev);
-/* solver/cg_her_nd.c:57-160 and solver/cg_mms_tm_nd.c:64-215 run on the device for f / M_ndpsi = Qtm_pm_ndpsi on N = VOLUME/2
- * sites (up to 32 shifts); anything else ends the program with a message */
+/* solver/cg_her_nd.c:57-160 and solver/cg_mms_tm_nd.c:64-215 run on the device for f / M_ndpsi = Qtm_pm_ndpsi or Qsw_pm_ndpsi on
+ * N = VOLUME/2 sites (up to 32 shifts); anything else ends the program with a message */
 int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *const Q_dn, const int max_iter, double eps_sq,
               const int rel_prec, const int N, matrix_mult_nd f);
 int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *solver_params);
+/* ---- the clover doublet: operator/tm_operators_nd.h (Qsw_*), operator/clovertm_operators.h (the _nd functions), operator/clover_leaf.h ----
+ * fp64, unsplit lattices.  The device's clover term must belong to the current links (tmlqcd_hip_sw_term, or the host's sw_term followed
+ * by tmlqcd_hip_update_clover), and sw_invert_nd(mubar^2 - epsbar^2) must have run on it, as ndrat_monomial.c:89-91 does; otherwise every
+ * symbol below ends the program with a message.  sw_invert_nd keeps its result on the device beside sw_inv (cloverdet's inverse is not
+ * overwritten there) and copies it into the first VOLUME/2 entries of the host's sw_inv when the program has one, where the reference puts
+ * it.  sw_deriv_nd adds to the device-resident swm / swp of tmlqcd_hip_swpm_zero / tmlqcd_hip_sw_all.  These two are site-local and
+ * also run on T-split ranks; everything else of this block ends the program there.  A program that keeps the reference's
+ * clover_invert.o / clover_deriv.o on its link line resolves these two names there, not here.
+ * Order when cloverdet and the clover doublet alternate: tmlqcd_hip_sw_term, tmlqcd_hip_sw_invert(EE, mu), THEN sw_invert_nd.  A
+ * degenerate clover symbol called after sw_invert_nd without tmlqcd_hip_sw_invert in between uploads the host's sw / sw_inv again --
+ * whose first half now holds the doublet's inverse -- and drops sw_inv_nd.
+ * tmlqcd_hip_sw_invert_failures() returns six_invert's count of near-singular pivots of the last inversion (the reference prints it).
+ * Not here: the fp32 twins (Qsw_pm_ndpsi_32), Qsw_pm_ndbipsi, clover_nd, sw_trace_nd. */
+void sw_invert_nd(const double mshift);                                                                                  /* clover_invert.c:440 */
+void sw_deriv_nd(const int ieo);                                                                                         /* clover_deriv.c:156 */
+int tmlqcd_hip_sw_invert_failures(void);
+void assign_mul_one_sw_pm_imu_eps(const int ieo, spinor *const k_s, spinor *const k_c, const spinor *const l_s, const spinor *const l_c,
+                                  const double mu, const double eps);                                                    /* clovertm_operators.c:960 */
+void clover_inv_nd(const int ieo, spinor *const l_c, spinor *const l_s);                                                 /* :352 */
+void clover_gamma5_nd(const int ieo, spinor *const l_c, spinor *const l_s, const spinor *const k_c, const spinor *const k_s,
+                      const spinor *const j_c, const spinor *const j_s, const double mubar, const double epsbar);        /* :733 */
+void Qsw_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);          /* tm_operators_nd.c:91-111 */
+void Qsw_dagger_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);   /* :154-174 */
+void Qsw_pm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);       /* :240-285 */
+void Qsw_tau1_sub_const_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm,
+                              const _Complex double z, const double Cpol, const double invev);                            /* :378-444; l != k */
+void H_eo_sw_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);      /* :521-535 */
+void Msw_ee_inv_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);   /* :539-549 */
 
 /* ---- solver/cg_mms_tm.h:31: the single-flavour multi-shift CG (solver/cg_mms_tm.c:65-197) ----------------------------------
  * Device-resident (tmhip_cg_mms_tm) for M_psi = Qtm_pm_psi / Qsw_pm_psi with sdim = VOLUME/2 and M_psi = Q_pm_psi (no clover term)
@@ -304,6 +332,18 @@ int tmlqcd_hip_ndrat_heatbath(spinor *const pf, spinor *const pf2, const double 
                               const int max_iter, const double eps_sq, const int rel_prec, double *energy0);
 int tmlqcd_hip_ndrat_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np, const int max_iter,
                          const double eps_sq, const int rel_prec, double *energy1);
+/* type NDCLOVERRAT: the same three bodies on the clover doublet (Qsw_pm_ndpsi, Qsw_tau1_sub_const_ndpsi, H_eo_sw_ndpsi).  The derivative also
+ * does the clover part of ndrat_monomial.c:80-86, :162-184 on the device: swm / swp zeroed, four sw_spinor_eo per shift, sw_deriv_nd(EE)
+ * when trlog is set, sw_all(kappa, c_sw).  The caller runs tmlqcd_hip_sw_term and sw_invert_nd(mubar^2 - epsbar^2) first (:89-91).  The
+ * clover term must come from tmlqcd_hip_sw_term (it keeps the links sw_all walks): with the host's own sw_term + tmlqcd_hip_update_clover
+ * the operators and solvers run, the derivative ends the program with a message before it touches anything. */
+int tmlqcd_hip_ndcloverrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np,
+                                      const double EVMaxInv, const double kappa, const double c_sw, const int trlog, const int max_iter,
+                                      const double eps_sq, const int rel_prec);
+int tmlqcd_hip_ndcloverrat_heatbath(spinor *const pf, spinor *const pf2, const double *nu, const double *rnu, const int np, const double EVMaxInv,
+                                    const int max_iter, const double eps_sq, const int rel_prec, double *energy0);
+int tmlqcd_hip_ndcloverrat_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np, const int max_iter,
+                               const double eps_sq, const int rel_prec, double *energy1);
 int tmlqcd_hip_rat_derivative(hamiltonian_field_t *const hf, spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter,
                               const double eps_sq, const int rel_prec);
 int tmlqcd_hip_rat_heatbath(spinor *const pf, const double *nu, const double *rnu, const int np, const int max_iter, const double eps_sq,

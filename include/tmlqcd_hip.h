@@ -175,6 +175,58 @@ int tmhip_cg_mms_tm_nd(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmh
 /* shifts still active at the end of the last tmhip_cg_mms_tm_nd (the reference's local `shifts`, cg_mms_tm_nd.c:68,163) */
 int tmhip_nd_active_shifts(tmhip_ctx *ctx);
 
+/* ---- the clover doublet (Qsw_*_ndpsi of operator/tm_operators_nd.c, the _nd functions of operator/clovertm_operators.c) ----------
+ * Unsplit lattices, fp64: a T-split context or its loopback rehearsal is refused with a message before any launch.  The caller has run
+ * tmhip_sw_term and tmhip_sw_invert_nd(mubar^2 - epsbar^2) on the current links; whatever invalidates the clover term (tmhip_sw_term,
+ * tmhip_set_clover, tmhip_update_gauge, an ILDG read) drops sw_inv_nd with it, and every consumer then refuses with a message.
+ * mubar, epsbar and phmc_invmaxev come from tmhip_set_nd.  "nd_fused" 1 / 0 selects the doublet stencil with the clover mixing as its
+ * epilogue / two single-flavour stencils and one site-local pass, as for the twisted-mass doublet. */
+/* sw_invert_nd(mshift)   operator/clover_invert.c:440-495: ((1+T)^2 + mshift)^-1 on the even sites.  Deviation: the reference overwrites
+ * sw_inv; here the result lives in an array of its own (all four 3x3 blocks per chirality, 1152 bytes per even site), so cloverdet and
+ * ndcloverrat alternate without inverting again.  tmhip_get_clover_nd returns it as su3 sw_inv[VOLUME/2][4][2].
+ * tmhip_sw_invert_nd and tmhip_sw_deriv_nd are site-local and run on T-split contexts too; every operator, solver and monomial refuses. */
+int tmhip_sw_invert_nd(tmhip_ctx *ctx, double mshift);
+int tmhip_get_clover_nd(tmhip_ctx *ctx, void *sw_inv_host);
+/* near-singular pivots met by the last tmhip_sw_invert / tmhip_sw_invert_nd (six_invert's error count; the reference prints it) */
+int tmhip_sw_invert_failures(tmhip_ctx *ctx, int *fails);
+/* assign_mul_one_sw_pm_imu_eps(ieo,k_s,k_c,l_s,l_c,mu,eps)   clovertm_operators.c:960-1074; k may be l */
+int tmhip_assign_mul_one_sw_pm_imu_eps(tmhip_ctx *ctx, int ieo, tmhip_field *k_s, tmhip_field *k_c, tmhip_field *l_s, tmhip_field *l_c, double mu,
+                                       double eps);
+/* clover_inv_nd(ieo,l_c,l_s)   :352-425, in place, ieo = EE only (sw_invert_nd inverts the even sites) */
+int tmhip_clover_inv_nd(tmhip_ctx *ctx, int ieo, tmhip_field *l_c, tmhip_field *l_s);
+/* clover_gamma5_nd(ieo,l_c,l_s,k_c,k_s,j_c,j_s,mubar,epsbar)   :733-850; l may be k or j */
+int tmhip_clover_gamma5_nd(tmhip_ctx *ctx, int ieo, tmhip_field *l_c, tmhip_field *l_s, tmhip_field *k_c, tmhip_field *k_s, tmhip_field *j_c,
+                           tmhip_field *j_s, double mubar, double epsbar);
+int tmhip_Qsw_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);          /* tm_operators_nd.c:91-111 */
+int tmhip_Qsw_dagger_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);   /* :154-174 */
+int tmhip_Qsw_pm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);       /* :240-285; l may be k */
+/* Qsw_tau1_sub_const_ndpsi(l_s,l_c,k_s,k_c,z,Cpol,invev)   :378-444, statement by statement (the swapped output order of :393-395 included); l != k */
+int tmhip_Qsw_tau1_sub_const_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, double z_re, double z_im,
+                                   double Cpol, double invev);
+int tmhip_H_eo_sw_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);      /* :521-535; l may be k */
+int tmhip_Msw_ee_inv_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);   /* :539-549; l may be k */
+/* The doublet solvers on either operator: op = TMHIP_ND_OP_QTM_PM (the un-suffixed calls above, bit for bit) or TMHIP_ND_OP_QSW_PM
+ * (f / M_ndpsi = Qsw_pm_ndpsi).  One engine, one state, one polling loop. */
+enum { TMHIP_ND_OP_QTM_PM = 0, TMHIP_ND_OP_QSW_PM = 1 };
+int tmhip_cg_her_nd_op(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_field *Q_up, tmhip_field *Q_dn, int max_iter, double eps_sq,
+                       int rel_prec, int N, int op, int *iters);
+int tmhip_cg_mms_tm_nd_op(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmhip_field *Qup, tmhip_field *Qdn, const double *shifts,
+                          int nshifts, int max_iter, double eps_sq, int rel_prec, int op, int *iters);
+/* sw_deriv_nd(ieo)   operator/clover_deriv.c:156-243: swp += (1+T) sw_inv_nd summed over the chiralities, swm += their difference */
+int tmhip_sw_deriv_nd(tmhip_ctx *ctx, int ieo);
+/* The monomial of type NDCLOVERRAT (monomial/ndrat_monomial.c): the bodies of tmhip_ndrat_* with Qsw_pm_ndpsi, Qsw_tau1_sub_const_ndpsi and
+ * H_eo_sw_ndpsi, plus the clover part of the force: tmhip_swpm_zero, four sw_spinor_eo per shift (:164-175), sw_deriv_nd(EE) when trlog
+ * is set (:179-181), tmhip_sw_all(kappa, c_sw) (:182-184).  The arguments are those of tmhip_ndrat_*.  The clover term must come from
+ * tmhip_sw_term, which keeps the links sw_all walks; after tmhip_set_clover the four calls refuse before any launch. */
+int tmhip_ndcloverrat_force(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                            double kappa, double c_sw, int trlog);
+int tmhip_ndcloverrat_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                                 double kappa, double c_sw, int trlog, int max_iter, double eps_sq, int rel_prec, int *iters);
+int tmhip_ndcloverrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *nu, const double *rnu, int np, double invmaxev,
+                               int max_iter, double eps_sq, int rel_prec, double *energy0, int *iters);
+int tmhip_ndcloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, int max_iter,
+                          double eps_sq, int rel_prec, double *energy1, int *iters);
+
 /* ---- single-flavour multi-shift CG (solver/cg_mms_tm.c:65-197) ------------------------------------------------------------
  * cg_mms_tm(P,Q,solver_params,&reached_prec) with M_psi = Qtm_pm_psi / Qsw_pm_psi on N = VOLUME/2 sites (op TMHIP_OP_QTM_PM /
  * TMHIP_OP_QSW_PM, EO fields) or Q_pm_psi on N = VOLUME sites (op TMHIP_OP_Q_PM_FULL, FULL fields; g_mu as set by tmhip_set_mu).

@@ -243,6 +243,52 @@ __global__ __launch_bounds__(64) void sw_invert_kernel(const v2d *__restrict__ s
     }
 }
 
+// clover_invert.c:440-495 sw_invert_nd: thread = (even site i, chirality block b); ((1+T)^2 + mshift)^-1, all four 3x3 blocks stored.
+// The square is built a column of 1+T at a time (b[r][c] += a[r][k] a[k][c], k in the order of mult_6x6; 1+T is hermitian, so row k is
+// the conjugate of column k): only the 36 entries that are inverted in place live in registers.
+__global__ __launch_bounds__(64) void sw_invert_nd_kernel(const v2d *__restrict__ swp, v2d *__restrict__ swi, int gs, int Vh, double mshift, int *fails) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= Vh) return;
+  const int b = blockIdx.y;
+  v2d a[6][6];
+#pragma unroll
+  for (int r = 0; r < 6; r++)
+#pragma unroll
+    for (int c = 0; c < 6; c++) a[r][c] = v2d{0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    v2d col[6];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      if (k < 3) {
+        col[r] = swp[((size_t)(0 + b) * 9 + 3 * r + k) * gs + i];
+        col[r + 3] = m3_conj(swp[((size_t)(2 + b) * 9 + 3 * k + r) * gs + i]);
+      } else {
+        col[r] = swp[((size_t)(2 + b) * 9 + 3 * r + (k - 3)) * gs + i];
+        col[r + 3] = swp[((size_t)(4 + b) * 9 + 3 * r + (k - 3)) * gs + i];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+      for (int c = 0; c < 6; c++) a[r][c] += m3_cmul(col[r], m3_conj(col[c]));
+  }
+#pragma unroll
+  for (int r = 0; r < 6; r++) a[r][r].x += mshift;   // add_shift_6x6: a real shift
+  const int f = six_invert_dev(a);
+  if (f) atomicAdd(fails, f);
+  v2d *o = swi + i;
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      o[((size_t)(0 + b) * 9 + 3 * r + c) * gs] = a[r][c];
+      o[((size_t)(2 + b) * 9 + 3 * r + c) * gs] = a[r][c + 3];
+      o[((size_t)(4 + b) * 9 + 3 * r + c) * gs] = a[r + 3][c + 3];
+      o[((size_t)(6 + b) * 9 + 3 * r + c) * gs] = a[r + 3][c];
+    }
+}
+
 // inverse of sw_sort_kernel / swinv_sort_kernel: device layout -> the reference's host layout
 __global__ __launch_bounds__(256) void sw_unsort_kernel(v2d *__restrict__ raw, const v2d *__restrict__ d, int gs, int Vh, int LX, int LY, int LZ,
                                                         int toff) {
@@ -320,6 +366,39 @@ __global__ __launch_bounds__(256) void sw_deriv_kernel(v2d *__restrict__ swpm, c
     const v2d m0 = *pm, p0 = *pp;
     *pm = v2d{m0.x + fac * lm.x, m0.y + fac * lm.y};
     *pp = v2d{p0.x + fac * lp.x, p0.y + fac * lp.y};
+  }
+}
+
+// operator/clover_deriv.c:156-243 sw_deriv_nd: thread = (site of parity ieo, n); block n of a_b = (1+T)_b sw_inv_nd_b for both
+// chiralities b, then swp += a_1 + a_0, swm += a_1 - a_0 (fac = 1).  n = 0: (0,0), 1: (0,3), 2: (3,3), 3: (3,0).
+__device__ __forceinline__ M3 m3_plane(const v2d *__restrict__ w, size_t gs, int blk) {
+  M3 r;
+#pragma unroll
+  for (int e = 0; e < 9; e++) r.e[e] = w[((size_t)blk * 9 + e) * gs];
+  return r;
+}
+__global__ __launch_bounds__(256, 2) void sw_deriv_nd_kernel(v2d *__restrict__ swpm, const v2d *__restrict__ swp, const v2d *__restrict__ swi, int gs, int Vh,
+                                                          int V, int ieo) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Vh) return;
+  const int n = blockIdx.y;
+  const int R = n >= 2 ? 1 : 0, Cc = (n == 1 || n == 2) ? 1 : 0;   // block row / column of the 6x6 product
+  const size_t s = (size_t)ieo * Vh + i;
+#pragma unroll 1
+  for (int b = 0; b < 2; b++) {   // one chirality at a time (four 3x3 blocks live): swp += a_b, swm -= a_0, += a_1
+    // row R of 1+T: (S_R0, S_R1) = (sw[0], sw[1]) or (sw[1]^dagger, sw[2]); column Cc of the inverse: (W_0C, W_1C) = (inv[0], inv[3]) or (inv[1], inv[2])
+    const M3 w0 = m3_plane(swi + i, gs, (Cc ? 2 : 0) + b), w1 = m3_plane(swi + i, gs, (Cc ? 4 : 6) + b);
+    const M3 s1 = m3_plane(swp + i, gs, (R ? 4 : 2) + b);
+    const M3 s0 = m3_plane(swp + i, gs, (R ? 2 : 0) + b);
+    M3 a = R ? m3_mul<true, false>(s0, w0) : m3_mul<false, false>(s0, w0);
+    m3_acc(a, m3_mul<false, false>(s1, w1));
+    const double sg = b ? 1.0 : -1.0;
+#pragma unroll
+    for (int e = 0; e < 9; e++) {
+      v2d *pm = swpm + ((size_t)(0 * 4 + n) * 9 + e) * V + s, *pp = swpm + ((size_t)(1 * 4 + n) * 9 + e) * V + s;
+      *pm += sg * a.e[e];
+      *pp += a.e[e];
+    }
   }
 }
 
@@ -808,6 +887,7 @@ int tmhip_set_clover(tmhip_ctx *ctx, const void *sw_host, const void *sw_inv_hos
   ctx->sw_set = true;
   ctx->sw_inv_sets = 2;
   ctx->clover32_set = false;
+  ctx->clover_nd_set = false;
   return 0;
 }
 
@@ -874,6 +954,7 @@ int tmhip_sw_term(tmhip_ctx *ctx, const void *gauge_host, double kappa, double c
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   ctx->sw_set = true;
   ctx->clover_set = false;     // sw_inv no longer matches
+  ctx->clover_nd_set = false;
   ctx->clover32_set = false;
   return 0;
 }
@@ -897,6 +978,51 @@ int tmhip_sw_invert(tmhip_ctx *ctx, int ieo, double mu) {
   ctx->sw_inv_sets = nsets;
   ctx->clover_set = true;
   ctx->clover32_set = false;
+  return 0;
+}
+
+/* operator/clover_invert.c:440 sw_invert_nd(mshift): ((1+T)^2 + mshift)^-1 on the even sites, both chiralities.  Deviation from the
+ * reference, which overwrites sw_inv: the result has an array of its own (sw_inv_nd, all four 3x3 blocks: 8 x 9 x 16 = 1152 bytes per
+ * even site), so that cloverdet and ndcloverrat alternate inside one MD step without inverting again. */
+int tmhip_sw_invert_nd(tmhip_ctx *ctx, double mshift) {
+  if (!ctx->sw_set) TMHIP_FAIL("tmhip_sw_invert_nd called before tmhip_sw_term / tmhip_set_clover");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (clover_alloc(ctx)) return 1;
+  if (!ctx->sw_inv_nd) TMHIP_CHECK(hipMalloc((void **)&ctx->sw_inv_nd, (size_t)72 * ctx->gs * sizeof(v2d)));
+  TMHIP_CHECK(hipMemsetAsync(ctx->sw_fail, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(sw_invert_nd_kernel, dim3((ctx->Vh + 63) / 64, 2), dim3(64), 0, ctx->stream, swpar(ctx, 0), ctx->sw_inv_nd, ctx->gs, ctx->Vh, mshift,
+                     ctx->sw_fail);
+  TMHIP_CHECK(hipGetLastError());
+  int fails = 0;
+  TMHIP_CHECK(hipMemcpyAsync(&fails, ctx->sw_fail, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (fails > 0 && ctx->g.proc_t == 0) printf("# inversion failed in six_invert_nd code %d\n", fails);   /* clover_invert.c:475-478 */
+  ctx->clover_nd_set = true;
+  return 0;
+}
+
+/* near-singular pivots met by the last tmhip_sw_invert / tmhip_sw_invert_nd (the reference only prints them) */
+int tmhip_sw_invert_failures(tmhip_ctx *ctx, int *fails) {
+  if (!fails || !ctx->sw_fail) TMHIP_FAIL("tmhip_sw_invert_failures: no inversion has run");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  TMHIP_CHECK(hipMemcpyAsync(fails, ctx->sw_fail, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+/* sw_inv_nd in the reference's host layout sw_inv[icx][0..3][i], icx < VOLUME/2: su3 [VOLUME/2][4][2] */
+int tmhip_get_clover_nd(tmhip_ctx *ctx, void *sw_inv_host) {
+  if (!sw_inv_host) TMHIP_FAIL("tmhip_get_clover_nd: null argument");
+  if (!ctx->clover_nd_set) TMHIP_FAIL("tmhip_get_clover_nd: no inverse of the doublet's clover term on the device (tmhip_sw_invert_nd)");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)ctx->Vh * 72 * sizeof(v2d);
+  void *raw = nullptr;
+  TMHIP_CHECK(hipMalloc(&raw, bytes));
+  hipLaunchKernelGGL(swinv_unsort_kernel, dim3((ctx->Vh + 255) / 256, 1), dim3(256), 0, ctx->stream, (v2d *)raw, (const v2d *)ctx->sw_inv_nd, ctx->gs, ctx->Vh);
+  TMHIP_CHECK(hipGetLastError());
+  TMHIP_CHECK(hipMemcpyAsync(sw_inv_host, raw, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  TMHIP_CHECK(hipFree(raw));
   return 0;
 }
 
@@ -962,6 +1088,17 @@ int tmhip_sw_deriv(tmhip_ctx *ctx, int ieo, double mu) {
   if (swpm_alloc(ctx)) return 1;
   hipLaunchKernelGGL(sw_deriv_kernel, dim3((ctx->Vh + 255) / 256, 4), dim3(256), 0, ctx->stream, ctx->swpm, (const v2d *)ctx->sw_inv, ctx->gs, ctx->Vh,
                      ctx->V, ieo ? 1 : 0, nsets, nsets == 2 ? 0.5 : 1.0);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+/* operator/clover_deriv.c:156 sw_deriv_nd(ieo): needs tmhip_sw_invert_nd on the current clover term; like the reference's, the
+ * inverse belongs to the even sites (ieo = EE is the only call, ndrat_monomial.c:180) */
+int tmhip_sw_deriv_nd(tmhip_ctx *ctx, int ieo) {
+  if (!ctx->sw_set || !ctx->clover_nd_set) TMHIP_FAIL("sw_deriv_nd called before tmhip_sw_term + tmhip_sw_invert_nd");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (swpm_alloc(ctx)) return 1;
+  hipLaunchKernelGGL(sw_deriv_nd_kernel, dim3((ctx->Vh + 255) / 256, 4), dim3(256), 0, ctx->stream, ctx->swpm, swpar(ctx, ieo), (const v2d *)ctx->sw_inv_nd,
+                     ctx->gs, ctx->Vh, ctx->V, ieo ? 1 : 0);
   TMHIP_CHECK(hipGetLastError());
   return 0;
 }

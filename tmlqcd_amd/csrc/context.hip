@@ -227,6 +227,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   if (ctx->gauge32) (void)hipFree(ctx->gauge32);
   if (ctx->sw) (void)hipFree(ctx->sw);
   if (ctx->sw_inv) (void)hipFree(ctx->sw_inv);
+  if (ctx->sw_inv_nd) (void)hipFree(ctx->sw_inv_nd);
   if (ctx->sw32) (void)hipFree(ctx->sw32);
   if (ctx->sw_inv32) (void)hipFree(ctx->sw_inv32);
   if (ctx->sw_fail) (void)hipFree(ctx->sw_fail);

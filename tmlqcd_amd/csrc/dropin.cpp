@@ -98,6 +98,7 @@ bool g_gauge_uploaded = false;   // the current context holds a gauge copy
 bool g_dev_links_newer = false;   // resident mode: the device links are ahead of g_gauge_field until tmlqcd_hip_sync_gauge_to_host
 bool g_momenta_resident = false;  // the momenta live on the device (tmlqcd_hip_update_momenta), not re-uploaded by tmlqcd_hip_update_gauge
 bool g_clover_uploaded = false;
+bool g_sw_on_device = false;   // the device's 1+T belongs to the current links (tmlqcd_hip_sw_term, or the host's sw uploaded)
 tmhip_field *g_full_tmp = nullptr; // FULL-lattice scratch of Q_pm_psi / D_dagg_psi (tm_operators.c:380-397)
 tmhip_field *g_f32[3] = {nullptr, nullptr, nullptr};   // device fields of the fp32 host-pointer symbols (Hopping_Matrix_32 ...)
 
@@ -792,6 +793,7 @@ void tmlqcd_hip_finalize(void) {
   g_ctx = nullptr;
   g_gauge_uploaded = false;
   g_clover_uploaded = false;
+  g_sw_on_device = false;
   g_dev_links_newer = g_momenta_resident = false;
 }
 
@@ -983,6 +985,7 @@ static void ensure_clover(tmhip_ctx *c) {
     if (!&sw || !&sw_inv || !sw || !sw_inv) die("clover operator called but the host program has no sw / sw_inv (init_sw_fields)");
     CK(tmhip_set_clover(c, &sw[0][0][0], &sw_inv[0][0][0]));
     g_clover_uploaded = true;
+    g_sw_on_device = true;
   }
 }
 static tmhip_ctx *refresh_clover() {
@@ -990,7 +993,7 @@ static tmhip_ctx *refresh_clover() {
   ensure_clover(c);
   return c;
 }
-void tmlqcd_hip_update_clover(void) { g_clover_uploaded = false; }
+void tmlqcd_hip_update_clover(void) { g_clover_uploaded = false; g_sw_on_device = false; }
 void tmlqcd_hip_set_max_mirrors(int n) { if (n >= 8) g_mirror_cap = (size_t)n; }
 unsigned long tmlqcd_hip_calls(void) { return g_calls; }
 /* sw_term(g_gauge_field, kappa, c_sw) (operator/clover_term.c:88) computed in HBM; the host's sw array, if the program
@@ -1000,6 +1003,7 @@ void tmlqcd_hip_sw_term(const double kappa, const double c_sw) {
   CK(tmhip_sw_term(c, &g_gauge_field[0][0], kappa, c_sw));
   if (&sw && sw) CK(tmhip_get_clover(c, &sw[0][0][0], nullptr));
   g_clover_uploaded = false;
+  g_sw_on_device = true;
 }
 /* sw_invert(ieo, mu) (operator/clover_invert.c:170) from the device-resident clover term */
 void tmlqcd_hip_sw_invert(const int ieo, const double mu) {
@@ -1054,6 +1058,72 @@ void clover_inv(spinor *const l, const int tau3sign, const double mu) {
   tmhip_field *fl = in(c, l, TMHIP_FIELD_EO);
   CK(tmhip_clover_inv(c, fl, tau3sign, mu));
   done(c, l);
+}
+// ------------------------------------------------------------------ clover doublet (Qsw_*_ndpsi, tm_operators_nd.c; clovertm_operators.c)
+// The core refuses, with a message, when the device's 1+T or sw_inv_nd do not belong to the current links: run tmlqcd_hip_sw_term (or
+// the host's sw_term + tmlqcd_hip_update_clover) and sw_invert_nd first, as ndrat_monomial.c:89-91 does.
+/* operator/clover_invert.c:440 sw_invert_nd(mshift) from the device's clover term (the host's sw goes up first when the device has none
+ * for these links); the host's sw_inv, when the program has one, receives the result in its first VOLUME/2 entries as in the reference.
+ * On the device it lives beside sw_inv, not in it. */
+void sw_invert_nd(const double mshift) {
+  tmhip_ctx *c = refresh(false);
+  if (!g_sw_on_device) { g_clover_uploaded = false; ensure_clover(c); }
+  CK(tmhip_sw_invert_nd(c, mshift));
+  if (&sw_inv && sw_inv) CK(tmhip_get_clover_nd(c, &sw_inv[0][0][0]));
+}
+/* near-singular pivots met by the last sw_invert_nd / tmlqcd_hip_sw_invert (what the reference prints as "inversion failed in six_invert") */
+int tmlqcd_hip_sw_invert_failures(void) {
+  int n = 0;
+  CK(tmhip_sw_invert_failures(ctx(), &n));
+  return n;
+}
+/* operator/clover_deriv.c:156 sw_deriv_nd(ieo) into the device-resident swm / swp (tmlqcd_hip_swpm_zero / tmlqcd_hip_sw_all) */
+void sw_deriv_nd(const int ieo) { CK(tmhip_sw_deriv_nd(refresh(false), ieo)); }
+#define NDSW_OP(NAME, CORE)                                                                                         \
+  void NAME(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c) {                           \
+    tmhip_ctx *c = refresh_nd(#NAME);                                                                               \
+    tmhip_field *fks = in(c, k_s, TMHIP_FIELD_EO), *fkc = in(c, k_c, TMHIP_FIELD_EO);                               \
+    tmhip_field *fls = out(c, l_s, TMHIP_FIELD_EO), *flc = out(c, l_c, TMHIP_FIELD_EO);                             \
+    CK(CORE(c, fls, flc, fks, fkc));                                                                                \
+    done(c, l_s); done(c, l_c);                                                                                     \
+  }
+NDSW_OP(Qsw_ndpsi, tmhip_Qsw_ndpsi)                /* tm_operators_nd.c:91-111 */
+NDSW_OP(Qsw_dagger_ndpsi, tmhip_Qsw_dagger_ndpsi)  /* :154-174 */
+NDSW_OP(Qsw_pm_ndpsi, tmhip_Qsw_pm_ndpsi)          /* :240-285 */
+NDSW_OP(H_eo_sw_ndpsi, tmhip_H_eo_sw_ndpsi)        /* :521-535 */
+NDSW_OP(Msw_ee_inv_ndpsi, tmhip_Msw_ee_inv_ndpsi)  /* :539-549 */
+void Qsw_tau1_sub_const_ndpsi(spinor *const l_s, spinor *const l_c, spinor *const k_s, spinor *const k_c, const _Complex double z, const double Cpol,
+                              const double invev) {   /* :378-444 */
+  tmhip_ctx *c = refresh_nd("Qsw_tau1_sub_const_ndpsi");
+  tmhip_field *fks = in(c, k_s, TMHIP_FIELD_EO), *fkc = in(c, k_c, TMHIP_FIELD_EO);
+  tmhip_field *fls = out(c, l_s, TMHIP_FIELD_EO), *flc = out(c, l_c, TMHIP_FIELD_EO);
+  CK(tmhip_Qsw_tau1_sub_const_ndpsi(c, fls, flc, fks, fkc, __real__ z, __imag__ z, Cpol, invev));
+  done(c, l_s); done(c, l_c);
+}
+/* clovertm_operators.c:960-1074 */
+void assign_mul_one_sw_pm_imu_eps(const int ieo, spinor *const k_s, spinor *const k_c, const spinor *const l_s, const spinor *const l_c,
+                                  const double mu, const double eps) {
+  tmhip_ctx *c = refresh_nd("assign_mul_one_sw_pm_imu_eps");
+  tmhip_field *fls = in(c, l_s, TMHIP_FIELD_EO), *flc = in(c, l_c, TMHIP_FIELD_EO);
+  tmhip_field *fks = out(c, k_s, TMHIP_FIELD_EO), *fkc = out(c, k_c, TMHIP_FIELD_EO);
+  CK(tmhip_assign_mul_one_sw_pm_imu_eps(c, ieo, fks, fkc, fls, flc, mu, eps));
+  done(c, k_s); done(c, k_c);
+}
+/* clovertm_operators.c:352-425, in place */
+void clover_inv_nd(const int ieo, spinor *const l_c, spinor *const l_s) {
+  tmhip_ctx *c = refresh_nd("clover_inv_nd");
+  tmhip_field *flc = in(c, l_c, TMHIP_FIELD_EO), *fls = in(c, l_s, TMHIP_FIELD_EO);
+  CK(tmhip_clover_inv_nd(c, ieo, flc, fls));
+  done(c, l_c); done(c, l_s);
+}
+/* clovertm_operators.c:733-850 */
+void clover_gamma5_nd(const int ieo, spinor *const l_c, spinor *const l_s, const spinor *const k_c, const spinor *const k_s,
+                      const spinor *const j_c, const spinor *const j_s, const double mubar, const double epsbar) {
+  tmhip_ctx *c = refresh_nd("clover_gamma5_nd");
+  tmhip_field *fkc = in(c, k_c, TMHIP_FIELD_EO), *fks = in(c, k_s, TMHIP_FIELD_EO), *fjc = in(c, j_c, TMHIP_FIELD_EO), *fjs = in(c, j_s, TMHIP_FIELD_EO);
+  tmhip_field *flc = out(c, l_c, TMHIP_FIELD_EO), *fls = out(c, l_s, TMHIP_FIELD_EO);
+  CK(tmhip_clover_gamma5_nd(c, ieo, flc, fls, fkc, fks, fjc, fjs, mubar, epsbar));
+  done(c, l_c); done(c, l_s);
 }
 /* clovertm_operators.c:448-520 */
 void clover_gamma5(const int ieo, spinor *const l, const spinor *const k, const spinor *const j, const double mu) {
@@ -1573,21 +1643,22 @@ int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, 
 /* solver/mixed_cg_her.c:65-202 with f = Qtm_pm_psi: fp32 inner CG + fp64 defect correction, all in HBM */
 static_assert(sizeof(tmlqcd_solver_params) == 144 && offsetof(tmlqcd_solver_params, mcg_delta) == 52,
               "solver_params_t layout (solver/solver_params.h:46-109)");
-/* solver/cg_her_nd.c:57-160 with f = Qtm_pm_ndpsi, device-resident */
+/* solver/cg_her_nd.c:57-160 with f = Qtm_pm_ndpsi or Qsw_pm_ndpsi, device-resident */
 int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *const Q_dn, const int max_iter, double eps_sq,
               const int rel_prec, const int N, matrix_mult_nd f) {
-  if (f != &Qtm_pm_ndpsi || N != VOLUME / 2) die("cg_her_nd: only f = Qtm_pm_ndpsi on VOLUME/2 sites runs on the device");
+  if ((f != &Qtm_pm_ndpsi && f != &Qsw_pm_ndpsi) || N != VOLUME / 2) die("cg_her_nd: only f = Qtm_pm_ndpsi / Qsw_pm_ndpsi on VOLUME/2 sites runs on the device");
   tmhip_ctx *c = refresh_nd("cg_her_nd");
   tmhip_field *fqu = in(c, Q_up, TMHIP_FIELD_EO), *fqd = in(c, Q_dn, TMHIP_FIELD_EO);
   tmhip_field *fpu = in(c, P_up, TMHIP_FIELD_EO), *fpd = in(c, P_dn, TMHIP_FIELD_EO);
   int iters = -1;
-  CK(tmhip_cg_her_nd(c, fpu, fpd, fqu, fqd, max_iter, eps_sq, rel_prec, N, &iters));
+  CK(tmhip_cg_her_nd_op(c, fpu, fpd, fqu, fqd, max_iter, eps_sq, rel_prec, N, f == &Qsw_pm_ndpsi ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, &iters));
   done(c, P_up); done(c, P_dn);
   return iters;
 }
-/* solver/cg_mms_tm_nd.c:64-215 with M_ndpsi = Qtm_pm_ndpsi, device-resident */
+/* solver/cg_mms_tm_nd.c:64-215 with M_ndpsi = Qtm_pm_ndpsi or Qsw_pm_ndpsi, device-resident */
 int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *sp) {
-  if (sp->M_ndpsi != &Qtm_pm_ndpsi || sp->sdim != VOLUME / 2) die("cg_mms_tm_nd: only M_ndpsi = Qtm_pm_ndpsi on VOLUME/2 sites runs on the device");
+  if ((sp->M_ndpsi != &Qtm_pm_ndpsi && sp->M_ndpsi != &Qsw_pm_ndpsi) || sp->sdim != VOLUME / 2)
+    die("cg_mms_tm_nd: only M_ndpsi = Qtm_pm_ndpsi / Qsw_pm_ndpsi on VOLUME/2 sites runs on the device");
   const int n = sp->no_shifts;
   if (n < 1 || n > 32) die("cg_mms_tm_nd: no_shifts must be in [1, 32]");
   tmhip_ctx *c = refresh_nd("cg_mms_tm_nd");
@@ -1595,7 +1666,8 @@ int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spin
   tmhip_field *fu[32], *fd[32];
   for (int s = 0; s < n; s++) { fu[s] = out(c, Pup[s], TMHIP_FIELD_EO); fd[s] = out(c, Pdn[s], TMHIP_FIELD_EO); }
   int iters = -1;
-  CK(tmhip_cg_mms_tm_nd(c, fu, fd, fqu, fqd, sp->shifts, n, sp->max_iter, sp->squared_solver_prec, sp->rel_prec, &iters));
+  CK(tmhip_cg_mms_tm_nd_op(c, fu, fd, fqu, fqd, sp->shifts, n, sp->max_iter, sp->squared_solver_prec, sp->rel_prec,
+                           sp->M_ndpsi == &Qsw_pm_ndpsi ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, &iters));
   for (int s = 0; s < n; s++) { done(c, Pup[s]); done(c, Pdn[s]); }
   return iters;
 }
@@ -1842,6 +1914,36 @@ int tmlqcd_hip_ndrat_acc(spinor *const pf, spinor *const pf2, const double *mu, 
   CK(tmhip_ndrat_acc(c, fu, fd, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, &iters));
   return iters;
 }
+/* ndrat_monomial.c:80-184 for type NDCLOVERRAT, after the caller's sw_term + sw_invert_nd (:89-91): swm / swp are zeroed, filled and folded
+ * into the derivative on the device (trlog: the monomial's flag, :179-181) */
+int tmlqcd_hip_ndcloverrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np,
+                                      const double EVMaxInv, const double kappa, const double c_sw, const int trlog, const int max_iter,
+                                      const double eps_sq, const int rel_prec) {
+  tmhip_ctx *c = refresh_nd("tmlqcd_hip_ndcloverrat_derivative");
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  if (!g_deriv_pending) CK(tmhip_derivative_zero(c));
+  int iters = -1;
+  CK(tmhip_ndcloverrat_derivative(c, fu, fd, mu, rmu, np, EVMaxInv, kappa, c_sw, trlog, max_iter, eps_sq, rel_prec, &iters));
+  rat_force_done(hf);
+  return iters;
+}
+int tmlqcd_hip_ndcloverrat_heatbath(spinor *const pf, spinor *const pf2, const double *nu, const double *rnu, const int np, const double EVMaxInv,
+                                    const int max_iter, const double eps_sq, const int rel_prec, double *energy0) {
+  tmhip_ctx *c = refresh_nd("tmlqcd_hip_ndcloverrat_heatbath");
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_ndcloverrat_heatbath(c, fu, fd, nu, rnu, np, EVMaxInv, max_iter, eps_sq, rel_prec, energy0, &iters));
+  done(c, pf); done(c, pf2);
+  return iters;
+}
+int tmlqcd_hip_ndcloverrat_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np, const int max_iter,
+                               const double eps_sq, const int rel_prec, double *energy1) {
+  tmhip_ctx *c = refresh_nd("tmlqcd_hip_ndcloverrat_acc");
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_ndcloverrat_acc(c, fu, fd, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, &iters));
+  return iters;
+}
 /* rat_monomial.c:83-132 (type RAT) */
 int tmlqcd_hip_rat_derivative(hamiltonian_field_t *const hf, spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter,
                               const double eps_sq, const int rel_prec) {
@@ -1897,6 +1999,7 @@ void tmlqcd_hip_update_gauge(const double step, hamiltonian_field_t *const hf) {
   if (!g_momenta_resident) CK(tmhip_momenta_upload(c, &hf->momenta[0][0]));
   CK(tmhip_update_gauge(c, step));
   g_clover_uploaded = false;
+  g_sw_on_device = false;
   if (g_mode != TMLQCD_HIP_RESIDENT) {
     CK(tmhip_gauge_download(c, &hf->gaugefield[0][0]));
     links_in_step(hf->gaugefield, hf);
@@ -1947,7 +2050,7 @@ int read_gauge_field(char *filename, su3 **const gf) {
   if (info.xlf_info[0]) { free(GaugeInfo.xlfInfo); GaugeInfo.xlfInfo = strdup(info.xlf_info); }
   if (info.ildg_data_lfn[0]) { free(GaugeInfo.ildg_data_lfn); GaugeInfo.ildg_data_lfn = strdup(info.ildg_data_lfn); }
   g_update_gauge_copy = 1;                                          /* gauge_read.c:190 */
-  g_clover_uploaded = false;
+  g_clover_uploaded = false; g_sw_on_device = false;
   // (the flag stays raised exactly as the reference leaves it: the host program still has its xchange_gauge to do, and the next
   // operator call uploads g_gauge_field once more -- 11 ms per configuration read at 32^4 -- rather than guess that nothing changed)
   if (gf == g_gauge_field && info.gauge_read) g_dev_links_newer = false;
@@ -1960,7 +2063,7 @@ int write_gauge_field(char *filename, const int prec, paramsXlfInfo const *xlfIn
   if (g_nproc_t > 1) die("write_gauge_field: single-rank writer (T-split ranks: tmhip_gauge_pack_ildg for their part of the record)");
   tmhip_ctx *c = ctx();
   g_calls++;
-  if (!g_dev_links_newer) { CK(tmhip_set_gauge(c, &g_gauge_field[0][0])); g_gauge_uploaded = true; g_clover_uploaded = false; }
+  if (!g_dev_links_newer) { CK(tmhip_set_gauge(c, &g_gauge_field[0][0])); g_gauge_uploaded = true; g_clover_uploaded = false; g_sw_on_device = false; }
   char msg[1024];
   msg[0] = 0;
   if (xlfInfo) {                                                    /* io/utils_write_xlf.c:35-55: plain text, what write_gauge_field (io/gauge_write.c:35) writes */

@@ -179,7 +179,9 @@ struct RatMuZero {
   ~RatMuZero() { ctx->mu = mu; }
 };
 
-static int ndrat_force_body(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev) {
+// sw: type NDCLOVERRAT -- the clover operators, and the four sw_spinor_eo of ndrat_monomial.c:164-175 per shift
+static int ndrat_force_body(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                            bool sw = false) {
   TmhipRat *r = (TmhipRat *)ctx->rat;
   const int G = rat_group(ctx);
   if (rat_need(ctx, r->w, 6 * (G < np ? G : np))) return 1;
@@ -191,16 +193,45 @@ static int ndrat_force_body(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **
       const int j = hi - q;
       tmhip_field **w = r->w + 6 * q;
       // Y_j,o = (Q_h tau^1 + i mu_j) X_j,o (:130-132), X_j,e (:136-137), Y_j,e (:152-153)
-      if (tmhip_Q_tau1_sub_const_ndpsi(ctx, w[0], w[1], chi_up[j], chi_dn[j], 0.0, -mu[j], 1.0, invmaxev)) return 1;
-      if (tmhip_H_eo_tm_ndpsi(ctx, w[2], w[3], chi_up[j], chi_dn[j], TMHIP_EO)) return 1;
-      if (tmhip_H_eo_tm_ndpsi(ctx, w[4], w[5], w[0], w[1], TMHIP_EO)) return 1;
+      if (sw) {   // :118-125, :147-148
+        if (tmhip_Qsw_tau1_sub_const_ndpsi(ctx, w[0], w[1], chi_up[j], chi_dn[j], 0.0, -mu[j], 1.0, invmaxev)) return 1;
+        if (tmhip_H_eo_sw_ndpsi(ctx, w[2], w[3], chi_up[j], chi_dn[j])) return 1;
+        if (tmhip_H_eo_sw_ndpsi(ctx, w[4], w[5], w[0], w[1])) return 1;
+      } else {
+        if (tmhip_Q_tau1_sub_const_ndpsi(ctx, w[0], w[1], chi_up[j], chi_dn[j], 0.0, -mu[j], 1.0, invmaxev)) return 1;
+        if (tmhip_H_eo_tm_ndpsi(ctx, w[2], w[3], chi_up[j], chi_dn[j], TMHIP_EO)) return 1;
+        if (tmhip_H_eo_tm_ndpsi(ctx, w[4], w[5], w[0], w[1], TMHIP_EO)) return 1;
+      }
       f[2 * q] = f[2 * q + 1] = rmu[j] * invmaxev;                                      // forcefactor = EVMaxInv (:94)
       l0[2 * q] = w[2]; k0[2 * q] = w[0]; l0[2 * q + 1] = w[3]; k0[2 * q + 1] = w[1];   // deriv_Sb(EO, ..) (:140-143)
       l1[2 * q] = chi_up[j]; k1[2 * q] = w[4]; l1[2 * q + 1] = chi_dn[j]; k1[2 * q + 1] = w[5];   // deriv_Sb(OE, ..) (:157-160)
     }
     if (tmhip_deriv_Sb_batch(ctx, TMHIP_EO, 2 * g, l0, k0, f) || tmhip_deriv_Sb_batch(ctx, TMHIP_OE, 2 * g, l1, k1, f)) return 1;
+    for (int q = 0; sw && q < g; q++) {   // :164-175: EE (w5, w2), OO (chi_up, w1), EE (w4, w3), OO (chi_dn, w0)
+      const int j = hi - q;
+      tmhip_field **w = r->w + 6 * q;
+      if (tmhip_sw_spinor_eo(ctx, 0, w[5], w[2], f[2 * q]) || tmhip_sw_spinor_eo(ctx, 1, chi_up[j], w[1], f[2 * q])) return 1;
+      if (tmhip_sw_spinor_eo(ctx, 0, w[4], w[3], f[2 * q]) || tmhip_sw_spinor_eo(ctx, 1, chi_dn[j], w[0], f[2 * q])) return 1;
+    }
   }
   return 0;
+}
+
+// the clover monomial: refused before any launch unless the clover term and its doublet inverse are those of the current links
+static int ndcloverrat_prepare(tmhip_ctx *ctx, const char *who, int np) {
+  if (rat_prepare(ctx, who, np)) return 1;
+  if (!ctx->sw_set || !ctx->clover_nd_set) TMHIP_FAIL("%s: sw_inv_nd is not valid: call tmhip_sw_term and tmhip_sw_invert_nd on the current links", who);
+  // the force ends in sw_all on the links tmhip_sw_term kept: a clover term uploaded with tmhip_set_clover has none
+  if (!ctx->gauge_raw_valid) TMHIP_FAIL("%s: no lexicographic links on the device: the clover term must come from tmhip_sw_term, not tmhip_set_clover", who);
+  return 0;
+}
+// ndrat_monomial.c:80-86 before the loop, :179-184 after it
+static int ndcloverrat_force_all(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                                 double kappa, double c_sw, int trlog) {
+  if (tmhip_swpm_zero(ctx)) return 1;
+  if (ndrat_force_body(ctx, chi_up, chi_dn, mu, rmu, np, invmaxev, true)) return 1;
+  if (trlog && tmhip_sw_deriv_nd(ctx, 0)) return 1;
+  return tmhip_sw_all(ctx, nullptr, kappa, c_sw);
 }
 
 static int rat_force_body(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np) {
@@ -274,30 +305,31 @@ int tmhip_ndrat_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_d
   return ndrat_force_body(ctx, r->chi_up, r->chi_dn, mu, rmu, np, invmaxev);
 }
 
-int tmhip_ndrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *nu, const double *rnu, int np, double invmaxev,
-                         int max_iter, double eps_sq, int rel_prec, double *energy0, int *iters) {
-  if (rat_prepare(ctx, "ndrat_heatbath", np)) return 1;
+static int ndrat_heatbath_body(tmhip_ctx *ctx, bool sw, tmhip_field *pf_up, tmhip_field *pf_dn, const double *nu, const double *rnu, int np, double invmaxev,
+                               int max_iter, double eps_sq, int rel_prec, double *energy0, int *iters) {
+  if (sw ? ndcloverrat_prepare(ctx, "ndcloverrat_heatbath", np) : rat_prepare(ctx, "ndrat_heatbath", np)) return 1;
   if (!nu || !rnu || !iters || !energy0 || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndrat_heatbath: null argument or not an fp64 one-parity field");
   TmhipRat *r = (TmhipRat *)ctx->rat;
   if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np) || rat_need(ctx, r->w, 2)) return 1;
   double ea, eb;
   if (tmhip_square_norm(ctx, pf_up, ctx->Vh, 1, &ea) || tmhip_square_norm(ctx, pf_dn, ctx->Vh, 1, &eb)) return 1;   // :214,217
   *energy0 = ea + eb;
-  if (tmhip_cg_mms_tm_nd(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, nu, np, max_iter, eps_sq, rel_prec, iters)) return 1;   // :232
+  if (tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, nu, np, max_iter, eps_sq, rel_prec, sw ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, iters)) return 1;   // :232
   for (int j = np - 1; j >= 0; j--) {   // pf += i rnu_j (Q_h tau^1 - i nu_j) chi_j   (:239-254)
-    if (tmhip_Q_tau1_sub_const_ndpsi(ctx, r->w[0], r->w[1], r->chi_up[j], r->chi_dn[j], 0.0, nu[j], 1.0, invmaxev)) return 1;
+    if (sw ? tmhip_Qsw_tau1_sub_const_ndpsi(ctx, r->w[0], r->w[1], r->chi_up[j], r->chi_dn[j], 0.0, nu[j], 1.0, invmaxev)
+           : tmhip_Q_tau1_sub_const_ndpsi(ctx, r->w[0], r->w[1], r->chi_up[j], r->chi_dn[j], 0.0, nu[j], 1.0, invmaxev)) return 1;
     if (tmhip_assign_add_mul(ctx, pf_up, r->w[0], 0.0, rnu[j], ctx->Vh) || tmhip_assign_add_mul(ctx, pf_dn, r->w[1], 0.0, rnu[j], ctx->Vh)) return 1;
   }
   return 0;
 }
 
-int tmhip_ndrat_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, int max_iter,
-                    double eps_sq, int rel_prec, double *energy1, int *iters) {
-  if (rat_prepare(ctx, "ndrat_acc", np)) return 1;
+static int ndrat_acc_body(tmhip_ctx *ctx, bool sw, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, int max_iter,
+                          double eps_sq, int rel_prec, double *energy1, int *iters) {
+  if (sw ? ndcloverrat_prepare(ctx, "ndcloverrat_acc", np) : rat_prepare(ctx, "ndrat_acc", np)) return 1;
   if (!mu || !rmu || !iters || !energy1 || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndrat_acc: null argument or not an fp64 one-parity field");
   TmhipRat *r = (TmhipRat *)ctx->rat;
   if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np) || rat_need(ctx, r->w, 2)) return 1;
-  if (tmhip_cg_mms_tm_nd(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, iters)) return 1;   // :295
+  if (tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, sw ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, iters)) return 1;   // :295
   if (tmhip_assign(ctx, r->w[0], pf_up, ctx->Vh) || tmhip_assign(ctx, r->w[1], pf_dn, ctx->Vh)) return 1;                // :299-300
   for (int j = np - 1; j >= 0; j--)                                                                                        // :301-306
     if (tmhip_assign_add_mul_r(ctx, r->w[0], r->chi_up[j], rmu[j], ctx->Vh) || tmhip_assign_add_mul_r(ctx, r->w[1], r->chi_dn[j], rmu[j], ctx->Vh)) return 1;
@@ -305,6 +337,43 @@ int tmhip_ndrat_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, cons
   if (tmhip_scalar_prod_r(ctx, pf_up, r->w[0], ctx->Vh, 1, &ea) || tmhip_scalar_prod_r(ctx, pf_dn, r->w[1], ctx->Vh, 1, &eb)) return 1;   // :308-309
   *energy1 = ea + eb;
   return 0;
+}
+
+int tmhip_ndrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *nu, const double *rnu, int np, double invmaxev,
+                         int max_iter, double eps_sq, int rel_prec, double *energy0, int *iters) {
+  return ndrat_heatbath_body(ctx, false, pf_up, pf_dn, nu, rnu, np, invmaxev, max_iter, eps_sq, rel_prec, energy0, iters);
+}
+int tmhip_ndrat_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, int max_iter,
+                    double eps_sq, int rel_prec, double *energy1, int *iters) {
+  return ndrat_acc_body(ctx, false, pf_up, pf_dn, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, iters);
+}
+
+/* ---- type NDCLOVERRAT: the same bodies on the clover doublet, plus the clover part of the force ---- */
+int tmhip_ndcloverrat_force(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                            double kappa, double c_sw, int trlog) {
+  if (ndcloverrat_prepare(ctx, "ndcloverrat_force", np)) return 1;
+  if (!mu || !rmu || !chi_up || !chi_dn) TMHIP_FAIL("ndcloverrat_force: null argument");
+  if (rat_check_fields("ndcloverrat_force", chi_up, chi_dn, np)) return 1;
+  return ndcloverrat_force_all(ctx, chi_up, chi_dn, mu, rmu, np, invmaxev, kappa, c_sw, trlog);
+}
+
+int tmhip_ndcloverrat_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, double invmaxev,
+                                 double kappa, double c_sw, int trlog, int max_iter, double eps_sq, int rel_prec, int *iters) {
+  if (ndcloverrat_prepare(ctx, "ndcloverrat_derivative", np)) return 1;
+  if (!mu || !rmu || !iters || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndcloverrat_derivative: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np)) return 1;
+  if (tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, TMHIP_ND_OP_QSW_PM, iters)) return 1;   // :106-112
+  return ndcloverrat_force_all(ctx, r->chi_up, r->chi_dn, mu, rmu, np, invmaxev, kappa, c_sw, trlog);
+}
+
+int tmhip_ndcloverrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *nu, const double *rnu, int np, double invmaxev,
+                               int max_iter, double eps_sq, int rel_prec, double *energy0, int *iters) {
+  return ndrat_heatbath_body(ctx, true, pf_up, pf_dn, nu, rnu, np, invmaxev, max_iter, eps_sq, rel_prec, energy0, iters);
+}
+int tmhip_ndcloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, int np, int max_iter,
+                          double eps_sq, int rel_prec, double *energy1, int *iters) {
+  return ndrat_acc_body(ctx, true, pf_up, pf_dn, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, iters);
 }
 
 int tmhip_rat_force(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np) {

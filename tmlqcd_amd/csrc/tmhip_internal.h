@@ -102,6 +102,8 @@ struct tmhip_ctx {
   bool clover_set;     // sw and sw_inv both valid
   bool sw_set;         // sw valid (after tmhip_sw_term / tmhip_set_clover)
   int sw_inv_sets;     // 2 when the -mu set of sw_inv is valid as well (mu != 0), else 1
+  v2d *sw_inv_nd;      // [8][9][gs]  ((1+T)^2 + mshift)^-1 of the even sites (tmhip_sw_invert_nd), all four blocks, block 2a+b as sw_inv
+  bool clover_nd_set;  // sw_inv_nd valid: dropped by whatever invalidates sw (the rule of clover_set)
   v2d *swpm;           // clover-force accumulators swm / swp (clover_leaf.c:141-172): [2][4][9][V], site = parity * Vh + e/o index
   v2d *gauge_raw;      // lexicographic gauge field [VPR][4][9] kept from the last tmhip_sw_term for tmhip_sw_all; gauge_raw_valid
   bool gauge_raw_valid;

@@ -12,6 +12,7 @@ EO, OE = 0, 1
 FIELD_EO, FIELD_FULL = 0, 1
 OPS = {"Qtm_pm_psi": 0, "Qtm_plus_psi": 1, "Qtm_minus_psi": 2, "Mtm_plus_psi": 3, "Mtm_minus_psi": 4, "Qsw_pm_psi": 5}
 MMS_OPS = {"Qtm_pm_psi": 0, "Qsw_pm_psi": 5, "Q_pm_psi": 6}   # cg_mms_tm's operators (Q_pm_psi: FULL fields, TMHIP_OP_Q_PM_FULL)
+ND_OPS = {"Qtm_pm_ndpsi": 0, "Qsw_pm_ndpsi": 1}         # the doublet solvers' operators (TMHIP_ND_OP_*)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -171,6 +172,21 @@ def load_library():
         "tmhip_ndrat_derivative": [vp, vp, vp, pd, pd, i, d, i, d, i, C.POINTER(i)],
         "tmhip_ndrat_heatbath": [vp, vp, vp, pd, pd, i, d, i, d, i, pd, C.POINTER(i)],
         "tmhip_ndrat_acc": [vp, vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
+        "tmhip_sw_invert_nd": [vp, d], "tmhip_get_clover_nd": [vp, vp], "tmhip_sw_invert_failures": [vp, C.POINTER(i)],
+        "tmhip_assign_mul_one_sw_pm_imu_eps": [vp, i, vp, vp, vp, vp, d, d],
+        "tmhip_clover_inv_nd": [vp, i, vp, vp],
+        "tmhip_clover_gamma5_nd": [vp, i, vp, vp, vp, vp, vp, vp, d, d],
+        "tmhip_Qsw_ndpsi": [vp, vp, vp, vp, vp], "tmhip_Qsw_dagger_ndpsi": [vp, vp, vp, vp, vp],
+        "tmhip_Qsw_pm_ndpsi": [vp, vp, vp, vp, vp],
+        "tmhip_Qsw_tau1_sub_const_ndpsi": [vp, vp, vp, vp, vp, d, d, d, d],
+        "tmhip_H_eo_sw_ndpsi": [vp, vp, vp, vp, vp], "tmhip_Msw_ee_inv_ndpsi": [vp, vp, vp, vp, vp],
+        "tmhip_cg_her_nd_op": [vp, vp, vp, vp, vp, i, d, i, i, i, C.POINTER(i)],
+        "tmhip_cg_mms_tm_nd_op": [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, i, d, i, i, C.POINTER(i)],
+        "tmhip_sw_deriv_nd": [vp, i],
+        "tmhip_ndcloverrat_force": [vp, C.POINTER(vp), C.POINTER(vp), pd, pd, i, d, d, d, i],
+        "tmhip_ndcloverrat_derivative": [vp, vp, vp, pd, pd, i, d, d, d, i, i, d, i, C.POINTER(i)],
+        "tmhip_ndcloverrat_heatbath": [vp, vp, vp, pd, pd, i, d, i, d, i, pd, C.POINTER(i)],
+        "tmhip_ndcloverrat_acc": [vp, vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
         "tmhip_rat_force": [vp, C.POINTER(vp), pd, i],
         "tmhip_rat_derivative": [vp, vp, pd, pd, i, i, d, i, C.POINTER(i)],
         "tmhip_rat_heatbath": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
@@ -693,15 +709,20 @@ class Lattice:
         z = complex(z)
         _ck(self.lib.tmhip_Q_tau1_sub_const_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h, z.real, z.imag, Cpol, invev), "Q_tau1_sub_const_ndpsi")
 
-    def cg_her_nd(self, P_up, P_dn, Q_up, Q_dn, max_iter, eps_sq, rel_prec, N):
-        """solver/cg_her_nd.c with f = Qtm_pm_ndpsi; returns the reference's return value (iterations or -1)."""
+    def cg_her_nd(self, P_up, P_dn, Q_up, Q_dn, max_iter, eps_sq, rel_prec, N, op=None):
+        """solver/cg_her_nd.c with f = Qtm_pm_ndpsi (op None: the un-suffixed call; "Qtm_pm_ndpsi" / "Qsw_pm_ndpsi": tmhip_cg_her_nd_op);
+        returns the reference's return value (iterations or -1)."""
         it = C.c_int()
-        _ck(self.lib.tmhip_cg_her_nd(self.h, P_up.h, P_dn.h, Q_up.h, Q_dn.h, max_iter, eps_sq, rel_prec, N, C.byref(it)), "cg_her_nd")
+        if op is None:
+            _ck(self.lib.tmhip_cg_her_nd(self.h, P_up.h, P_dn.h, Q_up.h, Q_dn.h, max_iter, eps_sq, rel_prec, N, C.byref(it)), "cg_her_nd")
+        else:
+            _ck(self.lib.tmhip_cg_her_nd_op(self.h, P_up.h, P_dn.h, Q_up.h, Q_dn.h, max_iter, eps_sq, rel_prec, N, ND_OPS[op], C.byref(it)), "cg_her_nd_op")
         return it.value
 
-    def cg_mms_tm_nd(self, Q_up, Q_dn, shifts, max_iter, eps_sq, rel_prec, P=None):
+    def cg_mms_tm_nd(self, Q_up, Q_dn, shifts, max_iter, eps_sq, rel_prec, P=None, op=None):
         """solver/cg_mms_tm_nd.c with M_ndpsi = Qtm_pm_ndpsi: (iterations, [(Pup_i, Pdn_i) ...]), one pair per shift; P: pairs to
-        reuse as the solution fields (allocated otherwise).  Shifts still active at the end: nd_active_shifts()."""
+        reuse as the solution fields (allocated otherwise).  Shifts still active at the end: nd_active_shifts().
+        op None: the un-suffixed call; "Qtm_pm_ndpsi" / "Qsw_pm_ndpsi": tmhip_cg_mms_tm_nd_op."""
         n = len(shifts)
         if P is None:
             P = [(self.field(), self.field()) for _ in range(n)]
@@ -710,11 +731,63 @@ class Lattice:
         dn = (vp * n)(*[p[1].h for p in P])
         sh = (C.c_double * n)(*shifts)
         it = C.c_int()
-        _ck(self.lib.tmhip_cg_mms_tm_nd(self.h, up, dn, Q_up.h, Q_dn.h, sh, n, max_iter, eps_sq, rel_prec, C.byref(it)), "cg_mms_tm_nd")
+        if op is None:
+            _ck(self.lib.tmhip_cg_mms_tm_nd(self.h, up, dn, Q_up.h, Q_dn.h, sh, n, max_iter, eps_sq, rel_prec, C.byref(it)), "cg_mms_tm_nd")
+        else:
+            _ck(self.lib.tmhip_cg_mms_tm_nd_op(self.h, up, dn, Q_up.h, Q_dn.h, sh, n, max_iter, eps_sq, rel_prec, ND_OPS[op], C.byref(it)), "cg_mms_tm_nd_op")
         return it.value, P
 
     def nd_active_shifts(self):
         return self.lib.tmhip_nd_active_shifts(self.h)
+
+    # --- the clover doublet (Qsw_*_ndpsi, operator/tm_operators_nd.c; the _nd functions of operator/clovertm_operators.c) ---
+    def sw_invert_nd(self, mshift):
+        """operator/clover_invert.c:440: ((1+T)^2 + mshift)^-1 on the even sites, into sw_inv_nd (needs sw_term or set_clover first)."""
+        _ck(self.lib.tmhip_sw_invert_nd(self.h, mshift), "tmhip_sw_invert_nd")
+
+    def sw_invert_failures(self):
+        """near-singular pivots met by the last sw_invert / sw_invert_nd"""
+        n = C.c_int()
+        _ck(self.lib.tmhip_sw_invert_failures(self.h, C.byref(n)), "tmhip_sw_invert_failures")
+        return n.value
+
+    def get_clover_nd(self):
+        """sw_inv_nd in the reference's host layout sw_inv[icx][0..3][i]: [V/2][4][2][3][3][2]"""
+        swi = np.zeros((self.Vh, 4, 2, 3, 3, 2))
+        _ck(self.lib.tmhip_get_clover_nd(self.h, _hp(swi)), "tmhip_get_clover_nd")
+        return swi
+
+    def assign_mul_one_sw_pm_imu_eps(self, ieo, k_s, k_c, l_s, l_c, mu, eps):
+        _ck(self.lib.tmhip_assign_mul_one_sw_pm_imu_eps(self.h, ieo, k_s.h, k_c.h, l_s.h, l_c.h, mu, eps), "assign_mul_one_sw_pm_imu_eps")
+
+    def clover_inv_nd(self, ieo, l_c, l_s):
+        _ck(self.lib.tmhip_clover_inv_nd(self.h, ieo, l_c.h, l_s.h), "clover_inv_nd")
+
+    def clover_gamma5_nd(self, ieo, l_c, l_s, k_c, k_s, j_c, j_s, mubar, epsbar):
+        _ck(self.lib.tmhip_clover_gamma5_nd(self.h, ieo, l_c.h, l_s.h, k_c.h, k_s.h, j_c.h, j_s.h, mubar, epsbar), "clover_gamma5_nd")
+
+    def Qsw_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_Qsw_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Qsw_ndpsi")
+
+    def Qsw_dagger_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_Qsw_dagger_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Qsw_dagger_ndpsi")
+
+    def Qsw_pm_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_Qsw_pm_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Qsw_pm_ndpsi")
+
+    def Qsw_tau1_sub_const_ndpsi(self, l_s, l_c, k_s, k_c, z, Cpol, invev):
+        """tm_operators_nd.c:378-444 (complex z)"""
+        z = complex(z)
+        _ck(self.lib.tmhip_Qsw_tau1_sub_const_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h, z.real, z.imag, Cpol, invev), "Qsw_tau1_sub_const_ndpsi")
+
+    def H_eo_sw_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_H_eo_sw_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "H_eo_sw_ndpsi")
+
+    def Msw_ee_inv_ndpsi(self, l_s, l_c, k_s, k_c):
+        _ck(self.lib.tmhip_Msw_ee_inv_ndpsi(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Msw_ee_inv_ndpsi")
+
+    def sw_deriv_nd(self, ieo):
+        _ck(self.lib.tmhip_sw_deriv_nd(self.h, ieo), "sw_deriv_nd")
 
     # --- single-flavour multi-shift CG (solver/cg_mms_tm.c) ---------------------------------------------------------------
     def cg_mms_tm(self, Q, shifts, max_iter, eps_sq, rel_prec, op="Qtm_pm_psi", P=None):
@@ -770,6 +843,33 @@ class Lattice:
         (m, n), (r, _) = self._da(mu), self._da(rmu)
         it, e = C.c_int(), C.c_double()
         _ck(self.lib.tmhip_ndrat_acc(self.h, pf_up.h, pf_dn.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "ndrat_acc")
+        return e.value, it.value
+
+    def ndcloverrat_force(self, chi, mu, rmu, invmaxev, kappa, c_sw, trlog):
+        """ndrat_monomial.c:80-86, :114-184 for NDCLOVERRAT given the solutions; needs sw_term + sw_invert_nd on the current links."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        vp = C.c_void_p * max(n, 1)
+        _ck(self.lib.tmhip_ndcloverrat_force(self.h, vp(*[p[0].h for p in chi]), vp(*[p[1].h for p in chi]), m, r, n, invmaxev, kappa, c_sw, int(trlog)),
+            "ndcloverrat_force")
+
+    def ndcloverrat_derivative(self, pf_up, pf_dn, mu, rmu, invmaxev, kappa, c_sw, trlog, max_iter, eps_sq, rel_prec):
+        """solve with Qsw_pm_ndpsi + force; returns the solver's iteration count."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it = C.c_int()
+        _ck(self.lib.tmhip_ndcloverrat_derivative(self.h, pf_up.h, pf_dn.h, m, r, n, invmaxev, kappa, c_sw, int(trlog), max_iter, eps_sq, rel_prec, C.byref(it)),
+            "ndcloverrat_derivative")
+        return it.value
+
+    def ndcloverrat_heatbath(self, pf_up, pf_dn, nu, rnu, invmaxev, max_iter, eps_sq, rel_prec):
+        (m, n), (r, _) = self._da(nu), self._da(rnu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_ndcloverrat_heatbath(self.h, pf_up.h, pf_dn.h, m, r, n, invmaxev, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "ndcloverrat_heatbath")
+        return e.value, it.value
+
+    def ndcloverrat_acc(self, pf_up, pf_dn, mu, rmu, max_iter, eps_sq, rel_prec):
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_ndcloverrat_acc(self.h, pf_up.h, pf_dn.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "ndcloverrat_acc")
         return e.value, it.value
 
     def rat_force(self, chi, rmu):

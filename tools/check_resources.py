@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/rational.ru.txt
+    check_resources.py [--table OUT.txt] lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/rational.ru.txt lib/nd.ru.txt
 """
 import re
 import subprocess
@@ -46,6 +46,12 @@ RULES = [
     (r"^(void )?gaugehip::(plaquette|rectangle)_sum_kernel", "gauge action", 2),
     # the batched hopping force of the rational monomials (rational.hip): no scratch, two waves per SIMD
     (r"^(void )?rathip::deriv_Sb_batch_kernel", "batched hopping force", 2),
+    # the clover doublet (nd.hip): the doublet stencil with the clover mixing as its epilogue, and the site-local form of the same
+    # epilogues -- two 6x6 block products per flavour and chirality, streamed one 3x3 block at a time: no scratch, two waves per SIMD
+    (r"^void ndsw_hop_kernel<(\d+), (64|256), (true|false)>", "clover doublet stencil", 2),
+    (r"^void ndsw_mix_kernel<(\d+)>", "clover doublet site-local", 2),
+    (r"^(void )?sw_invert_nd_kernel", "sw_invert_nd", 2),
+    (r"^(void )?sw_deriv_nd_kernel", "sw_deriv_nd", 2),
 ]
 
 
@@ -88,7 +94,7 @@ def main(argv):
     for f in files:
         ks += parse(f)
     for k, n in zip(ks, demangle([k["mangled"] for k in ks])):
-        k["name"] = re.sub(r"\(.*$", "", n)   # drop the parameter list
+        k["name"] = re.sub(r"\(.*$", "", n.replace("(anonymous namespace)::", ""))   # drop the parameter list
     bad, rows, guarded = [], [], 0
     for k in sorted(ks, key=lambda k: k["name"]):
         tag, floor = "", None
