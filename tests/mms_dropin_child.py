@@ -4,8 +4,10 @@ A host program in miniature: the stub globals of tests/host_stub/globals.c plus 
 libtmlqcd_dropin.so, so that its weak references bind to them -- which needs a fresh process.  Calls cg_mms_tm with a
 tmlqcd_solver_params built as the rat monomial (M_psi = Qtm_pm_psi, sdim = VOLUME/2; solver/monomial_solve.c:176-215) and as
 invert_eo.c:463-490 builds it (M_psi = Q_pm_psi, sdim = VOLUME, g_mu = 0), and once with an M_psi the library does not know (a C
-function that calls Qtm_pm_psi: the generic path), in the residency mode given on the command line.  Prints the relative errors
-against tests/golden/ref_mms_4x4.npz and the other checks as one JSON line.
+function that calls Qtm_pm_psi: the generic path), in the residency mode given on the command line.  Then cg_her with that same
+unknown f on the reference's 4^4 fixture (tests/golden/ref_fields_4x4.npz, made by oracle/make_golden.py:66-70): its generic path
+runs in coherent mode and must hand the mode back as it found it.  Prints the relative errors against the golden files and the
+other checks as one JSON line.
 """
 import ctypes as C
 import json
@@ -96,6 +98,36 @@ def main(mode):
         out[name + "_iters"] = abs(it - case["iters"])
         out[name + "_reached"] = reached.value / case["reached_prec"]
         out[name + "_sloppy"] = ex.get_sloppy()
+
+    # cg_her, generic path, outside coherent mode: source = in, P = 0, the arguments the fixture was made with
+    ff = np.load(os.path.join(ROOT, "tests", "golden", "ref_fields_4x4.npz"))
+    ss = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_scalars_4x4.json")))
+    gauge = np.ascontiguousarray(ff["gauge"])
+    C.memmove(g, gauge.ctypes.data, gauge.nbytes)
+    stub.stub_mark_gauge_dirty()
+    stub.stub_boundary(ss["kappa"], 0.0, 0.0, 0.0, 0.0)
+    stub.stub_set_mu(ss["mu"])
+    d.cg_her.restype = C.c_int
+    d.cg_her.argtypes = [VP, VP, C.c_int, C.c_double, C.c_int, C.c_int, VP]
+    d.Qtm_pm_psi.argtypes = [VP, VP]
+
+    def max_rel(a, b):   # max |a-b| / max |b|, the measure of tests/util.py
+        return float(np.abs(a - b).max() / np.abs(b).max())
+
+    q, p = arr(V // 2, ff["in"]), arr(V // 2, 0.0)
+    it = d.cg_her(p[1], q[1], 1000, 1e-20, 1, V // 2, C.cast(ex.wrapped_Qtm_pm_psi, VP))
+    out["cg_her_generic"] = max_rel(host(p), ff["cg_solution"])
+    out["cg_her_generic_iters"] = abs(it - ss["cg_iters"])
+    # the mode is still the one set above: the next operator's result is on the host at once (coherent), stays in HBM until asked
+    # for (resident: the host array keeps its 7.0), or comes over through page faults as the host reads it (lazy)
+    l = arr(V // 2, 7.0)
+    st0, st1 = (C.c_ulong * 4)(), (C.c_ulong * 4)()
+    d.Qtm_pm_psi(l[1], q[1])
+    d.tmlqcd_hip_lazy_stats(st0)                # faults served before the host looks at the result ...
+    untouched = bool(np.all(l[0] == 7.0))
+    out["cg_her_generic_then_Qtm_pm_psi"] = max_rel(host(l), ff["Qtm_pm_psi"])
+    d.tmlqcd_hip_lazy_stats(st1)                # ... and after
+    out["cg_her_generic_mode_kept"] = {"coherent": not untouched and st1[0] == st0[0], "resident": untouched, "lazy": st1[0] > st0[0]}[mode]
     d.tmlqcd_hip_set_residency(0)
     print(json.dumps(out))
     sys.stdout.flush()

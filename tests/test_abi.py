@@ -50,6 +50,25 @@ def test_dropin_library_exports_reference_symbols():
     assert not missing, missing
 
 
+def test_dropin_library_exports_nothing_but_its_header():
+    """The library is loaded RTLD_GLOBAL next to host programs with names of their own (in, out, done, ctx, die ...): what its
+    translation units share among themselves (csrc/dropin_internal.h) must not become dynamic symbols.  Every defined dynamic
+    symbol is a function of include/tmlqcd_dropin.h, GaugeInfo, or a weak instantiation in namespace std."""
+    names = set(declared_functions("tmlqcd_dropin.h"))
+    out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(LIB, "libtmlqcd_dropin.so")], capture_output=True, text=True, check=True).stdout
+    stray = []
+    for line in out.splitlines():
+        if not line.strip():
+            continue
+        kind, sym = line.split()[-2:]
+        if sym in names or sym == "GaugeInfo":
+            continue
+        if kind in "WwVv" and sym.startswith(("_ZNSt", "_ZNKSt", "_ZSt")):
+            continue
+        stray.append((kind, sym))
+    assert not stray, stray
+
+
 def test_core_library_loads_and_reports_version():
     import tmlqcd_amd
     lib = tmlqcd_amd.load_library()

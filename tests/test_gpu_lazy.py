@@ -1,5 +1,5 @@
 """GPU: the drop-in's LAZY residency mode -- an UNMODIFIED host program keeps its fields in HBM, the library learns from page
-faults when the host reads or writes a mirrored array (dropin.cpp, "lazy coherence").  Host arrays are laid out as
+faults when the host reads or writes a mirrored array (tmlqcd_amd/csrc/residency.cpp, "lazy coherence").  Host arrays are laid out as
 init_spinor_field does (one block, fields back to back, base 32-byte aligned only), so every field shares its first and last
 page with its neighbours."""
 import ctypes as C
