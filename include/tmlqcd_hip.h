@@ -528,9 +528,17 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  * One option changes what is read from memory:
  * "gauge_recon" = 12 makes the twisted-mass stencil launches (fp64 and fp32) fetch only the first two rows of every link and
  * rebuild the third as conj(row0 x row1) in registers (the 12-real compression the reference exposes for its external
- * inverters, misc_types.h:29-33 COMPRESSION_12) -- 25 % fewer bytes per site.  It is opt-in and guarded: the links
- * of the resident gauge field must be SU(3) to 1e-13 (measured on the device at set_gauge / when the option is set),
- * otherwise the option is refused with a message and the full 18-real read stays in force. */
+ * inverters, misc_types.h:29-33 COMPRESSION_12) -- 25 % fewer bytes per site.  The 12-real instances are 256-thread kernels:
+ * launches with 64-thread blocks ("block" 64, or the automatic choice below 131072 sites per parity on an unsplit lattice)
+ * keep the full read.  It is opt-in and guarded: the links of the resident gauge field must be SU(3) to 1e-13, otherwise the
+ * option is refused with a message and the full 18-real read stays in force (set the option again to have links that are
+ * SU(3) again judged anew).  The rule: no stencil, operator or solver launch reads 12 reals of links whose max |row2 -
+ * conj(row0 x row1)| exceeds 1e-13.  The deviation is measured on the device when the option is set and, while it is in
+ * force, again by every call that changes the links the stencil reads, before that call returns: tmhip_set_gauge, the ILDG
+ * reader, tmhip_update_gauge, tmhip_multi_update_gauge, tmhip_sw_term / tmhip_sw_all with host links, tmhip_resort_gauge.
+ * Molecular-dynamics updates need this: restoresu3 normalises rows 0 and 1 of exp(step P) without orthogonalising them, so
+ * updated links leave SU(3) by 1e-7 after two steps with |step P| = 2.5 and by 1e-13 after some hundred ordinary ones.
+ * The measurement is one launch and one synchronisation per such call; with the default 18-real read nothing is added. */
 int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value);
 /* max |row2 - conj(row0 x row1)| over all links of the resident gauge field */
 int tmhip_gauge_su3_deviation(tmhip_ctx *ctx, double *maxdev);

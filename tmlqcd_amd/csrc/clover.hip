@@ -925,6 +925,9 @@ int tmhip_sw_term(tmhip_ctx *ctx, const void *gauge_host, double kappa, double c
     TMHIP_CHECK(hipMemcpyAsync(ctx->gauge_raw, gauge_host, gbytes, hipMemcpyHostToDevice, ctx->stream));
     ctx->gauge_copy_current = false;
     ctx->gauge_raw_valid = true;
+    // these are the resident links from now on: the stencil's copy (and the guard of "gauge_recon" 12) follows them on every rank, also on
+    // a T-split rank of one or two time-slices, whose clover term below reads the lexicographic field only
+    if (tmhip_resort_gauge(ctx)) return 1;
   }
   const bool split = ctx->g.nproc_t > 1;
   const int ib = split ? ctx->face : 0, ie = split ? ctx->Vh - ctx->face : ctx->Vh;      // sites whose plaquettes stay on this rank
@@ -1117,7 +1120,8 @@ static int sw_all_prepare(tmhip_ctx *ctx, const void *gauge_host) {
   if (!ctx->deriv && tmhip_derivative_zero(ctx)) return 1;
   const size_t XYZ = (size_t)ctx->g.LX * ctx->g.LY * ctx->g.LZ;
   // owner-computes form: the interior (or the whole unsplit lattice) reads the stencil's gauge copy -- it must come from the same links
-  if (!ctx->gauge_copy_current && (ctx->g.nproc_t == 1 || ctx->g.T > 2) && tmhip_resort_gauge(ctx)) return 1;
+  // (re-sorted on every rank: host links passed here are the resident links from now on, for the stencil and its 12-real guard too)
+  if (!ctx->gauge_copy_current && tmhip_resort_gauge(ctx)) return 1;
   // pass 1: the six insertion matrices of every site, compact (30 complex planes)
   const unsigned ws = (unsigned)ctx->V;
   if (!ctx->sw_ins) TMHIP_CHECK(hipMalloc((void **)&ctx->sw_ins, (size_t)30 * ws * sizeof(v2d)));

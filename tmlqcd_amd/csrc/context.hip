@@ -341,14 +341,15 @@ int tmhip_set_gauge(tmhip_ctx *ctx, const void *host) {
   if (!ctx->gauge_raw) TMHIP_CHECK(hipMalloc((void **)&ctx->gauge_raw, bytes));
   TMHIP_CHECK(hipMemcpyAsync(ctx->gauge_raw, host, bytes, hipMemcpyHostToDevice, ctx->stream));
   ctx->gauge_raw_valid = true;
-  if (tmhip_resort_gauge(ctx)) return 1;
+  if (tmhip_resort_gauge(ctx)) return 1;      // (with "gauge_recon" 12 in force: and the guard's measurement of the new links)
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (ctx->opt_recon == 12) return tmhip_check_gauge_recon(ctx);
   return 0;
 }
 
 /* "gauge_recon" = 12 is only exact for SU(3) links: measure how far the resident links are from it and drop back to the
- * full 18-real read (with a message) when they are not unitary to rounding, e.g. smeared or deliberately non-SU(3) input. */
+ * full 18-real read (with a message) when they are not unitary to rounding, e.g. smeared or deliberately non-SU(3) input, or
+ * links that molecular-dynamics updates have carried away from SU(3).  Called when the option is set and, while it is in
+ * force, by links_changed (md_update.hip) after every change of the stencil's gauge copy. */
 int tmhip_check_gauge_recon(tmhip_ctx *ctx) {
   if (!ctx->gauge_set) return 0;     // checked again by tmhip_set_gauge
   if (ctx->gauge_recon_dev < 0.0) {

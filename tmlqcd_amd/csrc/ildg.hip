@@ -358,7 +358,6 @@ int tmhip_gauge_unpack_ildg(tmhip_ctx *ctx, const void *file_bytes, int prec, un
   unsigned h[2];
   if (sums_fetch(ctx, h)) return 1;
   if (sums) { sums[0] = h[0]; sums[1] = h[1]; }
-  if (ctx->opt_recon == 12) return tmhip_check_gauge_recon(ctx);
   return 0;
 }
 

@@ -242,19 +242,24 @@ static int launch_halo_backward(tmhip_ctx *ctx) {
   TMHIP_CHECK(hipGetLastError());
   return 0;
 }
-static void links_changed(tmhip_ctx *ctx) {
+// Every path that puts new links into the stencil's gauge copy ends here (tmhip_resort_gauge -- behind tmhip_set_gauge, the ILDG reader and
+// tmhip_sw_term / tmhip_sw_all with host links --, tmhip_update_gauge, tmhip_multi_update_gauge), with the copy complete on ctx->stream.
+static int links_changed(tmhip_ctx *ctx) {
   ctx->gauge_set = true;
   ctx->gauge_copy_current = true;
   ctx->gauge32_set = false;       // the fp32 twin is rebuilt lazily from the new links
   ctx->gauge_recon_dev = -1.0;
+  // "gauge_recon" 12 holds for SU(3) links only, and restoresu3 (rows 0 and 1 normalised, not orthogonalised) lets the updated links drift
+  // away from it: the guard measures the new copy before any stencil can read 12 reals of it and gives the option up above 1e-13.  One
+  // launch and one synchronisation per change of the links under the option; nothing with the default 18-real read.
+  return ctx->opt_recon == 12 ? tmhip_check_gauge_recon(ctx) : 0;
 }
 
 // the stencil's gauge copy (and everything derived from the links) from the device-resident lexicographic field, halo slabs included
 int tmhip_resort_gauge(tmhip_ctx *ctx) {
   if (!ctx->gauge_raw || !ctx->gauge_raw_valid) TMHIP_FAIL("no lexicographic gauge field on the device");
   if (launch_links(ctx, false, 0.0) || launch_halo_backward(ctx)) return 1;
-  links_changed(ctx);
-  return 0;
+  return links_changed(ctx);
 }
 
 extern "C" {
@@ -300,8 +305,7 @@ int tmhip_update_gauge(tmhip_ctx *ctx, double step) {
   if (launch_halo_backward(ctx)) return 1;                     // T-split: the backward t-links of the t = 0 sites from the neighbour's updated slice
   // clover blocks belong to the old links: tmhip_sw_term (gauge = NULL: from the resident links) / tmhip_sw_invert again
   ctx->sw_set = false; ctx->clover_set = false; ctx->clover_nd_set = false; ctx->clover32_set = false;
-  links_changed(ctx);
-  return 0;
+  return links_changed(ctx);
 }
 
 /* The same on a T-split lattice held by n contexts of one process (peer copies instead of RCCL, as tmhip_multi_sw_all): every
@@ -325,7 +329,7 @@ int tmhip_multi_update_gauge(int n, tmhip_ctx **ctxs, double step) {
     TMHIP_CHECK(hipMemcpyPeerAsync(slab_dn, c->device, dn->gauge_raw + (size_t)(dn->g.T - 1) * XYZ * 36, dn->device, sb, c->stream));         // the down neighbour's t = T-1
     c->sw_set = false; c->clover_set = false; c->clover_nd_set = false; c->clover32_set = false;
     if (launch_halo_backward(c)) return 1;
-    links_changed(c);
+    if (links_changed(c)) return 1;
   }
   for (int r = 0; r < n; r++) { TMHIP_CHECK(hipSetDevice(ctxs[r]->device)); TMHIP_CHECK(hipStreamSynchronize(ctxs[r]->stream)); }
   return 0;
