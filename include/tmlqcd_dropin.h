@@ -210,10 +210,18 @@ int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spin
  * degenerate clover symbol called after sw_invert_nd without tmlqcd_hip_sw_invert in between uploads the host's sw / sw_inv again --
  * whose first half now holds the doublet's inverse -- and drops sw_inv_nd.
  * tmlqcd_hip_sw_invert_failures() returns six_invert's count of near-singular pivots of the last inversion (the reference prints it).
- * Not here: the fp32 twins (Qsw_pm_ndpsi_32), Qsw_pm_ndbipsi, clover_nd, sw_trace_nd. */
+ * Not here: the fp32 twins (Qsw_pm_ndpsi_32), Qsw_pm_ndbipsi, clover_nd. */
 void sw_invert_nd(const double mshift);                                                                                  /* clover_invert.c:440 */
 void sw_deriv_nd(const int ieo);                                                                                         /* clover_deriv.c:156 */
 int tmlqcd_hip_sw_invert_failures(void);
+/* The tr-log energies (operator/clover_det.c; replaces clover_det.o, which holds nothing else that has a caller outside it): from the
+ * device's clover term where it belongs to the current links, else the host's sw is uploaded first.  Site-local: they run on T-split
+ * ranks and return the sum over all ranks there, as the reference's MPI_Allreduce does.  The sum over the sites is the library's fixed-order
+ * one, not the reference's Kahan sum: the same bits on every run, equal to the reference's value to rounding on the scale of sum |term|.
+ * tmlqcd_hip_sw_trace_failures(): six_det's ifail of the last of the two calls, which the reference only prints. */
+double sw_trace(const int ieo, const double mu);                                                                         /* clover_det.c:115 */
+double sw_trace_nd(const int ieo, const double mu, const double eps);                                                    /* clover_det.c:202 */
+int tmlqcd_hip_sw_trace_failures(void);
 void assign_mul_one_sw_pm_imu_eps(const int ieo, spinor *const k_s, spinor *const k_c, const spinor *const l_s, const spinor *const l_c,
                                   const double mu, const double eps);                                                    /* clovertm_operators.c:960 */
 void clover_inv_nd(const int ieo, spinor *const l_c, spinor *const l_s);                                                 /* :352 */
@@ -285,7 +293,7 @@ void tmlqcd_hip_sync_momenta_to_host(hamiltonian_field_t *const hf);
 enum { TMLQCD_HIP_COHERENT = 0, TMLQCD_HIP_RESIDENT = 1, TMLQCD_HIP_LAZY = 2 };
 /* Device versions of sw_term(g_gauge_field, kappa, c_sw) / sw_invert(ieo, mu) (operator/clover_term.c:88,
  * operator/clover_invert.c:170).  They carry their own names because the reference keeps other, unrelated functions in
- * the same objects (six_det, sw_invert_nd, sw_trace ...), so those objects stay on the link line; replace the two calls
+ * the same objects (sw_invert_nd, six_invert ...), so those objects stay on the link line; replace the two calls
  * in operator.c:329-330,364 / the clover monomials to use them.  The host's sw / sw_inv arrays receive copies. */
 void tmlqcd_hip_sw_term(const double kappa, const double c_sw);
 void tmlqcd_hip_sw_invert(const int ieo, const double mu);
@@ -344,6 +352,17 @@ int tmlqcd_hip_ndcloverrat_heatbath(spinor *const pf, spinor *const pf2, const d
                                     const int max_iter, const double eps_sq, const int rel_prec, double *energy0);
 int tmlqcd_hip_ndcloverrat_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np, const int max_iter,
                                const double eps_sq, const int rel_prec, double *energy1);
+/* type CLOVERRAT of rat_monomial.c: the three bodies on Qsw_pm_psi / Qsw_plus_psi / H_eo_sw_inv_psi at g_mu = g_mu3 = 0 (both left alone).  The
+ * derivative also does the clover part of rat_monomial.c:66-73, :113-116, :134-139 on the device: swm / swp zeroed, two sw_spinor_eo per shift
+ * (summed per group of shifts in one launch per parity), sw_deriv(EE, 0.) when trlog is set, sw_all(kappa, c_sw).  The caller runs
+ * tmlqcd_hip_sw_term and tmlqcd_hip_sw_invert(EE, 0.) first (:76-78); with an inverse made for another parity or mu, or a clover term that came
+ * from the host (tmlqcd_hip_update_clover), the three calls end the program with a message before they touch anything. */
+int tmlqcd_hip_cloverrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, const double *mu, const double *rmu, const int np, const double kappa,
+                                    const double c_sw, const int trlog, const int max_iter, const double eps_sq, const int rel_prec);
+int tmlqcd_hip_cloverrat_heatbath(spinor *const pf, const double *nu, const double *rnu, const int np, const int max_iter, const double eps_sq,
+                                  const int rel_prec, double *energy0);
+int tmlqcd_hip_cloverrat_acc(spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter, const double eps_sq,
+                             const int rel_prec, double *energy1);
 int tmlqcd_hip_rat_derivative(hamiltonian_field_t *const hf, spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter,
                               const double eps_sq, const int rel_prec);
 int tmlqcd_hip_rat_heatbath(spinor *const pf, const double *nu, const double *rnu, const int np, const int max_iter, const double eps_sq,

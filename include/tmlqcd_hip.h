@@ -290,6 +290,21 @@ int tmhip_rat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, const 
                        double *energy0, int *iters);
 int tmhip_rat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
                   double *energy1, int *iters);
+/* Type CLOVERRAT of monomial/rat_monomial.c:56-262: the rat bodies on Qsw_pm_psi / Qsw_plus_psi / H_eo_sw_inv_psi(.., 0.) at twisted mass 0
+ * (mu and mu3 of the context are back on return), plus the clover part of the force: tmhip_swpm_zero, per group of "rat_batch" shifts one
+ * tmhip_sw_spinor_eo_batch launch per parity (EE (w2, w3), OO (w0, chi_j); the per-call kernel with "rat_batch" 1), tmhip_sw_deriv(EE, 0.) when
+ * trlog is set, tmhip_sw_all(NULL, kappa, c_sw).  The caller has run tmhip_sw_term and tmhip_sw_invert(EE, 0.) on the current links
+ * (rat_monomial.c:76-78,165-166,227-228).  The context remembers parity and mu of the last tmhip_sw_invert; the four calls refuse, before any
+ * launch and with every output untouched, when sw_inv is not valid, is not that of (EE, 0.) (made for OO or with mu != 0, or uploaded with
+ * tmhip_set_clover), when the clover term did not come from tmhip_sw_term, on a T-split or loopback context, for np outside [1, 32] and for
+ * fields that are not fp64 one-parity. */
+int tmhip_cloverrat_force(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np, double kappa, double c_sw, int trlog);
+int tmhip_cloverrat_derivative(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, double kappa, double c_sw, int trlog,
+                               int max_iter, double eps_sq, int rel_prec, int *iters);
+int tmhip_cloverrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, const double *rnu, int np, int max_iter, double eps_sq, int rel_prec,
+                             double *energy0, int *iters);
+int tmhip_cloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                        double *energy1, int *iters);
 
 /* Clover part of the force (monomial/cloverdet_monomial.c:110-147): the insertion matrices swm / swp (clover_leaf.c:141) are
  * device-resident; zero them, accumulate the spinor outer products (operator/clover_deriv.c:252) and the tr-log term
@@ -300,6 +315,10 @@ int tmhip_rat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const doubl
 int tmhip_swpm_zero(tmhip_ctx *ctx);
 int tmhip_sw_spinor_eo(tmhip_ctx *ctx, int ieo, tmhip_field *kk, tmhip_field *ll, double fac);
 int tmhip_sw_deriv(tmhip_ctx *ctx, int ieo, double mu);
+/* sum_j sw_spinor_eo(ieo, kk[j], ll[j], fac[j]) for j = 0 .. n-1, 1 <= n <= 64, in ONE launch: swm / swp of parity ieo are read and written
+ * once, whatever n is.  The fields are only read; one field may appear in several pairs.  fp64 one-parity fields of one stride; site-local,
+ * so T-split contexts are served.  The sum over j is formed before it is added: the result differs from n calls by rounding. */
+int tmhip_sw_spinor_eo_batch(tmhip_ctx *ctx, int ieo, int n, tmhip_field **kk, tmhip_field **ll, const double *fac);
 int tmhip_sw_all(tmhip_ctx *ctx, const void *gauge_field, double kappa, double c_sw);
 /* sw_all on a T-split lattice held by n contexts of THIS process (peer copies instead of RCCL for the two-sided derivative halo
  * that xchange/xchange_deri.c ships); every context needs its own tmhip_sw_term (which keeps the links incl. halo slabs). */
@@ -314,10 +333,21 @@ int tmhip_set_clover(tmhip_ctx *ctx, const void *sw, const void *sw_inv);
 /* ... or computed on the device: sw_term(gf, kappa, c_sw) (operator/clover_term.c:88) from the host gauge field handed
  * over exactly as for tmhip_set_gauge, then sw_invert(ieo, mu) (operator/clover_invert.c:170; the operators below expect
  * ieo = 0 = EE as operator.c:364 uses it).  tmhip_get_clover copies the blocks back in the reference's host layouts
- * (either pointer may be NULL) for host code that still wants them (sw_trace, sw_deriv ...). */
+ * (either pointer may be NULL) for host code that still wants them. */
 int tmhip_sw_term(tmhip_ctx *ctx, const void *gauge_field, double kappa, double c_sw);
 int tmhip_sw_invert(tmhip_ctx *ctx, int ieo, double mu);
 int tmhip_get_clover(tmhip_ctx *ctx, void *sw, void *sw_inv);
+/* The tr-log energies on the device's sw (operator/clover_det.c:115 sw_trace, :202 sw_trace_nd), sites of parity ieo:
+ *   sw_trace     sum_x sum_i log |det(1 + T_i(x) + i mu)|^2               (clover_trlog_monomial.c, the trlog option of cloverdet)
+ *   sw_trace_nd  sum_x log( Re det_0 Re det_1 ), det_i = det((1 + T_i(x))^2 + mu^2 - eps^2)   (clovernd_trlog_monomial.c)
+ * by a fully unrolled Householder triangularisation (six_det) per site and the library's fixed-order sum: the same lattice gives the same
+ * bits on every run (the reference's Kahan sum over the sites is not reproduced: the values agree to rounding on the scale of
+ * sum_x |term|).  Site-local, so T-split contexts are served; global != 0 adds the ranks' shares (the reference's MPI_Allreduce).
+ * Refused when sw is not that of the current links (tmhip_sw_term / tmhip_set_clover after the last link update).
+ * tmhip_sw_trace_failures: pivots below the reference's tiny_t met by the last of the two calls (six_det's ifail, which it only prints). */
+int tmhip_sw_trace(tmhip_ctx *ctx, int ieo, double mu, int global, double *out);
+int tmhip_sw_trace_nd(tmhip_ctx *ctx, int ieo, double mu, double eps, int global, double *out);
+int tmhip_sw_trace_failures(tmhip_ctx *ctx);
 int tmhip_clover_inv(tmhip_ctx *ctx, tmhip_field *l, int tau3sign, double mu);                                   /* clovertm_operators.c:287 */
 int tmhip_clover_gamma5(tmhip_ctx *ctx, int ieo, tmhip_field *l, tmhip_field *k, tmhip_field *j, double mu);     /* :448 */
 int tmhip_clover(tmhip_ctx *ctx, int ieo, tmhip_field *l, tmhip_field *k, tmhip_field *j, double mu);            /* :535 */
@@ -515,6 +545,8 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                flavour mixing in its epilogue; 0: two single-flavour stencils per hop and a mixing pass
  *   "rat_batch" shifts per group of the rat / ndrat force (clamped to [1, 32], default 12, the fastest of 1 / 2 / 4 / 12
  *                measured at 16^4 and 32^4 with np = 12, profiles/r08_rat_speed.log): one tmhip_deriv_Sb_batch launch per parity and group
+ *                and, for the clover types (ndcloverrat, cloverrat), one tmhip_sw_spinor_eo_batch launch per parity and group; 1: the per-call
+ *                tmhip_sw_spinor_eo kernel in the reference's order
  *   "gauge_global_sums" 0 (default) | 1: tmhip_measure_plaquette / _gauge_action / _rectangles return the rank's own share (0: the reference's value
  *                before its MPI_Allreduce) or the sum over the ranks of a T split (1: its return value; needs the communicator, like parallel = 1)
  *   "cg_sync" 1: host-side scalars as in the reference loop;  "cg_batch" n: iterations enqueued between two polls of `done`

@@ -348,6 +348,179 @@ __global__ __launch_bounds__(128) void sw_spinor_eo_kernel(v2d *__restrict__ swp
       }
 }
 
+// sw_spinor_eo for n pairs in one launch: swm / swp += sum_j fac_j (u_j -+ v_j), read and written once whatever n is (the per-call
+// kernel above moves 2 x 1152 B of swm / swp per site and call next to 384 B of spinors: 64.5 kB per site for the 24 pairs of
+// ndcloverrat at np = 12, against 11.5 kB when every word moves once).  All four blocks n of swm and swp in one thread are 144
+// doubles of accumulators and do not fit at two waves per SIMD, so the block n is the wave: a 256-thread block covers 64 sites,
+// wave w accumulates block n = w (36 doubles) and loads only the four colour vectors its n needs.  Every spinor word is then
+// read by two of the four waves -- waves of ONE block, hence of one CU, so the second read is an L1 / L2 hit and not a second
+// trip to HBM (with n in blockIdx.y, as sw_deriv_kernel has it, the two readers run far apart, on XCDs with separate L2s: 20.7 kB
+// per site).  152 VGPRs (the compiler keeps the loads of several pairs in flight), three waves per SIMD, no scratch
+// (tools/check_resources.py).
+// The fields are only read, and one field may serve several pairs on either side: no __restrict__ between them is claimed.
+struct SwBatchArgs {
+  const v2d *kk[RAT_MAX_PAIRS], *ll[RAT_MAX_PAIRS];
+  double fac[RAT_MAX_PAIRS];
+  v2d *swpm;
+  int n, ns, Vh, V, ieo;
+};
+__global__ __launch_bounds__(256) void sw_spinor_eo_batch_kernel(const SwBatchArgs a) {
+  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (i >= a.Vh) return;
+  const int n = threadIdx.x >> 6;
+  const int ra = n >> 1, sa = (n == 1 || n == 2) ? 1 : 0;     // as in sw_spinor_eo_kernel
+  const size_t ns = a.ns;
+  v2d sv[9], su[9];
+#pragma unroll
+  for (int e = 0; e < 9; e++) { sv[e] = v2d{0.0, 0.0}; su[e] = v2d{0.0, 0.0}; }
+  for (int j = 0; j < a.n; j++) {
+    const v2d *kp = a.kk[j] + i, *lp = a.ll[j] + i;
+    const double f = a.fac[j];
+    v2d r0[3], r2[3], q0[3], q2[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      r0[c] = f * kp[(size_t)(3 * ra + c) * ns]; r2[c] = f * kp[(size_t)(3 * (ra + 2) + c) * ns];
+      q0[c] = lp[(size_t)(3 * sa + c) * ns]; q2[c] = lp[(size_t)(3 * (sa + 2) + c) * ns];
+    }
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) { sv[3 * r + c] += cf_cmulc(r0[r], q0[c]); su[3 * r + c] -= cf_cmulc(r2[r], q2[c]); }
+  }
+  const size_t s = (size_t)a.ieo * a.Vh + i;
+#pragma unroll
+  for (int e = 0; e < 9; e++) {
+    v2d *pm = a.swpm + ((size_t)(0 * 4 + n) * 9 + e) * a.V + s, *pp = a.swpm + ((size_t)(1 * 4 + n) * 9 + e) * a.V + s;
+    *pm += su[e] - sv[e];
+    *pp += su[e] + sv[e];
+  }
+}
+
+// operator/clover_det.c:57-112 six_det: the triangularisation of six_invert_dev without the inverse; det = prod_k sigma_k * a[5][5].
+// Fully unrolled => `a` lives in registers.  fail counts the pivots below tiny_t (the reference's ifail).
+__device__ __forceinline__ v2d six_det_dev(v2d (&a)[6][6], int &fail) {
+  const double tiny = 1.0e-20;   // clover_leaf.c:55
+  v2d det = v2d{1.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = k + 1; j < 6; j++) s += a[j][k].x * a[j][k].x + a[j][k].y * a[j][k].y;
+    s = sqrt(1.0 + s / (a[k][k].x * a[k][k].x + a[k][k].y * a[k][k].y));
+    const v2d sigma = v2d{s * a[k][k].x, s * a[k][k].y};
+    det = m3_cmul(det, sigma);
+    if (sigma.x * sigma.x + sigma.y * sigma.y < tiny) fail++;
+    a[k][k] += sigma;
+    const double p = sigma.x * a[k][k].x + sigma.y * a[k][k].y;
+#pragma unroll
+    for (int j = k + 1; j < 6; j++) {
+      v2d z = v2d{0.0, 0.0};
+#pragma unroll
+      for (int i = k; i < 6; i++) z += m3_cmul(m3_conj(a[i][k]), a[i][j]);
+      z = v2d{z.x / p, z.y / p};
+#pragma unroll
+      for (int i = k; i < 6; i++) a[i][j] -= m3_cmul(z, a[i][k]);
+    }
+  }
+  const v2d sigma = a[5][5];
+  if (sigma.x * sigma.x + sigma.y * sigma.y < tiny) fail++;
+  return m3_cmul(det, sigma);
+}
+
+// det of a hermitian positive definite 6x6 block given by its lower triangle (a[r][c], c <= r; the rest is never touched): the product of the
+// pivots of an LDL^H factorisation without pivoting, real and positive.  36 doubles live instead of the 72 of the Householder sweep -- on
+// the squared block of sw_trace_nd that sweep spills at two waves per SIMD.  fail counts the pivots whose square is below tiny_t.
+__device__ __forceinline__ double six_det_herm_dev(v2d (&a)[6][6], int &fail) {
+  const double tiny = 1.0e-20;
+  double det = 1.0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double dk = a[k][k].x;
+    det *= dk;
+    if (dk * dk < tiny) fail++;
+    const double inv = 1.0 / dk;
+#pragma unroll
+    for (int i = k + 1; i < 6; i++) {
+      const v2d l = v2d{a[i][k].x * inv, a[i][k].y * inv};
+#pragma unroll
+      for (int j = k + 1; j <= i; j++) a[i][j] -= cf_cmulc(l, a[j][k]);
+    }
+  }
+  return det;
+}
+
+// operator/clover_det.c:115-279: thread = site of parity ieo, the two chiralities one after the other (one 6x6 block live).
+//   ND false, sw_trace:    sum_b log |det(1 + T_b + i mu)|^2
+//   ND true,  sw_trace_nd: log( det((1 + T_0)^2 + m) det((1 + T_1)^2 + m) ),  m = mu^2 - eps^2; the lower triangle of the square is built a column
+//             of 1 + T at a time as in sw_invert_nd_kernel; hermitian and positive definite, so LDL^H in the place of six_det
+// sw_trace: 245 VGPRs, sw_trace_nd: 202 (all loads of a block in flight), both without scratch at two waves per SIMD or more (tools/check_resources.py).
+// One partial per block through the library's fixed-order block sum (the reference's Kahan sum over the sites is not reproduced).
+template <bool ND>
+__global__ __launch_bounds__(256, 2) void sw_trace_kernel(const v2d *__restrict__ swp, int gs, int Vh, double m, double *partials, int *fails) {
+  __shared__ double wsum[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double acc = 0.0;
+  if (i < Vh) {
+    int f = 0;
+    double d0 = 1.0;
+#pragma unroll 1
+    for (int b = 0; b < 2; b++) {
+      v2d a[6][6];
+      if (!ND) {
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            a[r][c] = swp[((size_t)(0 + b) * 9 + 3 * r + c) * gs + i];
+            const v2d off = swp[((size_t)(2 + b) * 9 + 3 * r + c) * gs + i];
+            a[r][c + 3] = off;
+            a[c + 3][r] = m3_conj(off);
+            a[r + 3][c + 3] = swp[((size_t)(4 + b) * 9 + 3 * r + c) * gs + i];
+          }
+#pragma unroll
+        for (int r = 0; r < 6; r++) a[r][r].y += m;   // add_tm: the same sign for both chiralities (clover_det.c:155-158)
+      } else {
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+          for (int c = 0; c <= r; c++) a[r][c] = v2d{0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+          v2d col[6];
+#pragma unroll
+          for (int r = 0; r < 3; r++) {
+            if (k < 3) {
+              col[r] = swp[((size_t)(0 + b) * 9 + 3 * r + k) * gs + i];
+              col[r + 3] = m3_conj(swp[((size_t)(2 + b) * 9 + 3 * k + r) * gs + i]);
+            } else {
+              col[r] = swp[((size_t)(2 + b) * 9 + 3 * r + (k - 3)) * gs + i];
+              col[r + 3] = swp[((size_t)(4 + b) * 9 + 3 * r + (k - 3)) * gs + i];
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int c = 0; c <= r; c++) a[r][c] += cf_cmulc(col[r], col[c]);
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++) a[r][r].x += m;
+        const double det = six_det_herm_dev(a, f);
+        if (b == 0) d0 = det;
+        else acc = log(d0 * det);
+      }
+      if (!ND) {
+        const v2d det = six_det_dev(a, f);
+        acc += log(det.x * det.x + det.y * det.y);
+      }
+    }
+    if (f) atomicAdd(fails, f);
+  }
+  acc = tmhip_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
 // operator/clover_deriv.c:72-153: thread = (site of parity ieo, n); sw_inv blocks [set][2n + b]
 __global__ __launch_bounds__(256) void sw_deriv_kernel(v2d *__restrict__ swpm, const v2d *__restrict__ swi, int gs, int Vh, int V, int ieo, int nsets,
                                                        double fac) {
@@ -886,6 +1059,7 @@ int tmhip_set_clover(tmhip_ctx *ctx, const void *sw_host, const void *sw_inv_hos
   ctx->clover_set = true;
   ctx->sw_set = true;
   ctx->sw_inv_sets = 2;
+  ctx->sw_inv_ieo = -1;        // whatever the host inverted
   ctx->clover32_set = false;
   ctx->clover_nd_set = false;
   return 0;
@@ -957,6 +1131,7 @@ int tmhip_sw_term(tmhip_ctx *ctx, const void *gauge_host, double kappa, double c
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   ctx->sw_set = true;
   ctx->clover_set = false;     // sw_inv no longer matches
+  ctx->sw_inv_ieo = -1;
   ctx->clover_nd_set = false;
   ctx->clover32_set = false;
   return 0;
@@ -979,6 +1154,7 @@ int tmhip_sw_invert(tmhip_ctx *ctx, int ieo, double mu) {
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (fails > 0 && ctx->g.proc_t == 0) printf("# inversion failed in six_invert code %d\n", fails);   /* clover_invert.c:213-216 */
   ctx->sw_inv_sets = nsets;
+  ctx->sw_inv_ieo = ieo ? 1 : 0; ctx->sw_inv_mu = mu;
   ctx->clover_set = true;
   ctx->clover32_set = false;
   return 0;
@@ -1082,6 +1258,47 @@ int tmhip_sw_spinor_eo(tmhip_ctx *ctx, int ieo, tmhip_field *kk, tmhip_field *ll
   TMHIP_CHECK(hipGetLastError());
   return 0;
 }
+/* sw_spinor_eo(ieo, kk[j], ll[j], fac[j]) for j < n in one launch: swm / swp of parity ieo are read and written once */
+int tmhip_sw_spinor_eo_batch(tmhip_ctx *ctx, int ieo, int n, tmhip_field **kk, tmhip_field **ll, const double *fac) {
+  if (n < 1 || n > RAT_MAX_PAIRS) TMHIP_FAIL("sw_spinor_eo_batch: n = %d is outside [1, %d]", n, RAT_MAX_PAIRS);
+  if (!kk || !ll || !fac) TMHIP_FAIL("sw_spinor_eo_batch: null argument");
+  for (int j = 0; j < n; j++) {
+    if (need64(kk[j], "sw_spinor_eo_batch") || need64(ll[j], "sw_spinor_eo_batch")) return 1;
+    if (kk[j]->ns != kk[0]->ns || ll[j]->ns != kk[0]->ns) TMHIP_FAIL("sw_spinor_eo_batch: fields with different strides (pair %d)", j);
+  }
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (swpm_alloc(ctx)) return 1;
+  SwBatchArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < n; j++) { a.kk[j] = (const v2d *)kk[j]->d; a.ll[j] = (const v2d *)ll[j]->d; a.fac[j] = fac[j]; }
+  a.swpm = ctx->swpm; a.n = n; a.ns = kk[0]->ns; a.Vh = ctx->Vh; a.V = ctx->V; a.ieo = ieo ? 1 : 0;
+  hipLaunchKernelGGL(sw_spinor_eo_batch_kernel, dim3((ctx->Vh + 63) / 64), dim3(256), 0, ctx->stream, a);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+/* operator/clover_det.c:115 sw_trace(ieo, mu) and :202 sw_trace_nd(ieo, mu, eps) on the device's sw.  Site-local: they run on
+ * T-split contexts, where global != 0 adds the ranks' shares (the reference's MPI_Allreduce, :184,274). */
+static int sw_trace_run(tmhip_ctx *ctx, const char *who, bool nd, int ieo, double m, int global, double *out) {
+  if (!out) TMHIP_FAIL("%s: null argument", who);
+  if (!ctx->sw_set) TMHIP_FAIL("%s: the clover term is not that of the current links (call tmhip_sw_term / tmhip_set_clover)", who);
+  if (global && ctx->g.nproc_t > 1 && !ctx->comm_ready) TMHIP_FAIL("%s: a sum over the ranks was asked for but the context has no communicator", who);
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  const int nb = (ctx->Vh + 255) / 256;
+  if (nb > ctx->max_partials) TMHIP_FAIL("%s: partials buffer too small", who);
+  if (!ctx->sw_trace_fail) TMHIP_CHECK(hipMalloc((void **)&ctx->sw_trace_fail, sizeof(int)));
+  TMHIP_CHECK(hipMemsetAsync(ctx->sw_trace_fail, 0, sizeof(int), ctx->stream));
+  if (nd) hipLaunchKernelGGL(sw_trace_kernel<true>, dim3(nb), dim3(256), 0, ctx->stream, swpar(ctx, ieo), ctx->gs, ctx->Vh, m, ctx->partials, ctx->sw_trace_fail);
+  else hipLaunchKernelGGL(sw_trace_kernel<false>, dim3(nb), dim3(256), 0, ctx->stream, swpar(ctx, ieo), ctx->gs, ctx->Vh, m, ctx->partials, ctx->sw_trace_fail);
+  TMHIP_CHECK(hipGetLastError());
+  TMHIP_CHECK(hipMemcpyAsync(&ctx->sw_trace_fails, ctx->sw_trace_fail, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  return tmhip_reduce_finish(ctx, nb, global && ctx->g.nproc_t > 1, out);   // synchronises the stream
+}
+int tmhip_sw_trace(tmhip_ctx *ctx, int ieo, double mu, int global, double *out) { return sw_trace_run(ctx, "tmhip_sw_trace", false, ieo, mu, global, out); }
+int tmhip_sw_trace_nd(tmhip_ctx *ctx, int ieo, double mu, double eps, int global, double *out) {
+  return sw_trace_run(ctx, "tmhip_sw_trace_nd", true, ieo, mu * mu - eps * eps, global, out);
+}
+/* pivots below the reference's tiny_t met by the last tmhip_sw_trace / tmhip_sw_trace_nd (six_det's ifail, which it only prints) */
+int tmhip_sw_trace_failures(tmhip_ctx *ctx) { return ctx->sw_trace_fails; }
 /* operator/clover_deriv.c:72 sw_deriv(ieo, mu): needs the sw_inv of parity ieo (tmhip_sw_invert(ieo, mu) / tmhip_set_clover) */
 int tmhip_sw_deriv(tmhip_ctx *ctx, int ieo, double mu) {
   if (!ctx->clover_set) TMHIP_FAIL("sw_deriv called before tmhip_sw_invert / tmhip_set_clover");

@@ -231,6 +231,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   if (ctx->sw32) (void)hipFree(ctx->sw32);
   if (ctx->sw_inv32) (void)hipFree(ctx->sw_inv32);
   if (ctx->sw_fail) (void)hipFree(ctx->sw_fail);
+  if (ctx->sw_trace_fail) (void)hipFree(ctx->sw_trace_fail);
   if (ctx->swpm) (void)hipFree(ctx->swpm);
   if (ctx->gauge_raw) (void)hipFree(ctx->gauge_raw);
   if (ctx->deriv) (void)hipFree(ctx->deriv);

@@ -404,7 +404,7 @@ void mul_one_pm_itau2(spinor *const p, spinor *const q, spinor *const r, spinor 
 // ------------------------------------------------------------------ clover twisted mass
 void tmlqcd_hip_update_clover(void) { ses.clover_stale(); }
 /* sw_term(g_gauge_field, kappa, c_sw) (operator/clover_term.c:88) computed in HBM; the host's sw array, if the program
- * has one (init_sw_fields), receives a copy so that host-side consumers (sw_trace, sw_deriv ...) keep working. */
+ * has one (init_sw_fields), receives a copy so that host-side consumers (the reference's sw_deriv ...) keep working. */
 void tmlqcd_hip_sw_term(const double kappa, const double c_sw) {
   tmhip_ctx *c = ses.refresh(false);
   CK(tmhip_sw_term(c, &g_gauge_field[0][0], kappa, c_sw));
@@ -480,6 +480,25 @@ int tmlqcd_hip_sw_invert_failures(void) {
   CK(tmhip_sw_invert_failures(ctx(), &n));
   return n;
 }
+/* operator/clover_det.c:115 sw_trace(ieo, mu) and :202 sw_trace_nd(ieo, mu, eps): the tr-log energies of clover_trlog_monomial.c,
+ * clovernd_trlog_monomial.c and the trlog option of the clover monomials, from the device's clover term where it belongs to the current
+ * links (the host's sw goes up first otherwise, as for sw_invert_nd).  On T-split ranks the sum over all ranks, as the reference's. */
+double sw_trace(const int ieo, const double mu) {
+  tmhip_ctx *c = ses.refresh(false);
+  if (!ses.sw_on_device) { ses.clover_uploaded = false; ses.ensure_clover(); }
+  double r = 0.0;
+  CK(tmhip_sw_trace(c, ieo, mu, g_nproc_t > 1, &r));
+  return r;
+}
+double sw_trace_nd(const int ieo, const double mu, const double eps) {
+  tmhip_ctx *c = ses.refresh(false);
+  if (!ses.sw_on_device) { ses.clover_uploaded = false; ses.ensure_clover(); }
+  double r = 0.0;
+  CK(tmhip_sw_trace_nd(c, ieo, mu, eps, g_nproc_t > 1, &r));
+  return r;
+}
+/* pivots below tiny_t met by the last sw_trace / sw_trace_nd (what the reference prints as "ifail > 0 in six_det") */
+int tmlqcd_hip_sw_trace_failures(void) { return tmhip_sw_trace_failures(ctx()); }
 /* operator/clover_deriv.c:156 sw_deriv_nd(ieo) into the device-resident swm / swp (tmlqcd_hip_swpm_zero / tmlqcd_hip_sw_all) */
 void sw_deriv_nd(const int ieo) { CK(tmhip_sw_deriv_nd(ses.refresh(false), ieo)); }
 ND_OP(Qsw_ndpsi, tmhip_Qsw_ndpsi)                /* tm_operators_nd.c:91-111 */
@@ -1055,6 +1074,37 @@ int tmlqcd_hip_rat_acc(spinor *const pf, const double *mu, const double *rmu, co
   tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
   int iters = -1;
   CK(tmhip_rat_acc(c, f, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, &iters));
+  return iters;
+}
+/* rat_monomial.c:66-139 for type CLOVERRAT, after the caller's tmlqcd_hip_sw_term + tmlqcd_hip_sw_invert(EE, 0.) (:76-78): swm / swp are
+ * zeroed, filled and folded into the derivative on the device (trlog: the monomial's flag, :134-136) */
+int tmlqcd_hip_cloverrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, const double *mu, const double *rmu, const int np, const double kappa,
+                                    const double c_sw, const int trlog, const int max_iter, const double eps_sq, const int rel_prec) {
+  tmhip_ctx *c = ses.refresh_rat("tmlqcd_hip_cloverrat_derivative");
+  tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
+  force_begin(c);
+  int iters = -1;
+  CK(tmhip_cloverrat_derivative(c, f, mu, rmu, np, kappa, c_sw, trlog, max_iter, eps_sq, rel_prec, &iters));
+  force_end(hf);
+  return iters;
+}
+/* rat_monomial.c:175-199 on Qsw_pm_psi / Qsw_plus_psi */
+int tmlqcd_hip_cloverrat_heatbath(spinor *const pf, const double *nu, const double *rnu, const int np, const int max_iter, const double eps_sq,
+                                  const int rel_prec, double *energy0) {
+  tmhip_ctx *c = ses.refresh_rat("tmlqcd_hip_cloverrat_heatbath");
+  tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_cloverrat_heatbath(c, f, nu, rnu, np, max_iter, eps_sq, rel_prec, energy0, &iters));
+  done(c, pf);
+  return iters;
+}
+/* rat_monomial.c:232-250 on Qsw_pm_psi */
+int tmlqcd_hip_cloverrat_acc(spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter, const double eps_sq,
+                             const int rel_prec, double *energy1) {
+  tmhip_ctx *c = ses.refresh_rat("tmlqcd_hip_cloverrat_acc");
+  tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
+  int iters = -1;
+  CK(tmhip_cloverrat_acc(c, f, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, &iters));
   return iters;
 }
 

@@ -353,7 +353,7 @@ int tmhip_gauge_unpack_ildg(tmhip_ctx *ctx, const void *file_bytes, int prec, un
   TMHIP_CHECK(hipGetLastError());
   ctx->gauge_raw_valid = true;
   if (ctx->g.nproc_t > 1 && tmhip_exchange_gauge_halo(ctx)) return 1;
-  ctx->sw_set = false; ctx->clover_set = false; ctx->clover_nd_set = false; ctx->clover32_set = false;      // clover blocks belong to the old links
+  ctx->sw_set = false; ctx->clover_set = false; ctx->sw_inv_ieo = -1; ctx->clover_nd_set = false; ctx->clover32_set = false;      // clover blocks belong to the old links
   if (tmhip_resort_gauge(ctx)) return 1;
   unsigned h[2];
   if (sums_fetch(ctx, h)) return 1;

@@ -304,7 +304,7 @@ int tmhip_update_gauge(tmhip_ctx *ctx, double step) {
   if (tmhip_exchange_gauge_halo(ctx)) return 1;
   if (launch_halo_backward(ctx)) return 1;                     // T-split: the backward t-links of the t = 0 sites from the neighbour's updated slice
   // clover blocks belong to the old links: tmhip_sw_term (gauge = NULL: from the resident links) / tmhip_sw_invert again
-  ctx->sw_set = false; ctx->clover_set = false; ctx->clover_nd_set = false; ctx->clover32_set = false;
+  ctx->sw_set = false; ctx->clover_set = false; ctx->sw_inv_ieo = -1; ctx->clover_nd_set = false; ctx->clover32_set = false;
   return links_changed(ctx);
 }
 
@@ -327,7 +327,7 @@ int tmhip_multi_update_gauge(int n, tmhip_ctx **ctxs, double step) {
     v2d *slab_up = c->gauge_raw + (size_t)c->V * 36, *slab_dn = slab_up + XYZ * 36;                                    // t = T, t = -1
     TMHIP_CHECK(hipMemcpyPeerAsync(slab_up, c->device, up->gauge_raw, up->device, sb, c->stream));                                            // the up neighbour's t = 0
     TMHIP_CHECK(hipMemcpyPeerAsync(slab_dn, c->device, dn->gauge_raw + (size_t)(dn->g.T - 1) * XYZ * 36, dn->device, sb, c->stream));         // the down neighbour's t = T-1
-    c->sw_set = false; c->clover_set = false; c->clover_nd_set = false; c->clover32_set = false;
+    c->sw_set = false; c->clover_set = false; c->sw_inv_ieo = -1; c->clover_nd_set = false; c->clover32_set = false;
     if (launch_halo_backward(c)) return 1;
     if (links_changed(c)) return 1;
   }

@@ -1,5 +1,5 @@
-// Rational monomials on the device: rat (monomial/rat_monomial.c, type RAT) and ndrat (monomial/ndrat_monomial.c, type NDRAT),
-// fp64, unsplit lattices.
+// Rational monomials on the device: rat (monomial/rat_monomial.c, types RAT and CLOVERRAT) and ndrat (monomial/ndrat_monomial.c, types
+// NDRAT and NDCLOVERRAT), fp64, unsplit lattices.
 //
 // The hot path is the hopping force.  ndrat_derivative calls deriv_Sb four times per shift (ndrat_monomial.c:140-160), rat_derivative
 // twice (rat_monomial.c:124-131); every call reads the same four links per site and does a read-modify-write of the same 32
@@ -17,8 +17,6 @@
 // (solve + force), heatbath and acceptance energy.
 #include "tmhip_internal.h"
 #include "mshift.h"
-
-#define RAT_MAX_PAIRS 64
 
 namespace rathip {
 
@@ -174,12 +172,14 @@ static int rat_group(const tmhip_ctx *ctx) { return ctx->opt_rat_batch < 1 ? 1 :
 
 // rat runs at twisted mass 0 (rat_monomial.c:62,156,222): the context's mu is put back on every path out
 struct RatMuZero {
-  tmhip_ctx *ctx; double mu;
-  explicit RatMuZero(tmhip_ctx *c) : ctx(c), mu(c->mu) { c->mu = 0.0; }
-  ~RatMuZero() { ctx->mu = mu; }
+  tmhip_ctx *ctx; double mu, mu3;
+  // sw: the clover operators twist their odd-odd term with mu + mu3 (rat_monomial.c:63,157,223 zero g_mu3 as well)
+  explicit RatMuZero(tmhip_ctx *c, bool sw = false) : ctx(c), mu(c->mu), mu3(c->mu3) { c->mu = 0.0; if (sw) c->mu3 = 0.0; }
+  ~RatMuZero() { ctx->mu = mu; ctx->mu3 = mu3; }
 };
 
-// sw: type NDCLOVERRAT -- the clover operators, and the four sw_spinor_eo of ndrat_monomial.c:164-175 per shift
+// sw: type NDCLOVERRAT -- the clover operators, and the four sw_spinor_eo of ndrat_monomial.c:164-175 per shift: summed per group by one
+// sw_spinor_eo_batch launch per parity (clover.hip), or with "rat_batch" 1 by the per-call kernel in the reference's order
 static int ndrat_force_body(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **chi_dn, const double *mu, const double *rmu, int np, double invmaxev,
                             bool sw = false) {
   TmhipRat *r = (TmhipRat *)ctx->rat;
@@ -207,11 +207,20 @@ static int ndrat_force_body(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **
       l1[2 * q] = chi_up[j]; k1[2 * q] = w[4]; l1[2 * q + 1] = chi_dn[j]; k1[2 * q + 1] = w[5];   // deriv_Sb(OE, ..) (:157-160)
     }
     if (tmhip_deriv_Sb_batch(ctx, TMHIP_EO, 2 * g, l0, k0, f) || tmhip_deriv_Sb_batch(ctx, TMHIP_OE, 2 * g, l1, k1, f)) return 1;
-    for (int q = 0; sw && q < g; q++) {   // :164-175: EE (w5, w2), OO (chi_up, w1), EE (w4, w3), OO (chi_dn, w0)
+    for (int q = 0; sw && G == 1 && q < g; q++) {   // :164-175: EE (w5, w2), OO (chi_up, w1), EE (w4, w3), OO (chi_dn, w0)
       const int j = hi - q;
       tmhip_field **w = r->w + 6 * q;
       if (tmhip_sw_spinor_eo(ctx, 0, w[5], w[2], f[2 * q]) || tmhip_sw_spinor_eo(ctx, 1, chi_up[j], w[1], f[2 * q])) return 1;
       if (tmhip_sw_spinor_eo(ctx, 0, w[4], w[3], f[2 * q]) || tmhip_sw_spinor_eo(ctx, 1, chi_dn[j], w[0], f[2 * q])) return 1;
+    }
+    if (sw && G > 1) {   // the same 4 g pairs: l0 / k0 / l1 / k1 are free again
+      for (int q = 0; q < g; q++) {
+        const int j = hi - q;
+        tmhip_field **w = r->w + 6 * q;
+        l0[2 * q] = w[5]; k0[2 * q] = w[2]; l0[2 * q + 1] = w[4]; k0[2 * q + 1] = w[3];
+        l1[2 * q] = chi_up[j]; k1[2 * q] = w[1]; l1[2 * q + 1] = chi_dn[j]; k1[2 * q + 1] = w[0];
+      }
+      if (tmhip_sw_spinor_eo_batch(ctx, 0, 2 * g, l0, k0, f) || tmhip_sw_spinor_eo_batch(ctx, 1, 2 * g, l1, k1, f)) return 1;
     }
   }
   return 0;
@@ -234,7 +243,8 @@ static int ndcloverrat_force_all(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_fie
   return tmhip_sw_all(ctx, nullptr, kappa, c_sw);
 }
 
-static int rat_force_body(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np) {
+// sw: type CLOVERRAT (rat_monomial.c:97-118) -- the clover operators at twisted mass 0, and the two sw_spinor_eo per shift
+static int rat_force_body(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np, bool sw = false) {
   TmhipRat *r = (TmhipRat *)ctx->rat;
   const int G = rat_group(ctx);
   if (rat_need(ctx, r->w, 3 * (G < np ? G : np))) return 1;
@@ -245,16 +255,38 @@ static int rat_force_body(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, 
     for (int q = 0; q < g; q++) {
       const int j = hi - q;
       tmhip_field *w0 = r->w[3 * q], *w2 = r->w[3 * q + 1], *w3 = r->w[3 * q + 2];
-      if (tmhip_Qtm_plus_psi(ctx, w0, chi[j])) return 1;                        // Y_o = Qp X_o (:96)
-      if (tmhip_H_eo_tm_inv_psi(ctx, w2, chi[j], TMHIP_EO, -1.0)) return 1;     // X_e (:122)
-      if (tmhip_H_eo_tm_inv_psi(ctx, w3, w0, TMHIP_EO, +1.0)) return 1;         // Y_e (:128)
+      if (sw ? tmhip_Qsw_plus_psi(ctx, w0, chi[j]) : tmhip_Qtm_plus_psi(ctx, w0, chi[j])) return 1;                                       // Y_o = Qp X_o (:96)
+      if (sw ? tmhip_H_eo_sw_inv_psi(ctx, w2, chi[j], TMHIP_EO, -1, 0.) : tmhip_H_eo_tm_inv_psi(ctx, w2, chi[j], TMHIP_EO, -1.0)) return 1;   // X_e (:100,122)
+      if (sw ? tmhip_H_eo_sw_inv_psi(ctx, w3, w0, TMHIP_EO, +1, 0.) : tmhip_H_eo_tm_inv_psi(ctx, w3, w0, TMHIP_EO, +1.0)) return 1;           // Y_e (:106,128)
       f[q] = rmu[j];                                                            // forcefactor = 1 (:81)
       l1[q] = w0; k1[q] = w2;                                                   // deriv_Sb(OE, w0, w2) (:124)
       l0[q] = w3; k0[q] = chi[j];                                               // deriv_Sb(EO, w3, X_o) (:130)
     }
     if (tmhip_deriv_Sb_batch(ctx, TMHIP_OE, g, l1, k1, f) || tmhip_deriv_Sb_batch(ctx, TMHIP_EO, g, l0, k0, f)) return 1;
+    if (sw && G == 1) {          // :113,116: EE (w2, w3), OO (w0, X_o)
+      if (tmhip_sw_spinor_eo(ctx, 0, k1[0], l0[0], f[0]) || tmhip_sw_spinor_eo(ctx, 1, l1[0], k0[0], f[0])) return 1;
+    } else if (sw) {
+      if (tmhip_sw_spinor_eo_batch(ctx, 0, g, k1, l0, f) || tmhip_sw_spinor_eo_batch(ctx, 1, g, l1, k0, f)) return 1;
+    }
   }
   return 0;
+}
+
+// the clover monomial: refused before any launch unless sw and the inverse sw_invert(EE, 0.) made are those of the current links
+static int cloverrat_prepare(tmhip_ctx *ctx, const char *who, int np) {
+  if (rat_prepare(ctx, who, np)) return 1;
+  if (!ctx->clover_set) TMHIP_FAIL("%s: sw_inv is not valid: call tmhip_sw_term and tmhip_sw_invert(EE, 0.) on the current links", who);
+  if (ctx->sw_inv_ieo != 0 || ctx->sw_inv_mu != 0.0)
+    TMHIP_FAIL("%s: sw_inv is not the one of tmhip_sw_invert(EE, 0.) (%s)", who, ctx->sw_inv_ieo < 0 ? "uploaded with tmhip_set_clover" : "other parity or mu != 0");
+  if (!ctx->gauge_raw_valid) TMHIP_FAIL("%s: no lexicographic links on the device: the clover term must come from tmhip_sw_term, not tmhip_set_clover", who);
+  return 0;
+}
+// rat_monomial.c:66-73 before the loop, :134-139 after it
+static int cloverrat_force_all(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np, double kappa, double c_sw, int trlog) {
+  if (tmhip_swpm_zero(ctx)) return 1;
+  if (rat_force_body(ctx, chi, rmu, np, true)) return 1;
+  if (trlog && tmhip_sw_deriv(ctx, 0, 0.)) return 1;
+  return tmhip_sw_all(ctx, nullptr, kappa, c_sw);
 }
 
 static int rat_check_fields(const char *who, tmhip_field *const *a, tmhip_field *const *b, int n) {
@@ -395,35 +427,71 @@ int tmhip_rat_derivative(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, cons
   return rat_force_body(ctx, r->chi_up, rmu, np);
 }
 
-int tmhip_rat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, const double *rnu, int np, int max_iter, double eps_sq, int rel_prec,
-                       double *energy0, int *iters) {
-  if (rat_prepare(ctx, "rat_heatbath", np)) return 1;
-  if (!nu || !rnu || !iters || !energy0 || !rat_eo(pf)) TMHIP_FAIL("rat_heatbath: null argument or not an fp64 one-parity field");
+static int rat_heatbath_body(tmhip_ctx *ctx, bool sw, tmhip_field *pf, const double *nu, const double *rnu, int np, int max_iter, double eps_sq, int rel_prec,
+                            double *energy0, int *iters) {
+  if (sw ? cloverrat_prepare(ctx, "cloverrat_heatbath", np) : rat_prepare(ctx, "rat_heatbath", np)) return 1;
+  if (!nu || !rnu || !iters || !energy0 || !rat_eo(pf)) TMHIP_FAIL("%s: null argument or not an fp64 one-parity field", sw ? "cloverrat_heatbath" : "rat_heatbath");
   TmhipRat *r = (TmhipRat *)ctx->rat;
   if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->w, 1)) return 1;
-  RatMuZero z(ctx);
+  RatMuZero z(ctx, sw);
   if (tmhip_square_norm(ctx, pf, ctx->Vh, 1, energy0)) return 1;                                                                      // :177
-  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, nu, np, max_iter, eps_sq, rel_prec, ctx->Vh, TMHIP_OP_QTM_PM, iters, nullptr)) return 1;   // :188
+  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, nu, np, max_iter, eps_sq, rel_prec, ctx->Vh, sw ? TMHIP_OP_QSW_PM : TMHIP_OP_QTM_PM, iters, nullptr)) return 1;   // :188
   for (int j = np - 1; j >= 0; j--) {   // pf += i rnu_j (Q - i nu_j) chi_j   (:194-199)
-    if (tmhip_Qtm_plus_psi(ctx, r->w[0], r->chi_up[j])) return 1;
+    if (sw ? tmhip_Qsw_plus_psi(ctx, r->w[0], r->chi_up[j]) : tmhip_Qtm_plus_psi(ctx, r->w[0], r->chi_up[j])) return 1;
     if (tmhip_assign_add_mul(ctx, r->w[0], r->chi_up[j], 0.0, -nu[j], ctx->Vh)) return 1;
     if (tmhip_assign_add_mul(ctx, pf, r->w[0], 0.0, rnu[j], ctx->Vh)) return 1;
   }
   return 0;
 }
 
-int tmhip_rat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
-                  double *energy1, int *iters) {
-  if (rat_prepare(ctx, "rat_acc", np)) return 1;
-  if (!mu || !rmu || !iters || !energy1 || !rat_eo(pf)) TMHIP_FAIL("rat_acc: null argument or not an fp64 one-parity field");
+int tmhip_rat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, const double *rnu, int np, int max_iter, double eps_sq, int rel_prec,
+                       double *energy0, int *iters) {
+  return rat_heatbath_body(ctx, false, pf, nu, rnu, np, max_iter, eps_sq, rel_prec, energy0, iters);
+}
+
+static int rat_acc_body(tmhip_ctx *ctx, bool sw, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                        double *energy1, int *iters) {
+  if (sw ? cloverrat_prepare(ctx, "cloverrat_acc", np) : rat_prepare(ctx, "rat_acc", np)) return 1;
+  if (!mu || !rmu || !iters || !energy1 || !rat_eo(pf)) TMHIP_FAIL("%s: null argument or not an fp64 one-parity field", sw ? "cloverrat_acc" : "rat_acc");
   TmhipRat *r = (TmhipRat *)ctx->rat;
   if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->w, 1)) return 1;
-  RatMuZero z(ctx);
-  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, mu, np, max_iter, eps_sq, rel_prec, ctx->Vh, TMHIP_OP_QTM_PM, iters, nullptr)) return 1;   // :240
+  RatMuZero z(ctx, sw);
+  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, mu, np, max_iter, eps_sq, rel_prec, ctx->Vh, sw ? TMHIP_OP_QSW_PM : TMHIP_OP_QTM_PM, iters, nullptr)) return 1;   // :240
   if (tmhip_assign(ctx, r->w[0], pf, ctx->Vh)) return 1;                                                                              // :244
   for (int j = np - 1; j >= 0; j--)
     if (tmhip_assign_add_mul_r(ctx, r->w[0], r->chi_up[j], rmu[j], ctx->Vh)) return 1;                                                // :245-248
   return tmhip_scalar_prod_r(ctx, pf, r->w[0], ctx->Vh, 1, energy1);                                                                  // :250
+}
+int tmhip_rat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                  double *energy1, int *iters) {
+  return rat_acc_body(ctx, false, pf, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, iters);
+}
+
+/* ---- type CLOVERRAT (rat_monomial.c): the same bodies on the clover operators at twisted mass 0, plus the clover part of the force ---- */
+int tmhip_cloverrat_force(tmhip_ctx *ctx, tmhip_field **chi, const double *rmu, int np, double kappa, double c_sw, int trlog) {
+  if (cloverrat_prepare(ctx, "cloverrat_force", np)) return 1;
+  if (!rmu || !chi) TMHIP_FAIL("cloverrat_force: null argument");
+  if (rat_check_fields("cloverrat_force", chi, nullptr, np)) return 1;
+  RatMuZero z(ctx, true);
+  return cloverrat_force_all(ctx, chi, rmu, np, kappa, c_sw, trlog);
+}
+int tmhip_cloverrat_derivative(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, double kappa, double c_sw, int trlog,
+                               int max_iter, double eps_sq, int rel_prec, int *iters) {
+  if (cloverrat_prepare(ctx, "cloverrat_derivative", np)) return 1;
+  if (!mu || !rmu || !iters || !rat_eo(pf)) TMHIP_FAIL("cloverrat_derivative: null argument or not an fp64 one-parity field");
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  if (rat_need(ctx, r->chi_up, np)) return 1;
+  RatMuZero z(ctx, true);
+  if (tmhip_cg_mms_tm(ctx, r->chi_up, pf, mu, np, max_iter, eps_sq, rel_prec, ctx->Vh, TMHIP_OP_QSW_PM, iters, nullptr)) return 1;   // :92
+  return cloverrat_force_all(ctx, r->chi_up, rmu, np, kappa, c_sw, trlog);
+}
+int tmhip_cloverrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, const double *rnu, int np, int max_iter, double eps_sq, int rel_prec,
+                             double *energy0, int *iters) {
+  return rat_heatbath_body(ctx, true, pf, nu, rnu, np, max_iter, eps_sq, rel_prec, energy0, iters);
+}
+int tmhip_cloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
+                        double *energy1, int *iters) {
+  return rat_acc_body(ctx, true, pf, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, iters);
 }
 
 }  // extern "C"

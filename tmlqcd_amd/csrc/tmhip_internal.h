@@ -102,6 +102,8 @@ struct tmhip_ctx {
   bool clover_set;     // sw and sw_inv both valid
   bool sw_set;         // sw valid (after tmhip_sw_term / tmhip_set_clover)
   int sw_inv_sets;     // 2 when the -mu set of sw_inv is valid as well (mu != 0), else 1
+  int sw_inv_ieo;      // parity and mu of the tmhip_sw_invert that made sw_inv; ieo = -1: unknown (tmhip_set_clover, or sw_inv dropped)
+  double sw_inv_mu;
   v2d *sw_inv_nd;      // [8][9][gs]  ((1+T)^2 + mshift)^-1 of the even sites (tmhip_sw_invert_nd), all four blocks, block 2a+b as sw_inv
   bool clover_nd_set;  // sw_inv_nd valid: dropped by whatever invalidates sw (the rule of clover_set)
   v2d *swpm;           // clover-force accumulators swm / swp (clover_leaf.c:141-172): [2][4][9][V], site = parity * Vh + e/o index
@@ -110,6 +112,8 @@ struct tmhip_ctx {
   bool gauge_copy_current;   // the stencil's gauge copy was sorted from the links now in gauge_raw
   unsigned *io_sums;   // SciDAC checksum words A, B accumulated by the ILDG pack / unpack kernels (ildg.hip)
   int *sw_fail;        // device counter of near-singular pivots met by tmhip_sw_invert
+  int *sw_trace_fail;  // the same for tmhip_sw_trace / tmhip_sw_trace_nd (six_det's ifail), and its value after the last call
+  int sw_trace_fails;
   v2f *sw32, *sw_inv32; bool clover32_set;
   v2f *gauge32;        // fp32 twin of the gauge copy (g_gauge_field_copy_32), built on first use
   bool gauge32_set;
@@ -285,6 +289,7 @@ int tmhip_launch_hopping_dot32(tmhip_ctx *ctx, int ieo, v2f *out, const v2f *in,
                                const v2f *cw = nullptr, int chained = 0);
 bool tmhip_fused_dot32_ok(const tmhip_ctx *ctx);
 int tmhip_reduce_finish(tmhip_ctx *ctx, int nblocks, int parallel, double *out);
+#define RAT_MAX_PAIRS 64   // pairs per launch of the batched force kernels (rational.hip deriv_Sb_batch, clover.hip sw_spinor_eo_batch)
 // After a host-visible synchronisation of a T-split rank: non-zero (with a message) when a bounded device-side wait for the
 // neighbours' faces gave up ("flag_timeout_ms") or the communicator reports an asynchronous error, i.e. the result just
 // synchronised cannot be trusted.  Reported once per occurrence -- the error word is cleared, the next call starts clean.

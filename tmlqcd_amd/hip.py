@@ -191,6 +191,12 @@ def load_library():
         "tmhip_rat_derivative": [vp, vp, pd, pd, i, i, d, i, C.POINTER(i)],
         "tmhip_rat_heatbath": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
         "tmhip_rat_acc": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
+        "tmhip_sw_spinor_eo_batch": [vp, i, i, C.POINTER(vp), C.POINTER(vp), pd],
+        "tmhip_sw_trace": [vp, i, d, i, pd], "tmhip_sw_trace_nd": [vp, i, d, d, i, pd], "tmhip_sw_trace_failures": [vp],
+        "tmhip_cloverrat_force": [vp, C.POINTER(vp), pd, i, d, d, i],
+        "tmhip_cloverrat_derivative": [vp, vp, pd, pd, i, d, d, i, i, d, i, C.POINTER(i)],
+        "tmhip_cloverrat_heatbath": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
+        "tmhip_cloverrat_acc": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -392,8 +398,37 @@ class Lattice:
     def sw_spinor_eo(self, ieo, kk, ll, fac):
         _ck(self.lib.tmhip_sw_spinor_eo(self.h, ieo, kk.h, ll.h, fac), "sw_spinor_eo")
 
+    def sw_spinor_eo_batch(self, ieo, kks, lls, facs):
+        """sum_j sw_spinor_eo(ieo, kks[j], lls[j], facs[j]) in one kernel launch (1 <= len <= 64 pairs): swm / swp move once."""
+        n = len(kks)
+        if len(lls) != n or len(facs) != n:
+            raise TmHipError("sw_spinor_eo_batch: kks, lls and facs must have the same length")
+        m = max(n, 1)
+        _ck(self.lib.tmhip_sw_spinor_eo_batch(self.h, ieo, n, (C.c_void_p * m)(*[f.h for f in kks]), (C.c_void_p * m)(*[f.h for f in lls]),
+                                              (C.c_double * m)(*facs)), "sw_spinor_eo_batch")
+
     def sw_deriv(self, ieo, mu):
         _ck(self.lib.tmhip_sw_deriv(self.h, ieo, mu), "sw_deriv")
+
+    # --- tr-log energies on the device's clover term (operator/clover_det.c) ---
+    def sw_trace(self, ieo, mu, global_sum=None):
+        """clover_det.c:115: sum over the sites of parity ieo and both chiralities of log |det(1 + T + i mu)|^2.  global_sum: add the
+        shares of the T-split ranks (default: whenever the lattice is split, as the reference's MPI_Allreduce)."""
+        out = C.c_double()
+        g = self.nproc_t > 1 if global_sum is None else bool(global_sum)
+        _ck(self.lib.tmhip_sw_trace(self.h, ieo, mu, int(g), C.byref(out)), "sw_trace")
+        return out.value
+
+    def sw_trace_nd(self, ieo, mu, eps, global_sum=None):
+        """clover_det.c:202: sum over the sites of parity ieo of log(Re det_0 Re det_1), det_i = det((1 + T_i)^2 + mu^2 - eps^2)."""
+        out = C.c_double()
+        g = self.nproc_t > 1 if global_sum is None else bool(global_sum)
+        _ck(self.lib.tmhip_sw_trace_nd(self.h, ieo, mu, eps, int(g), C.byref(out)), "sw_trace_nd")
+        return out.value
+
+    def sw_trace_failures(self):
+        """pivots below the reference's tiny_t met by the last sw_trace / sw_trace_nd (six_det's ifail)"""
+        return self.lib.tmhip_sw_trace_failures(self.h)
 
     def sw_all(self, kappa, c_sw, gauge=None):
         _ck(self.lib.tmhip_sw_all(self.h, _hp(gauge) if gauge is not None else None, kappa, c_sw), "sw_all")
@@ -893,6 +928,31 @@ class Lattice:
         (m, n), (r, _) = self._da(mu), self._da(rmu)
         it, e = C.c_int(), C.c_double()
         _ck(self.lib.tmhip_rat_acc(self.h, pf.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "rat_acc")
+        return e.value, it.value
+
+    def cloverrat_force(self, chi, rmu, kappa, c_sw, trlog):
+        """rat_monomial.c:66-73, :95-139 for CLOVERRAT given the solutions chi = [chi_j ...]; needs sw_term + sw_invert(EE, 0.) on the
+        current links; runs at twisted mass 0."""
+        r, n = self._da(rmu)
+        _ck(self.lib.tmhip_cloverrat_force(self.h, (C.c_void_p * max(n, 1))(*[f.h for f in chi]), r, n, kappa, c_sw, int(trlog)), "cloverrat_force")
+
+    def cloverrat_derivative(self, pf, mu, rmu, kappa, c_sw, trlog, max_iter, eps_sq, rel_prec):
+        """solve with Qsw_pm_psi + force; returns the solver's iteration count."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it = C.c_int()
+        _ck(self.lib.tmhip_cloverrat_derivative(self.h, pf.h, m, r, n, kappa, c_sw, int(trlog), max_iter, eps_sq, rel_prec, C.byref(it)), "cloverrat_derivative")
+        return it.value
+
+    def cloverrat_heatbath(self, pf, nu, rnu, max_iter, eps_sq, rel_prec):
+        (m, n), (r, _) = self._da(nu), self._da(rnu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_cloverrat_heatbath(self.h, pf.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "cloverrat_heatbath")
+        return e.value, it.value
+
+    def cloverrat_acc(self, pf, mu, rmu, max_iter, eps_sq, rel_prec):
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it, e = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_cloverrat_acc(self.h, pf.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "cloverrat_acc")
         return e.value, it.value
 
     # --- multi-GPU --------------------------------------------------------

@@ -52,6 +52,10 @@ RULES = [
     (r"^void ndsw_mix_kernel<(\d+)>", "clover doublet site-local", 2),
     (r"^(void )?sw_invert_nd_kernel", "sw_invert_nd", 2),
     (r"^(void )?sw_deriv_nd_kernel", "sw_deriv_nd", 2),
+    # the batched clover outer products of the rational forces: one wave per block n of swm / swp, 36 doubles of accumulators
+    (r"^(void )?sw_spinor_eo_batch_kernel", "batched sw_spinor_eo", 3),
+    # the tr-log energies: a fully unrolled 6x6 factorisation per site in registers
+    (r"^void sw_trace_kernel<(true|false)>", "sw_trace / sw_trace_nd", 2),
 ]
 
 
