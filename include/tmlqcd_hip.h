@@ -570,8 +570,21 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  * reader, tmhip_update_gauge, tmhip_multi_update_gauge, tmhip_sw_term / tmhip_sw_all with host links, tmhip_resort_gauge.
  * Molecular-dynamics updates need this: restoresu3 normalises rows 0 and 1 of exp(step P) without orthogonalising them, so
  * updated links leave SU(3) by 1e-7 after two steps with |step P| = 2.5 and by 1e-13 after some hundred ordinary ones.
- * The measurement is one launch and one synchronisation per such call; with the default 18-real read nothing is added. */
+ * The measurement is one launch and one synchronisation per such call; with the default 18-real read nothing is added.
+ * "gauge_pack" -1 (automatic, default) | 0 | 1 changes what is read but never a result: the staged 256-thread fp64 stencil with a
+ * twisted-mass epilogue on an unsplit lattice reads a packed twin of the gauge copy -- two rows of every link, the fp32 residual of the
+ * third row against its rebuild conj(row_a x row_b), and one byte that says which cyclic rotation of the rows was stored: 121 bytes
+ * instead of 144.  The twin is built on the context's stream by the first such launch after the links changed (one kernel, a 12-byte copy
+ * and one synchronisation per change of the links) and every link is verified there bit for bit with the stencil's own rebuild
+ * function; a field in which some link has no exact rotation is read in full, silently.  0: never; 1: as automatic.  "gauge_recon" 12 takes
+ * precedence.  "gauge_pack_rot" -1 (default: the first rotation that verifies) | 0 | 1 | 2 (try that rotation first; for tests). */
 int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value);
+/* The packed twin of the gauge copy ("gauge_pack"), built now if it is stale: out = {1 if the stencil may read it else 0, links stored on
+ * rotation 0, 1, 2, links without an exact rotation}.  tmhip_gauge_pack_build_ms: device time of the last build. */
+int tmhip_gauge_pack_stats(tmhip_ctx *ctx, long long out[5]);
+int tmhip_gauge_pack_build_ms(tmhip_ctx *ctx, double *ms);
+/* stencil launches of this context that read the packed copy so far */
+int tmhip_gauge_pack_launches(tmhip_ctx *ctx, long long *n);
 /* max |row2 - conj(row0 x row1)| over all links of the resident gauge field */
 int tmhip_gauge_su3_deviation(tmhip_ctx *ctx, double *maxdev);
 

@@ -158,6 +158,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
   ctx->opt_nd_fused = 1; ctx->invmaxev = 1.0;
   ctx->opt_rat_batch = 12;
   ctx->gauge_recon_dev = -1.0;
+  ctx->opt_gauge_pack = -1; ctx->opt_gauge_pack_rot = -1;
   TMHIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   {  // boundary pipeline (pack, exchange, boundary kernels) must not queue behind the interior kernel's blocks
     int lo = 0, hi = 0;
@@ -225,6 +226,8 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   for (int i = 0; i < 2; i++) tmhip_field_free(ctx, ctx->scratch32[i]);
   for (int i = 0; i < 4; i++) tmhip_field_free(ctx, ctx->sf32[i]);
   if (ctx->gauge32) (void)hipFree(ctx->gauge32);
+  if (ctx->gpack_mem) (void)hipFree(ctx->gpack_mem);
+  if (ctx->gpack_ev_made) { (void)hipEventDestroy(ctx->gpack_ev[0]); (void)hipEventDestroy(ctx->gpack_ev[1]); }
   if (ctx->sw) (void)hipFree(ctx->sw);
   if (ctx->sw_inv) (void)hipFree(ctx->sw_inv);
   if (ctx->sw_inv_nd) (void)hipFree(ctx->sw_inv_nd);
@@ -320,6 +323,8 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
     ctx->opt_recon = value == 12 ? 12 : 0;
     if (ctx->opt_recon == 12) return tmhip_check_gauge_recon(ctx);
   }
+  else if (!strcmp(name, "gauge_pack")) { if (value < -1 || value > 1) TMHIP_FAIL("gauge_pack must be -1 (automatic), 0 (never read the packed links) or 1"); ctx->opt_gauge_pack = value; }
+  else if (!strcmp(name, "gauge_pack_rot")) { if (value < -1 || value > 2) TMHIP_FAIL("gauge_pack_rot must be -1 (the first rotation that verifies) or the rotation to try first, 0, 1 or 2"); ctx->opt_gauge_pack_rot = value; ctx->gpack_state = 0; }
   else if (!strcmp(name, "hopsplit")) { if (value < -1 || value > 1) TMHIP_FAIL("hopsplit must be -1 (automatic), 0 or 1"); ctx->opt_hopsplit = value; }
   else if (!strcmp(name, "lds32")) { if (value < 0 || value > 1) TMHIP_FAIL("lds32 must be 0 or 1"); ctx->opt_stg32 = value; }
   else if (!strcmp(name, "lds")) { if (value < 0 || value > 1) TMHIP_FAIL("lds must be 0 (gather kernel) or 1 (per-wave LDS staging of the own-site spinors)"); ctx->opt_stg = value; }

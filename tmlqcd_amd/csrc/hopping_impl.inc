@@ -11,6 +11,7 @@ struct HopArgs {
   const ET *in;
   const ET *p;
   const ET *gauge;  // already offset to the parity of the output sites
+  TmhipGaugePack pack;   // GAUX 15 instances: the packed twin of the gauge copy, offset to the parity like `gauge`
   const ET *halo_up, *halo_dn;
   const ET *cw;      // clover epilogues: sw (6 blocks) or sw_inv (8 blocks) of the output sites, [blk][9][gs]
   const ET *dotv;   // EPI_TM_SUB_G5_DOT: field whose real scalar product with the output is accumulated
@@ -122,9 +123,12 @@ template <int D, bool HALO, bool NT, int GAUX = -1, int SM = 0>
 __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ in, int ns, int j, int j2,
                                         const ET *__restrict__ halo, int face,
                                         const ET *__restrict__ g, size_t gs, int i, V2T ka,
-                                        const unsigned char *lds = nullptr, int jl = 0) {
-  (void)j2;
+                                        const unsigned char *lds = nullptr, int jl = 0, const TmhipGaugePack &pk = TmhipGaugePack{}) {
+  (void)j2; (void)pk;
   V2T pa[3], pb[3];
+  V2T ra[3], rb[3], rc[3]; v4f r4 = {}; v2f r2 = {}; int rot = 0;   // GAUX 15: the two stored rows, the rebuilt one, its residual, the selector
+  (void)ra; (void)rb; (void)rc; (void)r4; (void)r2; (void)rot;
+  static_assert(GAUX != 15 || !HALO, "the packed link read has no boundary form");
   if (HALO) {
     V2T h[6];
     ld6_fresh(h, halo, (size_t)face, j, 0);   // written by the exchange while this kernel may already have been running: never from L1
@@ -144,6 +148,27 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
     } else {
       ld6<false>(s, in, (size_t)ns, j, 0); ld6<false>(s + 6, in, (size_t)ns, j, 1);
     }
+    if constexpr (GAUX == 15) {
+      // Packed link read: the link's eleven loads are requested right behind the spinor's, and the spinor is projected (48 -> 24
+      // registers) while they are in flight; the rebuild and the selects below then have the room they need.  Left to itself
+      // the compiler asks for the link first and rebuilds it with the whole neighbour spinor outstanding: 176 registers for EPI_TM_SUB_G5
+      // when the instance is compiled with __launch_bounds__(256, 1) (tools/micro/regprobe.hip), scratch under the bound of three waves.
+      __builtin_amdgcn_sched_barrier(0);
+      // (scalar plane base + one 32-bit lane offset per load: a direction's planes of one parity span < 4 GiB, pack_setup)
+      const unsigned int ugs = (unsigned int)gs, ui = (unsigned int)i;
+      const char *prow = reinterpret_cast<const char *>(pk.rows + (size_t)D * 6 * gs);
+  #pragma unroll
+      for (int e = 0; e < 3; e++) {
+        ra[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)e * ugs + ui) * 16u)));
+        rb[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)(3 + e) * ugs + ui) * 16u)));
+      }
+      const v4f *p4 = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(pk.res4 + (size_t)D * gs) + (size_t)(ui * 16u));
+      const v2f *p2 = reinterpret_cast<const v2f *>(reinterpret_cast<const char *>(pk.res2 + (size_t)D * gs) + (size_t)(ui * 8u));
+      const unsigned char *ps = pk.sel + (size_t)D * gs + (size_t)ui;
+      r4 = NT ? __builtin_nontemporal_load(p4) : *p4;
+      r2 = NT ? __builtin_nontemporal_load(p2) : *p2;
+      rot = NT ? __builtin_nontemporal_load(ps) : *ps;
+    }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const V2T s0 = s[c], s1 = s[3 + c], s2 = s[6 + c], s3 = s[9 + c];
@@ -155,6 +180,12 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
       if (D == 5) { pa[c] = s0 - s3; pb[c] = s1 + s2; }                                           // hopping.h:639,644
       if (D == 6) { pa[c] = V2T{s0.x - s2.y, s0.y + s2.x}; pb[c] = V2T{s1.x + s3.y, s1.y - s3.x}; }  // s0+i s2, s1-i s3
       if (D == 7) { pa[c] = V2T{s0.x + s2.y, s0.y - s2.x}; pb[c] = V2T{s1.x - s3.y, s1.y + s3.x}; }  // s0-i s2, s1+i s3
+    }
+    if constexpr (GAUX == 15) {
+      // (the projected half-spinor is pinned here: an empty statement the compiler cannot move the additions past)
+#pragma unroll
+      for (int c = 0; c < 3; c++) asm volatile("" : "+v"(pa[c]), "+v"(pb[c]));
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
   const ET *gd = g + (size_t)D * 9 * gs + i;
@@ -177,7 +208,19 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
     }
   }
 #else
-  if constexpr (GAUX == 12) {
+  if constexpr (GAUX == 15) {
+    // packed read ("gauge_pack"): two rows, the fp32 residual of the third and the selector byte -- 121 bytes; the third row is
+    // rebuilt by the function that verified it bit for bit when the copy was built (gauge_pack_kernel, md_update.hip), and the rows
+    // go back to their places by selects on the selector: every load is uniform across the wave, the result is the stored link
+    const float rs[6] = {r4.x, r4.y, r4.z, r4.w, r2.x, r2.y};
+    tmhip_su3_row_rebuild(ra, rb, rs, rc);
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+      u[e] = rot == 0 ? ra[e] : (rot == 1 ? rc[e] : rb[e]);
+      u[3 + e] = rot == 0 ? rb[e] : (rot == 1 ? ra[e] : rc[e]);
+      u[6 + e] = rot == 0 ? rc[e] : (rot == 1 ? rb[e] : ra[e]);
+    }
+  } else if constexpr (GAUX == 12) {
     // opt-in 12-real storage read ("gauge_recon" = 12): rows 0 and 1 are loaded, row 2 = conj(row0 x row1) is rebuilt
     // in registers -- exact for SU(3) links up to rounding; the third of the link bytes is never fetched.
 #pragma unroll
@@ -222,6 +265,9 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
     if (D == 6) { acc[6 + c] += V2T{a.y, -a.x}; acc[9 + c] += V2T{-b.y, b.x}; }   // s2 -= i a ; s3 += i b
     if (D == 7) { acc[6 + c] += V2T{-a.y, a.x}; acc[9 + c] += V2T{b.y, -b.x}; }   // s2 += i a ; s3 -= i b
   }
+  // (packed link read: nothing of the next hop is requested before this one is added up -- as in the other instances, there by the
+  // compiler's own choice -- so that the registers of the rebuild are free again)
+  if constexpr (GAUX == 15) __builtin_amdgcn_sched_barrier(0);
 }
 
 // TSKIP (T-split rank, DESIGN.md section 7): the launch still covers ALL sites of the rank, but the one hop that crosses the rank
@@ -301,6 +347,7 @@ __device__ __forceinline__ void faces_count_in(const HopArgs &a, unsigned int or
 template <int EPI, int TSKIP, bool NTIO, int BS, int MINW, int GAUX = -1, int STG = 0>
 __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
   static_assert(STG == 0 || (STG == 64 && HOP_SITES == 1), "the LDS-staged variant: one site per thread, whole blocks");
+  static_assert(GAUX != 15 || (STG == 64 && TSKIP == 0), "the packed link read exists in the staged kernel of unsplit lattices only");
   // gauge links: used once per call -> non-temporal (0.19 -> 0.16 ms at 32^4).  GAUX = -2 (small unsplit lattices, 64-thread blocks, the
   // gauge copy under ~200 MB: launch_variant): NOT marked streaming, so the links stay in the 256 MiB Infinity Cache from one call to
   // the next: 12^4 10.5 -> 8.8, 16^4 15.3 -> 12.1, 20^4 25.3 -> 21.9 us per launch; beyond the cache it is a loss (24^4 53 -> 62,
@@ -401,14 +448,14 @@ __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
     const int i0 = i - lid;
     stage_put(st, lid, in, (size_t)a.ns, i);
     __builtin_amdgcn_wave_barrier();
-    if (do_tp) hop_dir<0, false, NT, GAUX>(acc, in, a.ns, jtp, 0, nullptr, 0, g, a.gs, i, ka0);
-    if (do_tm) hop_dir<1, false, NT, GAUX>(acc, in, a.ns, jtm, 0, nullptr, 0, g, a.gs, i, ka0);
-    hop_dir<2, false, NT, GAUX>(acc, in, a.ns, jxp, 0, nullptr, 0, g, a.gs, i, ka1);
-    hop_dir<3, false, NT, GAUX>(acc, in, a.ns, jxm, 0, nullptr, 0, g, a.gs, i, ka1);
-    hop_dir<4, false, NT, GAUX, 2>(acc, in, a.ns, jyp, 0, nullptr, 0, g, a.gs, i, ka2, st, jyp - i0);
-    hop_dir<5, false, NT, GAUX, 2>(acc, in, a.ns, jym, 0, nullptr, 0, g, a.gs, i, ka2, st, jym - i0);
-    hop_dir<6, false, NT, GAUX, 1>(acc, in, a.ns, jzp, 0, nullptr, 0, g, a.gs, i, ka3, st, jzp - i0);
-    hop_dir<7, false, NT, GAUX, 1>(acc, in, a.ns, jzm, 0, nullptr, 0, g, a.gs, i, ka3, st, jzm - i0);
+    if (do_tp) hop_dir<0, false, NT, GAUX>(acc, in, a.ns, jtp, 0, nullptr, 0, g, a.gs, i, ka0, nullptr, 0, a.pack);
+    if (do_tm) hop_dir<1, false, NT, GAUX>(acc, in, a.ns, jtm, 0, nullptr, 0, g, a.gs, i, ka0, nullptr, 0, a.pack);
+    hop_dir<2, false, NT, GAUX>(acc, in, a.ns, jxp, 0, nullptr, 0, g, a.gs, i, ka1, nullptr, 0, a.pack);
+    hop_dir<3, false, NT, GAUX>(acc, in, a.ns, jxm, 0, nullptr, 0, g, a.gs, i, ka1, nullptr, 0, a.pack);
+    hop_dir<4, false, NT, GAUX, 2>(acc, in, a.ns, jyp, 0, nullptr, 0, g, a.gs, i, ka2, st, jyp - i0, a.pack);
+    hop_dir<5, false, NT, GAUX, 2>(acc, in, a.ns, jym, 0, nullptr, 0, g, a.gs, i, ka2, st, jym - i0, a.pack);
+    hop_dir<6, false, NT, GAUX, 1>(acc, in, a.ns, jzp, 0, nullptr, 0, g, a.gs, i, ka3, st, jzp - i0, a.pack);
+    hop_dir<7, false, NT, GAUX, 1>(acc, in, a.ns, jzm, 0, nullptr, 0, g, a.gs, i, ka3, st, jzm - i0, a.pack);
   } else {
     if (do_tp) hop_dir<0, false, NT, GAUX>(acc, in, a.ns, jtp, 0, nullptr, 0, g, a.gs, i, ka0);
     if (do_tm) hop_dir<1, false, NT, GAUX>(acc, in, a.ns, jtm, 0, nullptr, 0, g, a.gs, i, ka0);
@@ -890,7 +937,7 @@ __global__ __launch_bounds__(256) void hop_exterior_kernel(const HopArgs a) {
 }
 
 #ifndef HOP_KERNELS_ONLY   /* (tools/micro/regprobe.hip instantiates single kernels to look at their register budget) */
-struct HopLaunch { int block; int minw; int xcd; int occ; int tgrp; int recon; int *grid_out /* receives the number of waves = partial sums */; int stg; int split4; int gcache; };
+struct HopLaunch { int block; int minw; int xcd; int occ; int tgrp; int recon; int *grid_out /* receives the number of waves = partial sums */; int stg; int split4; int gcache; int pack /* a.pack is valid: the staged twisted-mass instances read the packed links */; long long *pack_count /* counts the launches that do */; };
 // Block order ("xcd" option): 0 none (hardware round-robin), 1 one contiguous chunk per XCD, 2 = default: automatic choice
 // between the tile order and the slab order, 3 slab order, 4 tile order.
 //   tile order: contiguous chunk of time-slices per XCD, inside it t runs fastest over a small group of slices, so +-t AND
@@ -979,6 +1026,11 @@ static void launch_variant(const HopArgs &a, hipStream_t st, const HopLaunch &o)
     if (stg_ok(a, o)) {
       if constexpr (TM_EPI) {
         if (o.recon == 12) { launch_one<EPI, TSKIP, true, 256, 3, 12, 64>(a, st, o); return; }
+#ifndef HOP_GAUGE_PACKED
+        if constexpr (!TSKIP) {
+          if (o.pack) { launch_one<EPI, 0, true, 256, 3, 15, 64>(a, st, o); if (o.pack_count) ++*o.pack_count; return; }   // bit-exact 121-byte link read ("gauge_pack")
+        }
+#endif
       }
       // __launch_bounds__(256, 3) keeps the twisted-mass instances at the gather kernel's three waves per SIMD (146-164 VGPRs, no
       // scratch; left alone the compiler takes 190 for the plain store epilogue); the clover epilogues would spill under that bound
@@ -1077,7 +1129,27 @@ static void fill_args(HopArgs &a, tmhip_ctx *ctx, int ieo, ET *out, const ET *in
 }
 
 static HopLaunch launch_opts(const tmhip_ctx *ctx, int block) {
-  return HopLaunch{block, ctx->opt_minw, ctx->opt_xcd, HOP_CTX_OCC(ctx), ctx->opt_tgrp, ctx->opt_recon, nullptr, HOP_CTX_STG(ctx), use_split4(ctx), ctx->opt_gauge_cache};
+  return HopLaunch{block, ctx->opt_minw, ctx->opt_xcd, HOP_CTX_OCC(ctx), ctx->opt_tgrp, ctx->opt_recon, nullptr, HOP_CTX_STG(ctx), use_split4(ctx), ctx->opt_gauge_cache, 0, nullptr};
+}
+
+// "gauge_pack": where this launch would take the staged twisted-mass instance of an unsplit fp64 lattice, make sure the packed twin
+// of the gauge copy is current (built on ctx->stream by the first such launch after the links changed) and hand it to the kernel
+// if every link of the field has an exact rotation; otherwise the launch reads the 18-real copy as before.
+static int pack_setup(tmhip_ctx *ctx, HopArgs &a, HopLaunch &o, int ieo, int epi, bool split) {
+#ifndef HOP_GAUGE_PACKED
+  const bool clover = epi == EPI_CLOVER_INV || epi == EPI_CLOVER || HOP_EPI_CLOVER_G5(epi);
+  if (split || clover || ctx->opt_gauge_pack == 0 || o.recon == 12 || o.split4 || !stg_ok(a, o)) return 0;
+  if ((size_t)ctx->gs * 96 >= ((size_t)1 << 32)) return 0;   // the kernel addresses a direction's planes with 32-bit lane offsets
+  bool usable = false;
+  if (tmhip_gauge_pack_prepare(ctx, &usable)) return 1;
+  if (!usable) return 0;
+  const size_t off = (size_t)(ieo ? 1 : 0) * 8 * ctx->gs;
+  a.pack.rows = ctx->gpack.rows + off * 6; a.pack.res4 = ctx->gpack.res4 + off; a.pack.res2 = ctx->gpack.res2 + off; a.pack.sel = ctx->gpack.sel + off;
+  o.pack = 1; o.pack_count = &ctx->gpack_launches;
+#else
+  (void)ctx; (void)a; (void)o; (void)ieo; (void)epi; (void)split;
+#endif
+  return 0;
 }
 
 // (a kernel that may wait at its head: at most 2 x 32 blocks)
@@ -1134,8 +1206,9 @@ int launch_hopping(tmhip_ctx *ctx, int ieo, ET *out, const ET *in, const ET *p, 
   fill_args(a, ctx, ieo, out, in, p, cre, cim);
   a.cw = cw;
   if ((epi == EPI_CLOVER_INV || epi == EPI_CLOVER_G5 || epi == EPI_CLOVER) && !cw) TMHIP_FAIL("clover operator called before tmhip_set_clover");
-  const HopLaunch o = launch_opts(ctx, tmhip_hop_block(ctx));
+  HopLaunch o = launch_opts(ctx, tmhip_hop_block(ctx));
   const bool split = ctx->g.nproc_t > 1 || ctx->loopback;
+  if (pack_setup(ctx, a, o, ieo, epi, split)) return 1;
   if (!split) launch_epi<0>(a, epi, ctx->stream, o);
   else if (launch_split(ctx, a, epi, o, comm)) return 1;
   TMHIP_CHECK(hipGetLastError());
@@ -1182,6 +1255,7 @@ int launch_hopping_dot(tmhip_ctx *ctx, int ieo, ET *out, const ET *in, const ET 
   }
   int nwave = 0;
   o.grid_out = &nwave;
+  if (pack_setup(ctx, a, o, ieo, epi, split)) return 1;
   if (!split) launch_epi<0>(a, epi, ctx->stream, o);
   else if (launch_split(ctx, a, epi, o, HOP_COMM | ((chained & 1) ? HOP_CHAINED : 0) | ((chained & 2) ? HOP_FEED : 0))) return 1;   // chained: bit 0 HOP_CHAINED, bit 1 HOP_FEED
   *npartials = (split ? ctx->last_ext_partials : 0) + nwave;

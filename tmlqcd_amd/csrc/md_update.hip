@@ -249,6 +249,7 @@ static int links_changed(tmhip_ctx *ctx) {
   ctx->gauge_copy_current = true;
   ctx->gauge32_set = false;       // the fp32 twin is rebuilt lazily from the new links
   ctx->gauge_recon_dev = -1.0;
+  ctx->gpack_state = 0;           // ... and so is the packed twin, by the first stencil launch that can read it
   // "gauge_recon" 12 holds for SU(3) links only, and restoresu3 (rows 0 and 1 normalised, not orthogonalised) lets the updated links drift
   // away from it: the guard measures the new copy before any stencil can read 12 reals of it and gives the option up above 1e-13.  One
   // launch and one synchronisation per change of the links under the option; nothing with the default 18-real read.
@@ -262,7 +263,140 @@ int tmhip_resort_gauge(tmhip_ctx *ctx) {
   return links_changed(ctx);
 }
 
+// ---- the packed twin of the gauge copy (TmhipGaugePack, tmhip_internal.h) ----
+// One thread per link slot of ctx->gauge (blockIdx.y = parity * 8 + direction).  The rotations r = first, first + 1, first + 2 (mod 3) are
+// tried in turn: rows r and r + 1 are kept, the residual of row r + 2 against its rebuild from them is taken in double and rounded
+// to fp32, the row is rebuilt WITH that residual by the function the stencil uses and compared with the stored row as 64-bit
+// integers.  The first rotation that reproduces all six reals is stored; a link without one is counted in count[2] and the field
+// is then not read packed at all.  count[0..1]: links on rotation 1 / 2 (one atomic per wave that has any).
+__global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__ g, v2d *__restrict__ rows, v4f *__restrict__ res4, v2f *__restrict__ res2,
+                                                         unsigned char *__restrict__ sel, int gs, int Vh, int first, unsigned int *count) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  int chosen = 0;   // 0..2: rotation, 3: none, -1: no link
+  if (i >= Vh) chosen = -1;
+  else {
+    const size_t slot = (size_t)blockIdx.y * gs + i;
+    const v2d *gp = g + (size_t)blockIdx.y * 9 * gs + i;
+    v2d u[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) u[e] = gp[(size_t)e * gs];
+    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    v2d ka[3], kb[3];
+    float kr[6];
+    int kept = 0;
+    chosen = 3;
+    for (int n = 0; n < 3 && chosen == 3; n++) {
+      const int r = (first + n) % 3;
+      v2d a[3], b[3], c[3], w[3], t[3];
+      float rs[6];
+#pragma unroll
+      for (int e = 0; e < 3; e++) {   // selects, not indexed registers
+        a[e] = r == 0 ? u[e] : (r == 1 ? u[3 + e] : u[6 + e]);
+        b[e] = r == 0 ? u[3 + e] : (r == 1 ? u[6 + e] : u[e]);
+        c[e] = r == 0 ? u[6 + e] : (r == 1 ? u[e] : u[3 + e]);
+      }
+      tmhip_su3_row_rebuild(a, b, zero, w);
+#pragma unroll
+      for (int e = 0; e < 3; e++) { rs[2 * e] = (float)(c[e].x - w[e].x); rs[2 * e + 1] = (float)(c[e].y - w[e].y); }
+      tmhip_su3_row_rebuild(a, b, rs, t);
+      bool same = true;
+#pragma unroll
+      for (int e = 0; e < 3; e++)
+        same = same && __double_as_longlong(t[e].x) == __double_as_longlong(c[e].x) && __double_as_longlong(t[e].y) == __double_as_longlong(c[e].y);
+      if (same || n == 2) {   // (a link without an exact rotation still gets defined planes)
+#pragma unroll
+        for (int e = 0; e < 3; e++) { ka[e] = a[e]; kb[e] = b[e]; }
+#pragma unroll
+        for (int e = 0; e < 6; e++) kr[e] = rs[e];
+        kept = r;
+        if (same) chosen = r;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+      rows[((size_t)blockIdx.y * 6 + e) * gs + i] = ka[e];
+      rows[((size_t)blockIdx.y * 6 + 3 + e) * gs + i] = kb[e];
+    }
+    res4[slot] = v4f{kr[0], kr[1], kr[2], kr[3]};
+    res2[slot] = v2f{kr[4], kr[5]};
+    sel[slot] = (unsigned char)kept;
+  }
+#pragma unroll
+  for (int v = 1; v <= 3; v++) {
+    const unsigned long long m = __ballot(chosen == v);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(count + (v - 1), (unsigned int)__popcll(m));
+  }
+}
+
+int tmhip_gauge_pack_prepare(tmhip_ctx *ctx, bool *usable) {
+  *usable = false;
+  if (!ctx->gauge_set) return 0;
+  if (ctx->gpack_unavailable) return 0;
+  if (ctx->gpack_state == 0) {
+    const size_t n = (size_t)16 * ctx->gs;   // link slots, padding included
+    if (!ctx->gpack_mem) {
+      if (!ctx->gpack_ev_made) {
+        TMHIP_CHECK(hipEventCreate(&ctx->gpack_ev[0]));
+        if (hipEventCreate(&ctx->gpack_ev[1]) != hipSuccess) { (void)hipEventDestroy(ctx->gpack_ev[0]); TMHIP_FAIL("tmhip_gauge_pack_prepare: hipEventCreate failed"); }
+        ctx->gpack_ev_made = true;
+      }
+      // (out of memory is no error: the field is simply not read packed, and the allocation is not tried again)
+      if (hipMalloc(&ctx->gpack_mem, n * 121 + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->gpack_mem = nullptr; ctx->gpack_unavailable = true;
+        for (int k = 0; k < 4; k++) ctx->gpack_stats[k] = 0;
+        return 0;
+      }
+      unsigned char *m = (unsigned char *)ctx->gpack_mem;
+      ctx->gpack.rows = (const v2d *)m;
+      ctx->gpack.res4 = (const v4f *)(m + n * 96);
+      ctx->gpack.res2 = (const v2f *)(m + n * 112);
+      ctx->gpack.sel = m + n * 120;
+      ctx->gpack_count = (unsigned int *)(m + (n * 121 + 15) / 16 * 16);
+    }
+    TMHIP_CHECK(hipMemsetAsync(ctx->gpack_count, 0, 3 * sizeof(unsigned int), ctx->stream));
+    TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[0], ctx->stream));
+    const int first = ctx->opt_gauge_pack_rot < 0 ? 0 : ctx->opt_gauge_pack_rot;
+    hipLaunchKernelGGL(gauge_pack_kernel, dim3((ctx->Vh + 255) / 256, 16), dim3(256), 0, ctx->stream, (const v2d *)ctx->gauge, (v2d *)ctx->gpack.rows,
+                       (v4f *)ctx->gpack.res4, (v2f *)ctx->gpack.res2, (unsigned char *)ctx->gpack.sel, ctx->gs, ctx->Vh, first, ctx->gpack_count);
+    TMHIP_CHECK(hipGetLastError());
+    TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[1], ctx->stream));
+    unsigned int h[3] = {0, 0, 0};
+    TMHIP_CHECK(hipMemcpyAsync(h, ctx->gpack_count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    TMHIP_CHECK(hipEventElapsedTime(&ctx->gpack_build_ms, ctx->gpack_ev[0], ctx->gpack_ev[1]));
+    ctx->gpack_stats[1] = h[0]; ctx->gpack_stats[2] = h[1]; ctx->gpack_stats[3] = h[2];
+    ctx->gpack_stats[0] = (long long)16 * ctx->Vh - h[0] - h[1] - h[2];
+    ctx->gpack_state = h[2] == 0 ? 1 : 2;
+  }
+  *usable = ctx->gpack_state == 1;
+  return 0;
+}
+
 extern "C" {
+
+int tmhip_gauge_pack_stats(tmhip_ctx *ctx, long long out[5]) {
+  if (!out) TMHIP_FAIL("tmhip_gauge_pack_stats: null argument");
+  if (!ctx->gauge_set) TMHIP_FAIL("tmhip_gauge_pack_stats called before tmhip_set_gauge");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  bool usable = false;
+  if (tmhip_gauge_pack_prepare(ctx, &usable)) return 1;
+  out[0] = usable ? 1 : 0;
+  for (int k = 0; k < 4; k++) out[1 + k] = ctx->gpack_stats[k];
+  return 0;
+}
+
+int tmhip_gauge_pack_launches(tmhip_ctx *ctx, long long *n) {
+  if (!n) TMHIP_FAIL("tmhip_gauge_pack_launches: null argument");
+  *n = ctx->gpack_launches;
+  return 0;
+}
+
+int tmhip_gauge_pack_build_ms(tmhip_ctx *ctx, double *ms) {
+  if (!ms) TMHIP_FAIL("tmhip_gauge_pack_build_ms: null argument");
+  *ms = (double)ctx->gpack_build_ms;
+  return 0;
+}
 
 int tmhip_momenta_upload(tmhip_ctx *ctx, const void *host) {
   if (!host) TMHIP_FAIL("tmhip_momenta_upload: null argument");

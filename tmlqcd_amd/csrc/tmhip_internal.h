@@ -82,6 +82,37 @@ struct TmhipDirect {
   unsigned long long sum_seq;   // reductions done so far (the same number on every rank)
 };
 
+// Packed links of the fp64 stencil: two rows of a link (six v2d planes), the fp32 residual of the third (a v4f and a v2f plane) and
+// one byte that says which cyclic rotation of the rows was stored: 96 + 24 + 1 = 121 bytes instead of 144.  Selector r: rows r and
+// r + 1 (mod 3) are kept, row r + 2 is tmhip_su3_row_rebuild of them.
+struct TmhipGaugePack {
+  const v2d *rows;            // [8][6][gs]: kept row a (elements 0..2), kept row b (elements 0..2)
+  const v4f *res4;            // [8][gs]: residual of the rebuilt row, elements 0 and 1 (re, im, re, im)
+  const v2f *res2;            // [8][gs]: ... element 2
+  const unsigned char *sel;   // [8][gs]
+};
+// The third row of an SU(3) link from the other two, c = conj(a x b) + residual: ONE sequence of operations for the kernel that builds
+// the packed copy (and verifies every link bit for bit) and for the stencil that reads it.  Explicit fma() calls, no contraction, the
+// residual added last in an addition of its own: both callers round exactly alike.
+__device__ __forceinline__ void tmhip_su3_row_rebuild(const v2d (&a)[3], const v2d (&b)[3], const float (&res)[6], v2d (&c)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const int i = (k + 1) % 3, j = (k + 2) % 3;   // (a x b)_k = a_i b_j - a_j b_i
+    double re = a[i].x * b[j].x;
+    re = fma(-a[i].y, b[j].y, re);
+    re = fma(-a[j].x, b[i].x, re);
+    re = fma(a[j].y, b[i].y, re);
+    double im = a[i].x * b[j].y;
+    im = fma(a[i].y, b[j].x, im);
+    im = fma(-a[j].x, b[i].y, im);
+    im = fma(-a[j].y, b[i].x, im);
+    const double rr = (double)res[2 * k], ri = (double)res[2 * k + 1];
+    c[k].x = re + rr;
+    c[k].y = -im + ri;
+  }
+}
+
 struct tmhip_ctx {
   tmhip_geom g;
   int device;
@@ -177,6 +208,19 @@ struct tmhip_ctx {
   int opt_rat_batch;                  // shifts per deriv_Sb_batch launch of the rat / ndrat force
   void *mms; int mms_active_shifts;   // single-flavour multi-shift CG (mms.hip): work fields and solver state
   double gauge_recon_dev;   // max |U_row2 - conj(row0 x row1)| over all links of the resident gauge field (-1: not measured)
+  // packed twin of the gauge copy (121 bytes per link, bit-exact: DESIGN.md section 6, "packed gauge read"), built on first use like gauge32
+  void *gpack_mem;          // one allocation behind the four plane sets of gpack
+  TmhipGaugePack gpack;     // device planes, [2 parities][8 directions][..][gs] each (null until the first build)
+  int gpack_state;          // 0 stale, 1 built and every link has an exact rotation (the stencil may read it), 2 built, some link has none
+  bool gpack_unavailable;   // the allocation failed once: the field is read in full from then on, no further attempt
+  bool gpack_ev_made;       // gpack_ev exist
+  long long gpack_launches; // stencil launches that read the packed copy so far (tmhip_gauge_pack_launches: what the tests look at)
+  long long gpack_stats[4]; // links stored on rotation 0, 1, 2 / links without an exact rotation, of the last build
+  unsigned int *gpack_count;// device: [0..1] links on rotation 1, 2, [2] links without one
+  int opt_gauge_pack;       // -1 automatic (default) and 1: read the packed copy where it is valid and the instance exists; 0: never
+  int opt_gauge_pack_rot;   // -1: the first rotation that verifies; 0..2: try that one first (tests)
+  float gpack_build_ms;     // device time of the last build (HIP events)
+  hipEvent_t gpack_ev[2];
 };
 
 // N is a site count of a one-parity field: 0 is a legal empty loop in the reference (linalg/*.c), anything outside [0, V/2] would
@@ -295,6 +339,8 @@ int tmhip_reduce_finish(tmhip_ctx *ctx, int nblocks, int parallel, double *out);
 // synchronised cannot be trusted.  Reported once per occurrence -- the error word is cleared, the next call starts clean.
 int tmhip_check_async_error(tmhip_ctx *ctx);
 extern "C" int tmhip_check_gauge_recon(tmhip_ctx *ctx);   // context.hip: unitarity guard of the gauge_recon=12 option
+// md_update.hip: builds the packed twin of the gauge copy on ctx->stream if it is stale ("gauge_pack"); *usable: the stencil may read it
+int tmhip_gauge_pack_prepare(tmhip_ctx *ctx, bool *usable);
 // The polling loop of every device-resident solver.  enqueue(k) puts iteration number k on ctx->stream; the host enqueues `batch`
 // of them, reads `done` and `err` of the solver's device state into result_host[2..3], synchronises, and polls after every single
 // iteration once err <= near_below (within 10^3 of the target: no stencil is enqueued far past convergence; exactness never depends

@@ -102,6 +102,8 @@ def load_library():
         "tmhip_read_gauge_field": [vp, C.c_char_p, i, i, vp, C.POINTER(GaugeInfo)],
         "tmhip_write_gauge_field": [vp, C.c_char_p, i, C.c_char_p, C.POINTER(C.c_uint)],
         "tmhip_gauge_su3_deviation": [vp, pd],
+        "tmhip_gauge_pack_stats": [vp, C.POINTER(C.c_longlong)], "tmhip_gauge_pack_build_ms": [vp, pd],
+        "tmhip_gauge_pack_launches": [vp, C.POINTER(C.c_longlong)],
         "tmhip_derivative_zero": [vp],
         "tmhip_swpm_zero": [vp], "tmhip_sw_spinor_eo": [vp, i, vp, vp, d], "tmhip_sw_deriv": [vp, i, d],
         "tmhip_sw_all": [vp, vp, d, d], "tmhip_get_swpm": [vp, vp, vp],
@@ -337,6 +339,25 @@ class Lattice:
         """max |row2 - conj(row0 x row1)| over the resident links (what the gauge_recon=12 guard looks at)."""
         out = C.c_double()
         _ck(self.lib.tmhip_gauge_su3_deviation(self.h, C.byref(out)), "tmhip_gauge_su3_deviation")
+        return out.value
+
+    def gauge_pack_stats(self):
+        """(packed 0/1, links on rotation 0, 1, 2, links without an exact rotation) of the packed twin of the gauge copy
+        (option gauge_pack); builds it if it is stale."""
+        out = (C.c_longlong * 5)()
+        _ck(self.lib.tmhip_gauge_pack_stats(self.h, out), "tmhip_gauge_pack_stats")
+        return tuple(int(v) for v in out)
+
+    def gauge_pack_launches(self):
+        """stencil launches that read the packed copy so far"""
+        out = C.c_longlong()
+        _ck(self.lib.tmhip_gauge_pack_launches(self.h, C.byref(out)), "tmhip_gauge_pack_launches")
+        return out.value
+
+    def gauge_pack_build_ms(self):
+        """device time of the last build of the packed twin, in ms"""
+        out = C.c_double()
+        _ck(self.lib.tmhip_gauge_pack_build_ms(self.h, C.byref(out)), "tmhip_gauge_pack_build_ms")
         return out.value
 
     def sync(self):

@@ -26,6 +26,8 @@ CLOVER_EPI = {5, 6, 7, 10, 11, 13}
 RULES = [
     # fp64, large lattices: the LDS-staged kernel, __launch_bounds__(256, 3) for the twisted-mass epilogues, (256, 1) for the clover ones
     (r"^void hop64::hop_kernel<(\d+), ([013]), true, 256, (3|1), -1, 64>", "fp64 staged"),
+    # ... and its packed link read (GAUX 15, "gauge_pack"): twisted-mass epilogues of unsplit lattices, three waves per SIMD, no scratch
+    (r"^void hop64::hop_kernel<(\d+), 0, true, 256, 3, 15, 64>", "fp64 staged packed"),
     # the shifted residual epilogue of the multi-shift CG (EPI 12, mms.hip) in the gather kernel: one more field than its sibling EPI 9
     # (190 VGPRs, two waves per SIMD); its staged form above keeps three
     (r"^void hop64::hop_kernel<12, 0, true, (64|256), 1, (-1|-2), 0>", "fp64 gather shifted res", 2),
