@@ -121,10 +121,24 @@ void diff(spinor *const Q, const spinor *const R, const spinor *const S, const i
 void assign(spinor *const R, spinor *const S, const int N);
 void add(spinor *const Q, const spinor *const R, const spinor *const S, const int N);   /* linalg/add.h */
 void mul_r(spinor *const R, const double c, spinor *const S, const int N);               /* linalg/mul_r.h */
+_Complex double scalar_prod(const spinor *const S, const spinor *const R, const int N, const int parallel);   /* linalg/scalar_prod.h: sum conj(S) R */
+void assign_diff_mul(spinor *const S, spinor *const R, const _Complex double c, const int N);                /* linalg/assign_diff_mul.h: S -= c R */
+void mul(spinor *const R, const _Complex double c, spinor *const S, const int N);                            /* linalg/mul.h: R = c S, R may be S */
 
 /* ---- solver/cg_her.h ------------------------------------------------------- */
 int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec,
            const int N, matrix_mult f);
+
+/* ---- solver/chrono_guess.h: the chronological guess of the det / cloverdet / detratio / cloverdetratio monomials -----------
+ * chrono_guess: trial = the Galerkin solution of f x = phi in the span of the _n stored vectors v[index_array[0 .. _n-1]]; the stored
+ * vectors older than the newest one are orthogonalised against it in place.  _N <= 0, or _n = 0 (an empty list: the reference reads
+ * index_array[-1] there), gives trial = 0; _N > 20 ends the program with a message (the reference's buffers hold 20).  f from the
+ * table of cg_her runs on the device with the batched kernels (option csg_batch); any other f is called through host pointers, the
+ * linalg around it one call at a time in coherent mode.  Returns 0.
+ * chrono_add_solution: stores trial / |trial| in the list and advances index_array and *_n as the reference does. */
+int chrono_guess(spinor *const trial, spinor *const phi, spinor **const v, int index_array[], const int _N, const int _n, const int V,
+                 matrix_mult f);
+void chrono_add_solution(spinor *const trial, spinor **const v, int index_array[], const int _N, int *_n, const int V);
 
 /* ---- operator/clovertm_operators.h ----------------------- */
 /* The host keeps computing `sw` / `sw_inv` with its own sw_term / sw_invert (operator.c:329-330,364); the library

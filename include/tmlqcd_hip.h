@@ -134,6 +134,20 @@ int tmhip_diff(tmhip_ctx *ctx, tmhip_field *Q, tmhip_field *R, tmhip_field *S, i
 int tmhip_assign(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, int N);                                       /* assign.c:42 */
 int tmhip_add(tmhip_ctx *ctx, tmhip_field *Q, tmhip_field *R, tmhip_field *S, int N);                          /* linalg/add.c:45   Q = R + S */
 int tmhip_mul_r(tmhip_ctx *ctx, tmhip_field *R, double c, tmhip_field *S, int N);                              /* linalg/mul_r.c:40 R = c S */
+/* Complex singles: out = {Re, Im} of sum conj(S) R (linalg/scalar_prod_body.c:52), both parts from one launch; R -= c S; R = c S (R may be S).
+ * They are the one-field instances of the batched kernels below, so a batched value carries the bits of its single. */
+int tmhip_scalar_prod(tmhip_ctx *ctx, tmhip_field *S, tmhip_field *R, int N, int parallel, double out[2]);     /* linalg/scalar_prod.c */
+int tmhip_assign_diff_mul(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, double c_re, double c_im, int N);    /* linalg/assign_diff_mul.c */
+int tmhip_mul(tmhip_ctx *ctx, tmhip_field *R, double c_re, double c_im, tmhip_field *S, int N);                /* linalg/mul.c */
+/* Batched forms, 1 <= n <= TMHIP_CSG_MAX fields, unsplit fp64 EO fields; coefficients and results are (re, im) pairs.
+ *   multi_scalar_prod     out[i] = <S_i, R> in one pass over R (groups of six S_i per launch), ONE final-reduction launch, one copy to
+ *                         the host and one synchronisation; rank-local: a context that sums over ranks refuses it
+ *   multi_assign_diff_mul R_i -= c_i S for all i, S read once per group
+ *   lincomb               P = sum_i c_i V_i, every element added up from i = n-1 down to 0 (chrono_guess.c:144-153) */
+#define TMHIP_CSG_MAX 20
+int tmhip_multi_scalar_prod(tmhip_ctx *ctx, int n, tmhip_field *const *S, tmhip_field *R, int N, double *out /* 2n */);
+int tmhip_multi_assign_diff_mul(tmhip_ctx *ctx, int n, tmhip_field *const *R, tmhip_field *S, const double *c /* 2n */, int N);
+int tmhip_lincomb(tmhip_ctx *ctx, tmhip_field *P, int n, tmhip_field *const *V, const double *c /* 2n */, int N);
 
 /* ---- solver --------------------------------------------------------------- */
 enum { TMHIP_OP_QTM_PM = 0, TMHIP_OP_QTM_PLUS = 1, TMHIP_OP_QTM_MINUS = 2, TMHIP_OP_MTM_PLUS = 3, TMHIP_OP_MTM_MINUS = 4,
@@ -145,6 +159,24 @@ enum { TMHIP_OP_QTM_PM = 0, TMHIP_OP_QTM_PLUS = 1, TMHIP_OP_QTM_MINUS = 2, TMHIP
  * err after each iteration, up to hist_len entries. */
 int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec,
                  int N, int op, int *iters, double *res_hist, int hist_len);
+
+/* ---- chronological solver guess (solver/chrono_guess.c) ---------------------
+ * tmhip_chrono_guess: the starting vector of A x = phi from the last n normalised solutions v[0..n-1] (oldest first, i.e. already in
+ * index_array order), A = operator `op` (TMHIP_OP_*), N sites of EO fields:
+ *   1. every older vector is made orthogonal to the newest one, v_i -= <v_{n-1}, v_i> v_{n-1} for i < n-1 (the caller's v_i change);
+ *   2. G[i][j] = <v_i, A v_j> is computed for i <= j and mirrored, G[j][i] = conj(G[i][j]); b[j] = <v_j, phi>;
+ *   3. G y = b is solved on the host by a row-wise LU factorisation with partial pivoting;
+ *   4. trial = sum_i y_i v_i.
+ * n = 0 or N = 0 gives trial = 0; n > TMHIP_CSG_MAX is an error.  G_out (2 n n doubles, row-major) and b_out (2 n doubles, the
+ * projections of step 2) may be NULL.  Option "csg_batch" 1 (default): steps 1, 2 and 4 run on the batched kernels (n + 2 host
+ * synchronisations instead of (n-1) + n(n+1)/2 + n); 0, a rank that sums over ranks, or N != VOLUME/2: the same steps as a sequence of
+ * the complex singles with the cross-rank sum.
+ * tmhip_chrono_add_solution: slot = trial / |trial| (square_norm over all ranks, then mul_r). */
+int tmhip_chrono_guess(tmhip_ctx *ctx, tmhip_field *trial, tmhip_field *phi, tmhip_field *const *v, int n, int op, int N,
+                       double *G_out, double *b_out);
+int tmhip_chrono_add_solution(tmhip_ctx *ctx, tmhip_field *slot, tmhip_field *trial, int N);
+/* step 3 alone, on the host: G (2 n n doubles, row-major, overwritten with its factors) y = b, y returned in b (2 n doubles); 1 <= n <= TMHIP_CSG_MAX */
+int tmhip_csg_solve(int n, double *G, double *b);
 
 /* ---- non-degenerate twisted-mass doublet (operator/tm_operators_nd.c) ------------------------
  * A doublet is a pair of EO fields (strange = up, charm = dn).  Unsplit lattices only: a context with nproc_t > 1 refuses every
@@ -549,6 +581,8 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                tmhip_sw_spinor_eo kernel in the reference's order
  *   "gauge_global_sums" 0 (default) | 1: tmhip_measure_plaquette / _gauge_action / _rectangles return the rank's own share (0: the reference's value
  *                before its MPI_Allreduce) or the sum over the ranks of a T split (1: its return value; needs the communicator, like parallel = 1)
+ *   "csg_batch" 1 (default) | 0: tmhip_chrono_guess on the batched kernels (tmhip_multi_scalar_prod, tmhip_multi_assign_diff_mul, tmhip_lincomb)
+ *                or as a sequence of the complex singles
  *   "cg_sync" 1: host-side scalars as in the reference loop;  "cg_batch" n: iterations enqueued between two polls of `done`
  *   "gauge_cache" -1 (automatic) / 0 / 1: the 64-thread stencil launches of small unsplit lattices, and the stencil launches of a T-split rank,
  *                  load the links with (0) or without (1) the streaming hint; automatic = without while the gauge copy is <= 200 MB (it then

@@ -157,6 +157,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
   ctx->opt_stg = 1; ctx->opt_stg32 = 0; ctx->opt_hopsplit = -1; ctx->opt_occ32 = 0; ctx->opt_recon = 0; ctx->opt_swall_order = 2; ctx->opt_swterm_order = 1; ctx->opt_gauge_cache = -1;
   ctx->opt_nd_fused = 1; ctx->invmaxev = 1.0;
   ctx->opt_rat_batch = 12;
+  ctx->opt_csg_batch = 1;
   ctx->gauge_recon_dev = -1.0;
   ctx->opt_gauge_pack = -1; ctx->opt_gauge_pack_rot = -1;
   TMHIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
@@ -243,6 +244,9 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   if (ctx->force_recv) (void)hipFree(ctx->force_recv);
   if (ctx->sw_ins) (void)hipFree(ctx->sw_ins);
   if (ctx->io_sums) (void)hipFree(ctx->io_sums);
+  if (ctx->csg_partials) (void)hipFree(ctx->csg_partials);
+  if (ctx->csg_res_dev) (void)hipFree(ctx->csg_res_dev);
+  if (ctx->csg_res_host) (void)hipHostFree(ctx->csg_res_host);
   if (ctx->swpm_halo_send) (void)hipFree(ctx->swpm_halo_send);
   if (ctx->swpm_halo_recv) (void)hipFree(ctx->swpm_halo_recv);
   tmhip_direct_destroy(ctx);
@@ -332,6 +336,7 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "cg_sync")) ctx->opt_cg_sync = value;
   else if (!strcmp(name, "nd_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_fused must be 0 (two single-flavour stencils + a mixing pass) or 1 (doublet stencil)"); ctx->opt_nd_fused = value; }
   else if (!strcmp(name, "rat_batch")) ctx->opt_rat_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
+  else if (!strcmp(name, "csg_batch")) { if (value < 0 || value > 1) TMHIP_FAIL("csg_batch must be 0 (complex singles) or 1 (batched kernels)"); ctx->opt_csg_batch = value; }
   else if (!strcmp(name, "gauge_global_sums")) { if (value < 0 || value > 1) TMHIP_FAIL("gauge_global_sums must be 0 (the rank's share) or 1 (summed over the ranks)"); ctx->opt_gauge_global_sums = value; }
   else if (!strcmp(name, "cg_batch")) ctx->opt_cg_batch = value > 0 ? value : 1;
   else TMHIP_FAIL("unknown option %s", name);

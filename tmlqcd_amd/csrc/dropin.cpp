@@ -268,6 +268,17 @@ template <class F> inline void team_once(F body) {
 #pragma omp barrier
 }
 
+int chrono_guess_generic(spinor *const trial, spinor *const phi, spinor **const v, const int *index_array, const int n, const int V, matrix_mult f);
+// the operators the device-resident solvers know by address (TMHIP_OP_*), -1 for any other function
+int op_of(matrix_mult f) {
+  if (f == &Qtm_pm_psi) return TMHIP_OP_QTM_PM;
+  if (f == &Qtm_plus_psi) return TMHIP_OP_QTM_PLUS;
+  if (f == &Qtm_minus_psi) return TMHIP_OP_QTM_MINUS;
+  if (f == &Mtm_plus_psi) return TMHIP_OP_MTM_PLUS;
+  if (f == &Mtm_minus_psi) return TMHIP_OP_MTM_MINUS;
+  if (f == &Qsw_pm_psi) return TMHIP_OP_QSW_PM;
+  return -1;
+}
 int cg_her_generic(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f);
 int cg_mms_tm_generic(spinor **const P, spinor *const Q, tmlqcd_solver_params *sp, double *cgmms_reached_prec);
 
@@ -716,6 +727,22 @@ void add(spinor *const Q, const spinor *const R, const spinor *const S, const in
 void mul_r(spinor *const R, const double cc, spinor *const S, const int N) {
   lin_op(N, rd(S), wr(R), none(), [&](Ctx c, Fld fs, Fld fr, Fld, int n) { CK(tmhip_mul_r(c, fr, cc, fs, n)); });
 }
+/* linalg/scalar_prod.c: sum conj(S) R */
+_Complex double scalar_prod(const spinor *const S, const spinor *const R, const int N, const int parallel) {
+  double re = 0, im = 0;
+  lin_op(N, rd(S), rd(R), none(), [&](Ctx c, Fld fs, Fld fr, Fld, int n) { double r[2]; CK(tmhip_scalar_prod(c, fs, fr, n, parallel, r)); re += r[0]; im += r[1]; });
+  _Complex double res;
+  __real__ res = re; __imag__ res = im;
+  return res;
+}
+/* linalg/assign_diff_mul.c: S -= c R */
+void assign_diff_mul(spinor *const S, spinor *const R, const _Complex double cc, const int N) {
+  lin_op(N, rw(S), rd(R), none(), [&](Ctx c, Fld fs, Fld fr, Fld, int n) { CK(tmhip_assign_diff_mul(c, fs, fr, __real__ cc, __imag__ cc, n)); });
+}
+/* linalg/mul.c: R = c S */
+void mul(spinor *const R, const _Complex double cc, spinor *const S, const int N) {
+  lin_op(N, rd(S), wr(R), none(), [&](Ctx c, Fld fs, Fld fr, Fld, int n) { CK(tmhip_mul(c, fr, __real__ cc, __imag__ cc, fs, n)); });
+}
 /* linalg/assign.c:42-46 */
 void assign(spinor *const R, spinor *const S, const int N) {
   lin_op(N, rd(S), wr(R), none(), [&](Ctx c, Fld fs, Fld fr, Fld, int n) { CK(tmhip_assign(c, fr, fs, n)); });
@@ -828,13 +855,7 @@ void assign_to_64(spinor *const R, spinor32 *const S, const int N) {   /* linalg
  * drop-in linalg in COHERENT mode, which is correct for an arbitrary host-side f (cg_her_generic, at the end of this file). */
 int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N,
            matrix_mult f) {
-  int op = -1;
-  if (f == &Qtm_pm_psi) op = TMHIP_OP_QTM_PM;
-  else if (f == &Qtm_plus_psi) op = TMHIP_OP_QTM_PLUS;
-  else if (f == &Qtm_minus_psi) op = TMHIP_OP_QTM_MINUS;
-  else if (f == &Mtm_plus_psi) op = TMHIP_OP_MTM_PLUS;
-  else if (f == &Mtm_minus_psi) op = TMHIP_OP_MTM_MINUS;
-  else if (f == &Qsw_pm_psi) op = TMHIP_OP_QSW_PM;
+  const int op = op_of(f);
   if (op < 0 || N != VOLUME / 2) return cg_her_generic(P, Q, max_iter, eps_sq, rel_prec, N, f);
   tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? ses.refresh_clover() : ses.refresh(true);
   tmhip_field *fq = in(c, Q, TMHIP_FIELD_EO), *fp = in(c, P, TMHIP_FIELD_EO);
@@ -842,6 +863,42 @@ int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, 
   CK(tmhip_cg_her(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, &iters, nullptr, 0));
   done(c, P);          // coherent mode: the solution is on the host when we return; resident mode: after tmlqcd_hip_sync_to_host
   return iters;
+}
+
+/* solver/chrono_guess.c:82-172.  The stored solutions, trial and phi are ordinary mirrors; the orthogonalisation changes the stored
+ * vectors older than the newest one, so those are handed back as written. */
+int chrono_guess(spinor *const trial, spinor *const phi, spinor **const v, int index_array[], const int _N, const int _n, const int V,
+                 matrix_mult f) {
+  if (_N > 20) die("chrono_guess: a list of more than 20 vectors is not supported (the reference's buffers hold max_N = 20)");
+  if (_N <= 0 || _n <= 0) {   /* :168, and the empty list */
+    if (V > 0) lin_op(V, wr(trial), none(), none(), [&](Ctx c, Fld ft, Fld, Fld, int) { CK(tmhip_field_zero(c, ft)); });
+    return 0;
+  }
+  if (_n > _N) die("chrono_guess: more vectors than the list holds");
+  const int op = op_of(f);
+  if (op < 0 || V != VOLUME / 2) return chrono_guess_generic(trial, phi, v, index_array, _n, V, f);
+  tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? ses.refresh_clover() : ses.refresh(true);
+  tmhip_field *fv[20];
+  for (int i = 0; i < _n; i++) fv[i] = in(c, v[index_array[i]], TMHIP_FIELD_EO);
+  tmhip_field *fphi = in(c, phi, TMHIP_FIELD_EO), *ft = out(c, trial, TMHIP_FIELD_EO);
+  CK(tmhip_chrono_guess(c, ft, fphi, fv, _n, op, V, nullptr, nullptr));
+  for (int i = 0; i < _n - 1; i++) done(c, v[index_array[i]]);
+  done(c, trial);
+  return 0;
+}
+/* solver/chrono_guess.c:43-75 */
+void chrono_add_solution(spinor *const trial, spinor **const v, int index_array[], const int _N, int *_n, const int V) {
+  if (_N <= 0) return;
+  if (*_n < _N) {
+    index_array[*_n] = *_n;
+    *_n += 1;
+  } else {
+    for (int i = 1; i < _N; i++) index_array[i - 1] = index_array[i];   /* the oldest slot is written next */
+    index_array[_N - 1] = _N > 1 ? (index_array[_N - 2] + 1) % _N : 0;   /* (a list of one vector: the reference reads index_array[-1], and anything % 1 is 0) */
+  }
+  const int slot = index_array[(*_n < _N ? *_n : _N) - 1];
+  const double norm = sqrt(square_norm(trial, V, 1));
+  mul_r(v[slot], 1 / norm, trial, V);
 }
 
 /* solver/mixed_cg_her.c:65-202 with f = Qtm_pm_psi: fp32 inner CG + fp64 defect correction, all in HBM */
@@ -1259,6 +1316,35 @@ int cg_her_generic(spinor *const P, spinor *const Q, const int max_iter, double 
   free(blk);
   if (iteration > max_iter) return -1;
   return iteration;
+}
+
+// chrono_guess with an operator the library does not know: f runs on host arrays, so everything around it runs in coherent mode, one
+// drop-in linalg call at a time (the residency rules of cg_her_generic).  The steps are those of tmhip_chrono_guess and the small
+// system is solved by the same function (tmhip_csg_solve).
+int chrono_guess_generic(spinor *const trial, spinor *const phi, spinor **const v, const int *index_array, const int n, const int V, matrix_mult f) {
+  CoherentScope coherent;
+  spinor *newest = v[index_array[n - 1]];
+  for (int i = n - 2; i >= 0; i--) assign_diff_mul(v[index_array[i]], newest, scalar_prod(newest, v[index_array[i]], V, 1), V);
+  double G[2 * 20 * 20], b[2 * 20];
+  for (int j = 0; j < n; j++) {
+    f(trial, v[index_array[j]]);
+    for (int i = 0; i <= j; i++) {
+      const _Complex double s = scalar_prod(v[index_array[i]], trial, V, 1);
+      G[2 * (i * n + j)] = __real__ s; G[2 * (i * n + j) + 1] = __imag__ s;
+      G[2 * (j * n + i)] = __real__ s; G[2 * (j * n + i) + 1] = i == j ? __imag__ s : -__imag__ s;
+    }
+    const _Complex double s = scalar_prod(v[index_array[j]], phi, V, 1);
+    b[2 * j] = __real__ s; b[2 * j + 1] = __imag__ s;
+  }
+  CK(tmhip_csg_solve(n, G, b));
+  _Complex double y;
+  __real__ y = b[2 * (n - 1)]; __imag__ y = b[2 * (n - 1) + 1];
+  mul(trial, y, newest, V);
+  for (int i = n - 2; i >= 0; i--) {
+    __real__ y = b[2 * i]; __imag__ y = b[2 * i + 1];
+    assign_add_mul(trial, v[index_array[i]], y, V);
+  }
+  return 0;
 }
 
 // generic path of cg_mms_tm: the reference loop verbatim on host-visible fields (assign_mul_add_mul_r inlined: the host program need not have it)

@@ -12,6 +12,7 @@
 // pairwise tree used here has an error bound of O(log N) ulp, tighter than the
 // sequential one, so no compensation is needed to stay within 1e-13 relative.
 #include "tmhip_internal.h"
+#include <type_traits>
 
 __device__ __forceinline__ void block_reduce_store(double v, double *partials) {
   __shared__ double wsum[LA_BS / 64];
@@ -146,26 +147,180 @@ __global__ __launch_bounds__(LA_BS) void diag_kernel(v2d *L, const v2d *K, const
   }
 }
 
+// ---- complex products and updates, one field or a group of G fields against one (the chronological guess, chrono.hip)
+// The per-thread accumulation, the sum over the block and the final pass are one piece of code for every G, and the four products of
+// a term are rounded one by one: a value of a group carries the bits of the same product taken alone, and <S, S> has an imaginary
+// part of exactly zero.  (This file is built with -ffp-contract=fast, which fuses across statements whatever a pragma says; a product
+// that has passed through an empty asm statement is a value the compiler cannot fuse into the addition behind it.)
+#define CSG_GROUP 8       // fields per launch of the update and combination kernels
+#define CSG_DOT_GROUP 6   // ... of the product kernel: two accumulators per field, and seven fields no longer fit the 64 registers of eight waves per SIMD
+template <int G> struct CsgFields { v2d *f[G]; double c[2 * G]; };
+
+__device__ __forceinline__ void cdot_add(double &re, double &im, const v2d a, const v2d b) {   // += conj(a) b   (scalar_prod_body.c:52)
+  double rr = a.x * b.x, ii = a.y * b.y, ri = a.x * b.y, ir = a.y * b.x;
+  asm("" : "+v"(rr), "+v"(ii), "+v"(ri), "+v"(ir));
+  re += rr + ii;
+  im += ri - ir;
+}
+
+// out[2g], out[2g+1] = Re, Im <S_g, R>: block sums of value k at partials[k * 12 * gridDim.x + ...], the layout of block_reduce_store per value
+template <int G>
+__global__ __launch_bounds__(LA_BS, 8) void csg_dot_kernel(const CsgFields<G> S, const v2d *R, int ns, int N, double *partials) {
+  __shared__ double wsum[2 * G][LA_BS / 64];
+  const size_t off = (size_t)blockIdx.y * ns;
+  const v2d *r = R + off;
+  double re[G], im[G];
+#pragma unroll
+  for (int g = 0; g < G; g++) re[g] = im[g] = 0.0;
+  const int base = blockIdx.x * LA_BS * LA_UNROLL + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < LA_UNROLL; u++) {
+    const int i = base + u * LA_BS;
+    if (i < N) {
+      const v2d b = r[i];
+#pragma unroll
+      for (int g = 0; g < G; g++) cdot_add(re[g], im[g], S.f[g][off + i], b);
+    }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int g = 0; g < G; g++) {
+    const double a = tmhip_wave_sum(re[g]), b = tmhip_wave_sum(im[g]);
+    if (lane == 0) { wsum[2 * g][w] = a; wsum[2 * g + 1][w] = b; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * G) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < LA_BS / 64; k++) s += wsum[threadIdx.x][k];
+    partials[(size_t)threadIdx.x * 12 * gridDim.x + blockIdx.y * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// value k = blockIdx.x: the fixed-order pass of reduce_final_kernel over its n block sums
+__global__ __launch_bounds__(256) void reduce_final_multi_kernel(const double *__restrict__ partials, int n, double *out) {
+  __shared__ double sm[256];
+  const double *p = partials + (size_t)blockIdx.x * n;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += p[i];
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = sm[0];
+}
+
+// R_g -= c_g S   (linalg/assign_diff_mul.c)
+template <int G>
+__global__ __launch_bounds__(LA_BS, 8) void csg_axpy_kernel(const CsgFields<G> R, const v2d *S, int ns, int N) {
+  const size_t off = (size_t)blockIdx.y * ns;
+  const v2d *s = S + off;
+  const int base = blockIdx.x * LA_BS * LA_UNROLL + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < LA_UNROLL; u++) {
+    const int i = base + u * LA_BS;
+    if (i < N) {
+      const v2d b = s[i];
+#pragma unroll
+      for (int g = 0; g < G; g++) {
+        const double cre = R.c[2 * g], cim = R.c[2 * g + 1];
+        const v2d a = R.f[g][off + i];
+        R.f[g][off + i] = v2d{a.x - cre * b.x + cim * b.y, a.y - cre * b.y - cim * b.x};
+      }
+    }
+  }
+}
+
+// P = [P +] c_{G-1} V_{G-1} + ... + c_0 V_0, added in that order   (linalg/mul.c, then linalg/assign_add_mul.c per field); element-wise: P may be a V_g
+template <int G, bool ACC>
+__global__ __launch_bounds__(LA_BS, 8) void csg_lincomb_kernel(v2d *P, const CsgFields<G> V, int ns, int N) {
+  const size_t off = (size_t)blockIdx.y * ns;
+  v2d *p = P + off;
+  const int base = blockIdx.x * LA_BS * LA_UNROLL + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < LA_UNROLL; u++) {
+    const int i = base + u * LA_BS;
+    if (i < N) {
+      v2d acc = ACC ? p[i] : v2d{0.0, 0.0};
+#pragma unroll
+      for (int g = G - 1; g >= 0; g--) {
+        const double cre = V.c[2 * g], cim = V.c[2 * g + 1];
+        const v2d b = V.f[g][off + i];
+        if (!ACC && g == G - 1) acc = v2d{cre * b.x - cim * b.y, cre * b.y + cim * b.x};
+        else acc = v2d{acc.x + cre * b.x - cim * b.y, acc.y + cre * b.y + cim * b.x};
+      }
+      p[i] = acc;
+    }
+  }
+}
+
 
 static int check_eo(const tmhip_field *f, const char *who) {
   if (!f || f->kind != TMHIP_FIELD_EO || f->prec != 0) { fprintf(stderr, "[tmlqcd_hip] %s: needs a one-parity (EO) field\n", who); return 1; }
   return 0;
 }
 
+// MPI_Allreduce(..., MPI_SUM) of the reference (square_norm.c:314): one double over RCCL
+int tmhip_rank_sum(tmhip_ctx *ctx) {
+  if (ctx->direct.on && ctx->direct.sums_on) return tmhip_direct_allreduce(ctx, ctx->result_dev);
+  if (ctx->shm) return tmhip_shm_allreduce(ctx, ctx->stream, ctx->result_dev, 1);
+  TMHIP_NCCL_CHECK(ncclAllReduce(ctx->result_dev, ctx->result_dev, 1, ncclDouble, ncclSum, ctx->comm_red, ctx->stream));
+  return 0;
+}
+
 int tmhip_reduce_finish(tmhip_ctx *ctx, int nblocks, int parallel, double *out) {
   hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->partials, nblocks, ctx->result_dev);
-  if (parallel && tmhip_reduce_over_ranks(ctx)) {
-    // MPI_Allreduce(..., MPI_SUM) of the reference (square_norm.c:314): one double over RCCL
-    if (ctx->direct.on && ctx->direct.sums_on) { if (tmhip_direct_allreduce(ctx, ctx->result_dev)) return 1; }
-    else {
-      if (ctx->shm) { if (tmhip_shm_allreduce(ctx, ctx->stream, ctx->result_dev, 1)) return 1; }
-      else { TMHIP_NCCL_CHECK(ncclAllReduce(ctx->result_dev, ctx->result_dev, 1, ncclDouble, ncclSum, ctx->comm_red, ctx->stream)); }
-    }
-  }
+  if (parallel && tmhip_reduce_over_ranks(ctx) && tmhip_rank_sum(ctx)) return 1;
   TMHIP_CHECK(hipMemcpyAsync(ctx->result_host, ctx->result_dev, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   *out = *ctx->result_host;
   return tmhip_check_async_error(ctx);
+}
+
+// ---- the complex singles and their batched forms: the host cuts n fields into groups of at most CSG_GROUP, one launch per group
+static int csg_buffers(tmhip_ctx *ctx) {
+  if (ctx->csg_partials) return 0;
+  const size_t nb = (size_t)12 * la_grid(ctx->Vh).x;
+  TMHIP_CHECK(hipMalloc((void **)&ctx->csg_partials, 2 * TMHIP_CSG_MAX * nb * sizeof(double)));
+  TMHIP_CHECK(hipMalloc((void **)&ctx->csg_res_dev, 2 * TMHIP_CSG_MAX * sizeof(double)));
+  TMHIP_CHECK(hipHostMalloc((void **)&ctx->csg_res_host, 2 * TMHIP_CSG_MAX * sizeof(double)));
+  return 0;
+}
+static int csg_check(tmhip_ctx *ctx, int n, tmhip_field *const *f, tmhip_field *one, const char *who) {
+  if (n < 1 || n > TMHIP_CSG_MAX) TMHIP_FAIL("%s: n = %d fields, must be in [1, %d]", who, n, TMHIP_CSG_MAX);
+  if (!f || check_eo(one, who)) return 1;
+  for (int i = 0; i < n; i++) if (check_eo(f[i], who) || f[i]->ns != one->ns) return 1;
+  return 0;
+}
+template <int G> static CsgFields<G> csg_pack(tmhip_field *const *f, const double *c) {
+  CsgFields<G> a;
+  for (int g = 0; g < G; g++) { a.f[g] = f[g]->d; a.c[2 * g] = c ? c[2 * g] : 0.0; a.c[2 * g + 1] = c ? c[2 * g + 1] : 0.0; }
+  return a;
+}
+// calls body(std::integral_constant<int, G>) for the run-time group size g in [1, CSG_GROUP]
+template <int G, class F> static inline void csg_dispatch(int g, F body) {
+  if (g == G) body(std::integral_constant<int, G>());
+  else if constexpr (G > 1) csg_dispatch<G - 1>(g, body);
+}
+
+// block sums of <S_i, R>, i < n, into csg_partials and one final pass into csg_res_dev[0 .. 2n)
+static int csg_dot_enqueue(tmhip_ctx *ctx, int n, tmhip_field *const *S, tmhip_field *R, int N) {
+  if (csg_buffers(ctx)) return 1;
+  const dim3 grid = la_grid(N);
+  const size_t per = (size_t)grid.x * grid.y;
+  for (int first = 0; first < n; first += CSG_DOT_GROUP) {
+    const int g = n - first < CSG_DOT_GROUP ? n - first : CSG_DOT_GROUP;
+    csg_dispatch<CSG_DOT_GROUP>(g, [&](auto Gc) {
+      constexpr int G = decltype(Gc)::value;
+      hipLaunchKernelGGL(csg_dot_kernel<G>, grid, dim3(LA_BS), 0, ctx->stream, csg_pack<G>(S + first, nullptr), (const v2d *)R->d, R->ns, N,
+                         ctx->csg_partials + 2 * first * per);
+    });
+  }
+  hipLaunchKernelGGL(reduce_final_multi_kernel, dim3(2 * n), dim3(256), 0, ctx->stream, (const double *)ctx->csg_partials, (int)per, ctx->csg_res_dev);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 extern "C" {
@@ -250,6 +405,74 @@ int tmhip_assign(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, int N) {
   hipLaunchKernelGGL(stream_kernel<3>, la_grid(N), dim3(LA_BS), 0, ctx->stream, R->d, S->d, (const v2d *)nullptr, 0.0, R->ns, N);
   TMHIP_CHECK(hipGetLastError());
   return 0;
+}
+
+int tmhip_multi_scalar_prod(tmhip_ctx *ctx, int n, tmhip_field *const *S, tmhip_field *R, int N, double *out) {
+  if (csg_check(ctx, n, S, R, "multi_scalar_prod")) return 1;
+  if (tmhip_reduce_over_ranks(ctx)) TMHIP_FAIL("multi_scalar_prod: rank-local; on a rank that sums over ranks call tmhip_scalar_prod per field");
+  LA_CHECK_N("multi_scalar_prod", memset(out, 0, 2 * n * sizeof(double)));
+  if (csg_dot_enqueue(ctx, n, S, R, N)) return 1;
+  TMHIP_CHECK(hipMemcpyAsync(ctx->csg_res_host, ctx->csg_res_dev, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  memcpy(out, ctx->csg_res_host, 2 * n * sizeof(double));
+  return tmhip_check_async_error(ctx);
+}
+
+int tmhip_scalar_prod(tmhip_ctx *ctx, tmhip_field *S, tmhip_field *R, int N, int parallel, double out[2]) {
+  if (csg_check(ctx, 1, &S, R, "scalar_prod")) return 1;
+  LA_CHECK_N("scalar_prod", out[0] = out[1] = 0.0);
+  if (csg_dot_enqueue(ctx, 1, &S, R, N)) return 1;
+  if (parallel && tmhip_reduce_over_ranks(ctx)) {
+    for (int k = 0; k < 2; k++) {   // the one-value sum over the ranks, once per part
+      TMHIP_CHECK(hipMemcpyAsync(ctx->result_dev, ctx->csg_res_dev + k, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      if (tmhip_rank_sum(ctx)) return 1;
+      TMHIP_CHECK(hipMemcpyAsync(ctx->csg_res_dev + k, ctx->result_dev, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+  }
+  TMHIP_CHECK(hipMemcpyAsync(ctx->csg_res_host, ctx->csg_res_dev, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  out[0] = ctx->csg_res_host[0]; out[1] = ctx->csg_res_host[1];
+  return tmhip_check_async_error(ctx);
+}
+
+int tmhip_multi_assign_diff_mul(tmhip_ctx *ctx, int n, tmhip_field *const *R, tmhip_field *S, const double *c, int N) {
+  if (csg_check(ctx, n, R, S, "multi_assign_diff_mul")) return 1;
+  LA_CHECK_N("multi_assign_diff_mul", (void)0);
+  for (int first = 0; first < n; first += CSG_GROUP) {
+    const int g = n - first < CSG_GROUP ? n - first : CSG_GROUP;
+    csg_dispatch<CSG_GROUP>(g, [&](auto Gc) {
+      constexpr int G = decltype(Gc)::value;
+      hipLaunchKernelGGL(csg_axpy_kernel<G>, la_grid(N), dim3(LA_BS), 0, ctx->stream, csg_pack<G>(R + first, c + 2 * first), (const v2d *)S->d, S->ns, N);
+    });
+  }
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_assign_diff_mul(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, double c_re, double c_im, int N) {
+  const double c[2] = {c_re, c_im};
+  return tmhip_multi_assign_diff_mul(ctx, 1, &R, S, c, N);
+}
+
+int tmhip_lincomb(tmhip_ctx *ctx, tmhip_field *P, int n, tmhip_field *const *V, const double *c, int N) {
+  if (csg_check(ctx, n, V, P, "lincomb")) return 1;
+  LA_CHECK_N("lincomb", (void)0);
+  // the group of the highest indices starts the sum, the groups below it add to P
+  for (int end = n; end > 0; end -= CSG_GROUP) {
+    const int g = end < CSG_GROUP ? end : CSG_GROUP, first = end - g;
+    csg_dispatch<CSG_GROUP>(g, [&](auto Gc) {
+      constexpr int G = decltype(Gc)::value;
+      if (end == n) hipLaunchKernelGGL((csg_lincomb_kernel<G, false>), la_grid(N), dim3(LA_BS), 0, ctx->stream, P->d, csg_pack<G>(V + first, c + 2 * first), P->ns, N);
+      else hipLaunchKernelGGL((csg_lincomb_kernel<G, true>), la_grid(N), dim3(LA_BS), 0, ctx->stream, P->d, csg_pack<G>(V + first, c + 2 * first), P->ns, N);
+    });
+  }
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_mul(tmhip_ctx *ctx, tmhip_field *R, double c_re, double c_im, tmhip_field *S, int N) {
+  const double c[2] = {c_re, c_im};
+  return tmhip_lincomb(ctx, R, 1, &S, c, N);
 }
 
 static int launch_diag(tmhip_ctx *ctx, tmhip_field *l, tmhip_field *k, tmhip_field *j, double zre, double zim, int beta,

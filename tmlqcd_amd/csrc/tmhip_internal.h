@@ -221,6 +221,9 @@ struct tmhip_ctx {
   int opt_gauge_pack_rot;   // -1: the first rotation that verifies; 0..2: try that one first (tests)
   float gpack_build_ms;     // device time of the last build (HIP events)
   hipEvent_t gpack_ev[2];
+  // complex scalar products (linalg.hip): [2 TMHIP_CSG_MAX][12 blocks] block sums, the 2 TMHIP_CSG_MAX results on the device and, pinned, on the host; allocated on first use
+  double *csg_partials, *csg_res_dev, *csg_res_host;
+  int opt_csg_batch;        // 1 (default): tmhip_chrono_guess on the batched kernels; 0: a sequence of the complex singles
 };
 
 // N is a site count of a one-parity field: 0 is a legal empty loop in the reference (linalg/*.c), anything outside [0, V/2] would
@@ -333,6 +336,7 @@ int tmhip_launch_hopping_dot32(tmhip_ctx *ctx, int ieo, v2f *out, const v2f *in,
                                const v2f *cw = nullptr, int chained = 0);
 bool tmhip_fused_dot32_ok(const tmhip_ctx *ctx);
 int tmhip_reduce_finish(tmhip_ctx *ctx, int nblocks, int parallel, double *out);
+int tmhip_rank_sum(tmhip_ctx *ctx);   // linalg.hip: *ctx->result_dev summed over the ranks in place, enqueued on ctx->stream (callers check tmhip_reduce_over_ranks)
 #define RAT_MAX_PAIRS 64   // pairs per launch of the batched force kernels (rational.hip deriv_Sb_batch, clover.hip sw_spinor_eo_batch)
 // After a host-visible synchronisation of a T-split rank: non-zero (with a message) when a bounded device-side wait for the
 // neighbours' faces gave up ("flag_timeout_ms") or the communicator reports an asynchronous error, i.e. the result just

@@ -170,6 +170,11 @@ def load_library():
         "tmhip_deriv_Sb_batch": [vp, i, i, C.POINTER(vp), C.POINTER(vp), pd],
         "tmhip_Q_tau1_sub_const_ndpsi": [vp, vp, vp, vp, vp, d, d, d, d],
         "tmhip_assign_add_mul": [vp, vp, vp, d, d, i],
+        "tmhip_scalar_prod": [vp, vp, vp, i, i, pd], "tmhip_assign_diff_mul": [vp, vp, vp, d, d, i], "tmhip_mul": [vp, vp, d, d, vp, i],
+        "tmhip_multi_scalar_prod": [vp, i, C.POINTER(vp), vp, i, pd], "tmhip_multi_assign_diff_mul": [vp, i, C.POINTER(vp), vp, pd, i],
+        "tmhip_lincomb": [vp, vp, i, C.POINTER(vp), pd, i],
+        "tmhip_chrono_guess": [vp, vp, vp, C.POINTER(vp), i, i, i, pd, pd], "tmhip_chrono_add_solution": [vp, vp, vp, i],
+        "tmhip_csg_solve": [i, pd, pd],
         "tmhip_ndrat_force": [vp, C.POINTER(vp), C.POINTER(vp), pd, pd, i, d],
         "tmhip_ndrat_derivative": [vp, vp, vp, pd, pd, i, d, i, d, i, C.POINTER(i)],
         "tmhip_ndrat_heatbath": [vp, vp, vp, pd, pd, i, d, i, d, i, pd, C.POINTER(i)],
@@ -227,6 +232,15 @@ def _hp(a):
     if a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"]:
         raise TmHipError("host arrays must be C-contiguous float64")
     return a.ctypes.data_as(C.c_void_p)
+
+
+def csg_solve(G, b):
+    """The small solve of chrono_guess alone (tmhip_csg_solve; host code, no device needed): y with G y = b."""
+    G = np.array(G, dtype=np.complex128, order="C")
+    b = np.array(b, dtype=np.complex128, order="C")
+    pd = C.POINTER(C.c_double)
+    _ck(load_library().tmhip_csg_solve(len(b), G.view(np.float64).ctypes.data_as(pd), b.view(np.float64).ctypes.data_as(pd)), "csg_solve")
+    return b
 
 
 class Field:
@@ -727,6 +741,71 @@ class Lattice:
 
     def assign(self, R, S, N):
         _ck(self.lib.tmhip_assign(self.h, R.h, S.h, N), "assign")
+
+    # --- complex linalg and its batched forms (linalg/scalar_prod.c, assign_diff_mul.c, mul.c) ---
+    @staticmethod
+    def _handles(fs):
+        return (C.c_void_p * max(len(fs), 1))(*[f.h for f in fs])
+
+    @staticmethod
+    def _pairs(cs):
+        a = np.ascontiguousarray(np.asarray(cs, dtype=np.complex128).reshape(-1))
+        return a, a.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))
+
+    def scalar_prod(self, S, R, N, parallel=0):
+        """sum conj(S) R"""
+        out = (C.c_double * 2)()
+        _ck(self.lib.tmhip_scalar_prod(self.h, S.h, R.h, N, parallel, out), "scalar_prod")
+        return complex(out[0], out[1])
+
+    def assign_diff_mul(self, R, S, c, N):
+        """R -= c S"""
+        c = complex(c)
+        _ck(self.lib.tmhip_assign_diff_mul(self.h, R.h, S.h, c.real, c.imag, N), "assign_diff_mul")
+
+    def mul(self, R, c, S, N):
+        """R = c S (R may be S)"""
+        c = complex(c)
+        _ck(self.lib.tmhip_mul(self.h, R.h, c.real, c.imag, S.h, N), "mul")
+
+    def multi_scalar_prod(self, Ss, R, N):
+        """[<S_i, R>] as a complex128 array, one pass over R per group of fields and one host synchronisation"""
+        n = len(Ss)
+        out = np.zeros(max(n, 1), dtype=np.complex128)
+        _ck(self.lib.tmhip_multi_scalar_prod(self.h, n, self._handles(Ss), R.h, N, out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))),
+            "multi_scalar_prod")
+        return out[:n]
+
+    def multi_assign_diff_mul(self, Rs, S, cs, N):
+        """R_i -= c_i S for all i"""
+        if len(cs) != len(Rs):
+            raise TmHipError("multi_assign_diff_mul: one coefficient per field")
+        keep, pc = self._pairs(cs)
+        _ck(self.lib.tmhip_multi_assign_diff_mul(self.h, len(Rs), self._handles(Rs), S.h, pc, N), "multi_assign_diff_mul")
+
+    def lincomb(self, P, Vs, cs, N):
+        """P = sum_i c_i V_i, added from the last field down to the first"""
+        if len(cs) != len(Vs):
+            raise TmHipError("lincomb: one coefficient per field")
+        keep, pc = self._pairs(cs)
+        _ck(self.lib.tmhip_lincomb(self.h, P.h, len(Vs), self._handles(Vs), pc, N), "lincomb")
+
+    # --- chronological solver guess (solver/chrono_guess.c) -----------------
+    def chrono_guess(self, trial, phi, vs, op="Qtm_pm_psi", N=None):
+        """trial = the guess for op x = phi from the stored solutions vs (oldest first; all but the last are orthogonalised against
+        the last in place).  Returns (G, bn): the projected operator [n][n] and the projected right-hand side [n], complex128."""
+        n = len(vs)
+        N = self.Vh if N is None else N
+        G = np.zeros((n, n), dtype=np.complex128)
+        bn = np.zeros(max(n, 1), dtype=np.complex128)
+        pd = C.POINTER(C.c_double)
+        _ck(self.lib.tmhip_chrono_guess(self.h, trial.h, phi.h, self._handles(vs), n, OPS[op], N,
+                                        G.view(np.float64).ctypes.data_as(pd) if n else None, bn.view(np.float64).ctypes.data_as(pd)), "chrono_guess")
+        return G, bn[:n]
+
+    def chrono_add_solution(self, slot, trial, N=None):
+        """slot = trial / |trial|"""
+        _ck(self.lib.tmhip_chrono_add_solution(self.h, slot.h, trial.h, self.Vh if N is None else N), "chrono_add_solution")
 
     # --- solver -----------------------------------------------------------
     def cg_her(self, P, Q, max_iter, eps_sq, rel_prec, N, op="Qtm_pm_psi"):

@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/rational.ru.txt lib/nd.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/rational.ru.txt lib/nd.ru.txt
 """
 import re
 import subprocess
@@ -58,6 +58,11 @@ RULES = [
     (r"^(void )?sw_spinor_eo_batch_kernel", "batched sw_spinor_eo", 3),
     # the tr-log energies: a fully unrolled 6x6 factorisation per site in registers
     (r"^void sw_trace_kernel<(true|false)>", "sw_trace / sw_trace_nd", 2),
+    # the complex linalg of the chronological guess (linalg.hip), one instance per group size: the accumulators of a group stay in
+    # registers -- no scratch -- at the eight waves per SIMD the build reports for dotr_kernel
+    (r"^void csg_dot_kernel<\d+>", "batched scalar_prod", 8),
+    (r"^void csg_axpy_kernel<\d+>", "batched assign_diff_mul", 8),
+    (r"^void csg_lincomb_kernel<\d+, (true|false)>", "lincomb", 8),
 ]
 
 
