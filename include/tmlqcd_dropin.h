@@ -338,6 +338,17 @@ double measure_gauge_action(const su3 **const gf, const double lambda);         
 double measure_rectangles(const su3 **const gf);                                 /* measure_rectangles.c:51 */
 void tmlqcd_hip_gauge_derivative(hamiltonian_field_t *const hf, const double beta, const double c0, const double c1, const int use_rectangles, const double glambda);
 
+/* ---- gradient flow (meas/gradient_flow.c, meas/measure_clover_field_strength_observables.c): replaces
+ *      meas/measure_clover_field_strength_observables.o -----------------------------------------------------------------------------
+ * measure_clover_field_strength_observables under the reference's name, on the device links: gf must be g_gauge_field, uploaded by the
+ * rule of every other entry point; in resident mode the device's newer links are measured without any transfer.
+ * tmlqcd_hip_gradient_flow_measurement is the body of gradient_flow_measurement with gf_eps / gf_tmax of measurement_list[id] as
+ * arguments: it flows device copies of the links (neither g_gauge_field nor the resident links change) and writes gradflow.<traj>
+ * (%06d) into the working directory in the reference's format.  An unopenable file and a T-split run end the program with a message. */
+typedef struct { double E; double Q; } field_strength_obs_t;                     /* meas/field_strength_types.h */
+void measure_clover_field_strength_observables(const su3 **const gf, field_strength_obs_t *const fso);
+void tmlqcd_hip_gradient_flow_measurement(const int traj, const double eps, const double tmax);
+
 /* ---- rational monomials (monomial/ndrat_monomial.c type NDRAT, monomial/rat_monomial.c type RAT) --------------------------------------
  * The bodies of the three monomial functions with the monomial's parameters as arguments (rational_t::mu / rmu / nu / rnu with np entries,
  * EVMaxInv, maxiter, forceprec or accprec, g_relative_precision_flag), as tmlqcd_hip_gauge_derivative does for the gauge monomial; the

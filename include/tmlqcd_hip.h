@@ -458,6 +458,28 @@ int tmhip_measure_plaquette(tmhip_ctx *ctx, double *out);
 int tmhip_measure_gauge_action(tmhip_ctx *ctx, double glambda, double *out);
 int tmhip_measure_rectangles(tmhip_ctx *ctx, double *out);
 
+/* ---- Wilson gradient flow and clover field strength on the device-resident links (meas/gradient_flow.c,
+ *      meas/measure_clover_field_strength_observables.c; flow.hip) -------------------------------------------------------
+ * fp64, unsplit lattices.  The flow works on private copies: the resident links, the stencil's gauge copy and the clover blocks are
+ * never touched.  tmhip_flow_begin allocates two link buffers and Z (2 x 576 + 288 bytes per site) and copies the resident links in
+ * (calling it again restarts from the links resident then); tmhip_flow_step is one step_gradient_flow (third-order Runge-Kutta,
+ * plaquette staples, cayley_hamilton_exponent); tmhip_flow_observables returns P = measure_plaquette / (6 VOLUME) and E, Q of
+ * measure_clover_field_strength_observables on the flowed links; tmhip_flow_end frees the buffers (tmhip_destroy does so too).
+ * tmhip_gradient_flow is the loop of gradient_flow_measurement: it measures at t = 0, then takes pairs of steps while (t[1] < tmax)
+ * with t[step] = t[step-1] + eps, and writes one row of eight doubles per pair at the odd step,
+ *   t  P  Eplaq = 36 (1 - P)  Esym  t^2 Eplaq  t^2 Esym  Wsym = t^2 (2 E_1 + t (E_2 - E_0) / (2 eps))  Qsym,
+ * at most max_rows of them (non-zero, nothing written past them, if the loop needs more); *nrows = rows written.
+ * Two calls on the same links give bit-identical results.  All return non-zero, launching nothing, without resident links
+ * (tmhip_set_gauge) and on a T-split rank (nproc_t > 1: the link halo would have to be refreshed after every stage);
+ * _step / _observables / _download also without a preceding tmhip_flow_begin. */
+int tmhip_measure_field_strength(tmhip_ctx *ctx, double *E, double *Q);      /* on the resident links */
+int tmhip_flow_begin(tmhip_ctx *ctx);
+int tmhip_flow_step(tmhip_ctx *ctx, double eps);
+int tmhip_flow_observables(tmhip_ctx *ctx, double *P, double *E, double *Q);
+int tmhip_flow_download(tmhip_ctx *ctx, void *host_gauge);                   /* flowed links, [VOLUME][4] su3 */
+int tmhip_flow_end(tmhip_ctx *ctx);
+int tmhip_gradient_flow(tmhip_ctx *ctx, double eps, double tmax, int max_rows, double *rows, int *nrows);
+
 /* ---- ILDG gauge configurations (io/gauge_read.c:28-198, io/gauge_read_binary.c:140-200, io/gauge_write.c:22-59,
  *      io/gauge_write_binary.c:150-175, io/dml.c:49-60).  The "ildg-binary-data" record travels to / from the device as it lies in
  *      the file; byte swap, 32 <-> 64 bit conversion, site and link re-ordering and the SciDAC checksum happen in HBM (ildg.hip). -- */

@@ -1060,6 +1060,49 @@ void tmlqcd_hip_gauge_derivative(hamiltonian_field_t *const hf, const double bet
   force_end(hf);
 }
 
+// ------------------------------------------------------------------ gradient flow and field strength (flow.hip)
+/* meas/measure_clover_field_strength_observables.c:55-225 on the device links, by the rules of the gauge measures above.  Unsplit
+ * lattices: on a T-split rank the core entry point refuses and the program ends with its message, as for the rectangle measures. */
+void measure_clover_field_strength_observables(const su3 **const gf, field_strength_obs_t *const fso) {
+  tmhip_ctx *c = gauge_links(gf, "measure_clover_field_strength_observables: gf is not g_gauge_field");
+  CK(tmhip_measure_field_strength(c, &fso->E, &fso->Q));
+}
+/* gradient_flow_measurement (meas/gradient_flow.c:132-239) with gf_eps / gf_tmax of measurement_list[id] as arguments: the flow runs on
+ * device copies of the links (g_gauge_field and the device's resident links are not modified), one line per pair of steps goes to
+ * gradflow.<traj> in the working directory, flushed as the reference does. */
+void tmlqcd_hip_gradient_flow_measurement(const int traj, const double eps, const double tmax) {
+  tmhip_ctx *c = gauge_links((const su3 **)g_gauge_field, "tmlqcd_hip_gradient_flow_measurement: no g_gauge_field");
+  if (g_nproc_t > 1) die("tmlqcd_hip_gradient_flow_measurement: not available on T-split ranks (the link halo would need a refresh after every stage)");
+  char filename[100];
+  snprintf(filename, 100, "gradflow.%06d", traj);
+  FILE *outfile = fopen(filename, "w");
+  if (outfile == NULL) {
+    char error_message[200];
+    snprintf(error_message, 200, "Couldn't open %s for writing during gradient flow measurement!", filename);
+    die(error_message);
+  }
+  fprintf(outfile, "traj t P Eplaq Esym tsqEplaq tsqEsym Wsym Qsym\n");
+  // the loop of gradient_flow.c:172-222 on the step-wise entry points, so that every line is on disk when its pair of steps is done
+  double t[3] = {0.0, 0.0, 0.0}, P[3] = {0.0, 0.0, 0.0}, E[3] = {0.0, 0.0, 0.0}, Q[3] = {0.0, 0.0, 0.0};
+  CK(tmhip_flow_begin(c));
+  CK(tmhip_flow_observables(c, &P[2], &E[2], &Q[2]));
+  while (t[1] < tmax) {
+    t[0] = t[2]; E[0] = E[2]; Q[0] = Q[2]; P[0] = P[2];
+    for (int step = 1; step < 3; ++step) {
+      t[step] = t[step - 1] + eps;
+      CK(tmhip_flow_step(c, eps));
+      CK(tmhip_flow_observables(c, &P[step], &E[step], &Q[step]));
+    }
+    const double W = t[1] * t[1] * (2 * E[1] + t[1] * ((E[2] - E[0]) / (2 * eps)));
+    const double tsqE = t[1] * t[1] * E[1];
+    fprintf(outfile, "%06d %f %2.12lf %2.12lf %2.12lf %2.12lf %2.12lf %2.12lf %.12lf \n", traj, t[1], P[1], 36 * (1 - P[1]), E[1],
+            t[1] * t[1] * 36 * (1 - P[1]), tsqE, W, Q[1]);
+    fflush(outfile);
+  }
+  CK(tmhip_flow_end(c));
+  fclose(outfile);
+}
+
 // ------------------------------------------------------------------ rational monomials (rational.hip)
 /* ndrat_monomial.c:96-160 */
 int tmlqcd_hip_ndrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np,

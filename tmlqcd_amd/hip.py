@@ -98,6 +98,9 @@ def load_library():
         "tmhip_update_gauge": [vp, d], "tmhip_gauge_download": [vp, vp],
         "tmhip_gauge_derivative": [vp, d, d, d, i, d],
         "tmhip_measure_plaquette": [vp, pd], "tmhip_measure_gauge_action": [vp, d, pd], "tmhip_measure_rectangles": [vp, pd],
+        "tmhip_measure_field_strength": [vp, pd, pd], "tmhip_flow_begin": [vp], "tmhip_flow_step": [vp, d],
+        "tmhip_flow_observables": [vp, pd, pd, pd], "tmhip_flow_download": [vp, vp], "tmhip_flow_end": [vp],
+        "tmhip_gradient_flow": [vp, d, d, i, pd, C.POINTER(i)],
         "tmhip_gauge_unpack_ildg": [vp, vp, i, C.POINTER(C.c_uint)], "tmhip_gauge_pack_ildg": [vp, vp, i, C.POINTER(C.c_uint)],
         "tmhip_read_gauge_field": [vp, C.c_char_p, i, i, vp, C.POINTER(GaugeInfo)],
         "tmhip_write_gauge_field": [vp, C.c_char_p, i, C.c_char_p, C.POINTER(C.c_uint)],
@@ -521,6 +524,45 @@ class Lattice:
         out = C.c_double(0.0)
         _ck(self.lib.tmhip_measure_rectangles(self.h, C.byref(out)), "measure_rectangles")
         return out.value
+
+    # --- Wilson gradient flow and clover field strength on the resident links (meas/gradient_flow.c; flow.hip) ---
+    def measure_field_strength(self):
+        """(E, Q) of measure_clover_field_strength_observables on the resident links."""
+        e, q = C.c_double(0.0), C.c_double(0.0)
+        _ck(self.lib.tmhip_measure_field_strength(self.h, C.byref(e), C.byref(q)), "measure_field_strength")
+        return e.value, q.value
+
+    def flow_begin(self):
+        """Copy the resident links into the flow buffers (t = 0); the resident links are never modified by the flow."""
+        _ck(self.lib.tmhip_flow_begin(self.h), "flow_begin")
+
+    def flow_step(self, eps):
+        """One step_gradient_flow."""
+        _ck(self.lib.tmhip_flow_step(self.h, eps), "flow_step")
+
+    def flow_observables(self):
+        """(P, E, Q) of the flowed links, P = measure_plaquette / (6 VOLUME)."""
+        p, e, q = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        _ck(self.lib.tmhip_flow_observables(self.h, C.byref(p), C.byref(e), C.byref(q)), "flow_observables")
+        return p.value, e.value, q.value
+
+    def flow_links(self):
+        """The flowed links, [V][4][3][3][2]."""
+        out = np.zeros((self.V, 4, 3, 3, 2))
+        _ck(self.lib.tmhip_flow_download(self.h, _hp(out)), "flow_download")
+        return out
+
+    def flow_end(self):
+        _ck(self.lib.tmhip_flow_end(self.h), "flow_end")
+
+    def gradient_flow(self, eps, tmax, max_rows=None):
+        """The loop of gradient_flow_measurement: an [n][8] array of rows t, P, Eplaq, Esym, tsqEplaq, tsqEsym, Wsym, Qsym."""
+        if max_rows is None:
+            max_rows = int(tmax / (2.0 * eps)) + 2 if eps > 0.0 else 0
+        rows = np.zeros((max(max_rows, 1), 8))
+        n = C.c_int(0)
+        _ck(self.lib.tmhip_gradient_flow(self.h, eps, tmax, max_rows, rows.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)), "gradient_flow")
+        return rows[:n.value].copy()
 
     # ---- ILDG gauge configurations (io/gauge_read.c, io/gauge_write.c; ildg.hip)
     def gauge_unpack_ildg(self, file_bytes, prec):

@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/rational.ru.txt lib/nd.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/rational.ru.txt lib/nd.ru.txt
 """
 import re
 import subprocess
@@ -46,6 +46,10 @@ RULES = [
     # the gauge monomial (gauge.hip): four to five 3x3 complex matrices live per link, no scratch, two waves per SIMD
     (r"^void gaugehip::gauge_force_kernel<(true|false)>", "gauge force", 2),
     (r"^(void )?gaugehip::(plaquette|rectangle)_sum_kernel", "gauge action", 2),
+    # the gradient flow (flow.hip): a stage is the plaquette force's staple sum plus the Cayley-Hamilton exponential; the field strength
+    # keeps two projected leaves of a site next to one rolled path product: no scratch, two waves per SIMD
+    (r"^void flowhip::flow_stage_kernel<[012]>", "flow stage", 2),
+    (r"^(void )?flowhip::field_strength_kernel", "field strength", 2),
     # the batched hopping force of the rational monomials (rational.hip): no scratch, two waves per SIMD
     (r"^(void )?rathip::deriv_Sb_batch_kernel", "batched hopping force", 2),
     # the clover doublet (nd.hip): the doublet stencil with the clover mixing as its epilogue, and the site-local form of the same
