@@ -349,6 +349,25 @@ typedef struct { double E; double Q; } field_strength_obs_t;                    
 void measure_clover_field_strength_observables(const su3 **const gf, field_strength_obs_t *const fso);
 void tmlqcd_hip_gradient_flow_measurement(const int traj, const double eps, const double tmax);
 
+/* ---- the other online measurements (meas/correlators.c, meas/pion_norm.c, meas/oriented_plaquettes.c, meas/polyakov_loop.c): replaces
+ *      meas/oriented_plaquettes.o ---------------------------------------------------------------------------------------------------
+ * tmlqcd_hip_slice_correlators: the sums of the t loop of correlators_measurement (dir 0: pp / pa / p4 hold T values each, what the
+ * loop calls res / respa / resp4 before its MPI_Reduce) and of the z loop of pion_norm_measurement (dir 3: LZ values; pa = p4 = NULL),
+ * taken from the two e/o halves of the propagator (optr->prop0 / prop1, g_spinor_field[2] / [3]) without convert_eo_to_lexic.  The
+ * halves are registered like any other input: in lazy or resident mode nothing travels.  Any other dir ends the program.
+ * measure_oriented_plaquettes and oriented_plaquettes_measurement under the reference's names, on the device links (gf must be
+ * g_gauge_field, by the rules of measure_plaquette); the second appends its line to oriented_plaquettes.data in the working directory
+ * and ends the program with a message when the file cannot be opened, as fatal_error does.
+ * tmlqcd_hip_polyakov_loop: pl[0] + i pl[1] = the Polyakov loop along dir = 0 .. 3 (for 2 and 3 the value of polyakov_loop).
+ * tmlqcd_hip_polyakov_loop_dir is polyakov_loop_dir: dir 0 or 3 (-1 otherwise), one line "nstore dir re im" written to
+ * polyakovloop_dir<dir> (mode "w" for nstore == 0, "a" otherwise); 0 on success, -1 when the file cannot be opened.
+ * The two gauge measurements end the program on T-split runs (g_nproc_t > 1). */
+void tmlqcd_hip_slice_correlators(const spinor *const even, const spinor *const odd, const int dir, double *const pp, double *const pa, double *const p4);
+void measure_oriented_plaquettes(const su3 **const gf, double *plaq);            /* meas/oriented_plaquettes.c:39 */
+void oriented_plaquettes_measurement(const int traj, const int id, const int ieo); /* meas/oriented_plaquettes.c:88 */
+void tmlqcd_hip_polyakov_loop(double pl[2], const int dir);
+int tmlqcd_hip_polyakov_loop_dir(const int nstore, const int dir);               /* meas/polyakov_loop.c:325 */
+
 /* ---- rational monomials (monomial/ndrat_monomial.c type NDRAT, monomial/rat_monomial.c type RAT) --------------------------------------
  * The bodies of the three monomial functions with the monomial's parameters as arguments (rational_t::mu / rmu / nu / rnu with np entries,
  * EVMaxInv, maxiter, forceprec or accprec, g_relative_precision_flag), as tmlqcd_hip_gauge_derivative does for the gauge monomial; the

@@ -480,6 +480,28 @@ int tmhip_flow_download(tmhip_ctx *ctx, void *host_gauge);                   /* 
 int tmhip_flow_end(tmhip_ctx *ctx);
 int tmhip_gradient_flow(tmhip_ctx *ctx, double eps, double tmax, int max_rows, double *rows, int *nrows);
 
+/* ---- the other online measurements (meas/correlators.c, meas/pion_norm.c, meas/polyakov_loop.c, meas/oriented_plaquettes.c; meas.hip)
+ * fp64.  Each call is one kernel, one final pass over its partial sums and ONE synchronisation, however many numbers it returns; the
+ * sums are added in a fixed order without atomics, so two calls on the same data give bit-identical results.
+ * tmhip_slice_correlators: the raw per-slice sums of a propagator given as its two one-parity halves (TMHIP_FIELD_EO, fp64), both
+ *   parities added: pp[s] = sum psi^+ psi, pa[s] = sum Re psi^+ (gamma0 psi), p4[s] = sum Im psi^+ (gamma5 gamma0 psi), composed from
+ *   _gamma0, _gamma5, _spinor_prod_re, _spinor_prod_im as correlators.c:165-169 does.  dir 0: time-slices, T values per array
+ *   (correlators.c:159-170); dir 3: z-slices, LZ values (pion_norm.c:98-107); any other dir returns non-zero.  pa and p4 may be NULL
+ *   (pion_norm needs pp only; with both NULL the bilinear is not computed).  Normalisation, the sign of pa, 1 / (2 kappa^2) and the output file stay with the caller.  The sum
+ *   is site-local: a T-split rank (nproc_t > 1) gets its local T slices (dir 0) or its share of every z-slice (dir 3) and the caller
+ *   adds over the ranks as the reference's MPI_Reduce does.  fp32 fields, FULL fields and fields of another context return non-zero
+ *   with a message and launch nothing.
+ * tmhip_polyakov_loop: the trace of the ordered product of the L_dir links along dir = 0 .. 3 from coordinate 0, summed over the
+ *   VOLUME / L_dir lines and divided by 3 VOLUME / L_dir (polyakov_loop.c:366-392, :498-537), on the resident links (tmhip_set_gauge,
+ *   kept current by tmhip_update_gauge).  An extent below 3 along dir returns non-zero (the reference's loop multiplies three links
+ *   there), as do a T-split rank and a context without resident links.
+ * tmhip_measure_oriented_plaquettes: the averages of Re tr P_{mu nu} / 3 over the sites for the planes (0,1), (0,2), (0,3), (1,2),
+ *   (1,3), (2,3), each divided by VOLUME (oriented_plaquettes.c:52-78); their sum times 3 VOLUME is tmhip_measure_plaquette.  Resident
+ *   links, unsplit lattices. */
+int tmhip_slice_correlators(tmhip_ctx *ctx, const tmhip_field *even, const tmhip_field *odd, int dir, double *pp, double *pa, double *p4);
+int tmhip_polyakov_loop(tmhip_ctx *ctx, int dir, double *re, double *im);
+int tmhip_measure_oriented_plaquettes(tmhip_ctx *ctx, double plaq[6]);
+
 /* ---- ILDG gauge configurations (io/gauge_read.c:28-198, io/gauge_read_binary.c:140-200, io/gauge_write.c:22-59,
  *      io/gauge_write_binary.c:150-175, io/dml.c:49-60).  The "ildg-binary-data" record travels to / from the device as it lies in
  *      the file; byte swap, 32 <-> 64 bit conversion, site and link re-ordering and the SciDAC checksum happen in HBM (ildg.hip). -- */

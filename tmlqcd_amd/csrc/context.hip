@@ -223,6 +223,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   tmhip_nd_destroy(ctx);
   tmhip_mms_destroy(ctx);
   tmhip_flow_destroy(ctx);
+  tmhip_meas_destroy(ctx);
   for (int i = 0; i < 3; i++) { tmhip_field_free(ctx, ctx->scratch[i]); tmhip_field_free(ctx, ctx->sf[i]); }
   tmhip_field_free(ctx, ctx->sf_extra);
   for (int i = 0; i < 2; i++) tmhip_field_free(ctx, ctx->scratch32[i]);

@@ -1103,6 +1103,64 @@ void tmlqcd_hip_gradient_flow_measurement(const int traj, const double eps, cons
   fclose(outfile);
 }
 
+// ------------------------------------------------------------------ the other online measurements (meas.hip)
+/* The site loops of correlators_measurement (meas/correlators.c:154-170, dir 0) and pion_norm_measurement (meas/pion_norm.c:93-107,
+ * dir 3) on the two e/o halves of the propagator, which are inputs like any other (uploaded unless their mirrors are current).  The
+ * raw sums of this rank: the reference's MPI_Reduce, normalisation and files stay the caller's. */
+void tmlqcd_hip_slice_correlators(const spinor *const even, const spinor *const odd, const int dir, double *const pp, double *const pa, double *const p4) {
+  tmhip_ctx *c = ses.refresh(false);
+  tmhip_field *fe = in(c, even, TMHIP_FIELD_EO), *fo = in(c, odd, TMHIP_FIELD_EO);
+  CK(tmhip_slice_correlators(c, fe, fo, dir, pp, pa, p4));
+}
+static tmhip_ctx *unsplit_gauge_links(const su3 **const gf, const char *who, const char *split) {
+  if (g_nproc_t > 1) die(split);
+  return gauge_links(gf, who);
+}
+/* meas/oriented_plaquettes.c:39-86 on the device links, by the rules of the gauge measures above */
+void measure_oriented_plaquettes(const su3 **const gf, double *plaq) {
+  tmhip_ctx *c = unsplit_gauge_links(gf, "measure_oriented_plaquettes: gf is not g_gauge_field", "measure_oriented_plaquettes: not available on T-split ranks");
+  CK(tmhip_measure_oriented_plaquettes(c, plaq));
+}
+/* meas/oriented_plaquettes.c:88-112; neither function reads measurement_list */
+void oriented_plaquettes_measurement(const int traj, const int id, const int ieo) {
+  (void)ieo;
+  double plaq[6];
+  measure_oriented_plaquettes((const su3 **)g_gauge_field, plaq);
+  char filename[] = "oriented_plaquettes.data";
+  FILE *outfile = fopen(filename, "a");
+  if (outfile == NULL) {
+    char error_message[200];
+    snprintf(error_message, 200, "Couldn't open %s for appending during measurement %d!", filename, id);
+    die(error_message);
+  }
+  fprintf(outfile, "%.8d %14.12lf %14.12lf %14.12lf %14.12lf %14.12lf %14.12lf\n", traj, plaq[0], plaq[1], plaq[2], plaq[3], plaq[4], plaq[5]);
+  fclose(outfile);
+}
+/* The Polyakov loop along any direction on the device links: polyakov_loop (meas/polyakov_loop.c:51-157) for dir 2 and 3, the value
+ * polyakov_loop_dir (:325-558) writes for dir 0 and 3 */
+void tmlqcd_hip_polyakov_loop(double pl[2], const int dir) {
+  tmhip_ctx *c = unsplit_gauge_links((const su3 **)g_gauge_field, "tmlqcd_hip_polyakov_loop: no g_gauge_field", "tmlqcd_hip_polyakov_loop: not available on T-split ranks");
+  CK(tmhip_polyakov_loop(c, dir, &pl[0], &pl[1]));
+}
+int tmlqcd_hip_polyakov_loop_dir(const int nstore, const int dir) {
+  if (dir != 0 && dir != 3) {
+    fprintf(stderr, "Wrong direction; must be 0 (t) or 3 (z)\n");
+    return -1;
+  }
+  double pl[2];
+  tmlqcd_hip_polyakov_loop(pl, dir);
+  char filename[50];
+  snprintf(filename, 50, "polyakovloop_dir%1d", dir);
+  FILE *ofs = fopen(filename, nstore == 0 ? "w" : "a");
+  if (ofs == NULL) {
+    fprintf(stderr, "Could not open file %s for writing\n", filename);
+    return -1;
+  }
+  fprintf(ofs, "%4d\t%2d\t%25.16e\t%25.16e\n", nstore, dir, pl[0], pl[1]);
+  fclose(ofs);
+  return 0;
+}
+
 // ------------------------------------------------------------------ rational monomials (rational.hip)
 /* ndrat_monomial.c:96-160 */
 int tmlqcd_hip_ndrat_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np,

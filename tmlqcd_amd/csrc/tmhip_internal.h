@@ -208,6 +208,7 @@ struct tmhip_ctx {
   int opt_rat_batch;                  // shifts per deriv_Sb_batch launch of the rat / ndrat force
   void *mms; int mms_active_shifts;   // single-flavour multi-shift CG (mms.hip): work fields and solver state
   void *flow;                         // gradient flow in progress (flow.hip): two link buffers and Z, from tmhip_flow_begin to tmhip_flow_end
+  void *meas;                         // online measurements (meas.hip): partial sums and the pinned results of a call, allocated on first use
   double gauge_recon_dev;   // max |U_row2 - conj(row0 x row1)| over all links of the resident gauge field (-1: not measured)
   // packed twin of the gauge copy (121 bytes per link, bit-exact: DESIGN.md section 6, "packed gauge read"), built on first use like gauge32
   void *gpack_mem;          // one allocation behind the four plane sets of gpack
@@ -393,6 +394,7 @@ void tmhip_nd_destroy(tmhip_ctx *ctx);   // nd.hip: work fields and state of the
 void tmhip_rat_destroy(tmhip_ctx *ctx);  // rational.hip: solution and work fields of the rational monomials
 void tmhip_mms_destroy(tmhip_ctx *ctx);  // mms.hip: work fields and state of the single-flavour multi-shift CG
 void tmhip_flow_destroy(tmhip_ctx *ctx); // flow.hip: the buffers of a gradient flow in progress
+void tmhip_meas_destroy(tmhip_ctx *ctx); // meas.hip: the reduction buffers of the online measurements
 // launch geometry shared by linalg.hip and cg.hip
 #define LA_BS 256
 #define LA_UNROLL 4

@@ -101,6 +101,8 @@ def load_library():
         "tmhip_measure_field_strength": [vp, pd, pd], "tmhip_flow_begin": [vp], "tmhip_flow_step": [vp, d],
         "tmhip_flow_observables": [vp, pd, pd, pd], "tmhip_flow_download": [vp, vp], "tmhip_flow_end": [vp],
         "tmhip_gradient_flow": [vp, d, d, i, pd, C.POINTER(i)],
+        "tmhip_slice_correlators": [vp, vp, vp, i, pd, pd, pd], "tmhip_polyakov_loop": [vp, i, pd, pd],
+        "tmhip_measure_oriented_plaquettes": [vp, pd],
         "tmhip_gauge_unpack_ildg": [vp, vp, i, C.POINTER(C.c_uint)], "tmhip_gauge_pack_ildg": [vp, vp, i, C.POINTER(C.c_uint)],
         "tmhip_read_gauge_field": [vp, C.c_char_p, i, i, vp, C.POINTER(GaugeInfo)],
         "tmhip_write_gauge_field": [vp, C.c_char_p, i, C.c_char_p, C.POINTER(C.c_uint)],
@@ -563,6 +565,33 @@ class Lattice:
         n = C.c_int(0)
         _ck(self.lib.tmhip_gradient_flow(self.h, eps, tmax, max_rows, rows.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)), "gradient_flow")
         return rows[:n.value].copy()
+
+    # --- the other online measurements (meas/correlators.c, pion_norm.c, polyakov_loop.c, oriented_plaquettes.c; meas.hip) ---
+    def slice_correlators(self, even, odd, dir=0, pa_p4=True):
+        """Raw per-slice sums of a propagator given as its two one-parity fields: (pp, pa, p4), or pp alone with pa_p4=False.
+        dir 0: T time-slices (correlators.c:159-170), dir 3: LZ z-slices (pion_norm.c:98-107)."""
+        n = self.LZ if dir == 3 else self.T
+        pd = C.POINTER(C.c_double)
+        pp = np.zeros(n)
+        if not pa_p4:
+            _ck(self.lib.tmhip_slice_correlators(self.h, even.h, odd.h, dir, pp.ctypes.data_as(pd), None, None), "slice_correlators")
+            return pp
+        pa, p4 = np.zeros(n), np.zeros(n)
+        _ck(self.lib.tmhip_slice_correlators(self.h, even.h, odd.h, dir, pp.ctypes.data_as(pd), pa.ctypes.data_as(pd), p4.ctypes.data_as(pd)),
+            "slice_correlators")
+        return pp, pa, p4
+
+    def polyakov_loop(self, dir):
+        """The Polyakov loop along dir = 0 .. 3 on the resident links (polyakov_loop.c), a complex number."""
+        re, im = C.c_double(0.0), C.c_double(0.0)
+        _ck(self.lib.tmhip_polyakov_loop(self.h, dir, C.byref(re), C.byref(im)), "polyakov_loop")
+        return complex(re.value, im.value)
+
+    def measure_oriented_plaquettes(self):
+        """The six plane averages of measure_oriented_plaquettes, planes (0,1), (0,2), (0,3), (1,2), (1,3), (2,3)."""
+        out = np.zeros(6)
+        _ck(self.lib.tmhip_measure_oriented_plaquettes(self.h, out.ctypes.data_as(C.POINTER(C.c_double))), "measure_oriented_plaquettes")
+        return [float(x) for x in out]
 
     # ---- ILDG gauge configurations (io/gauge_read.c, io/gauge_write.c; ildg.hip)
     def gauge_unpack_ildg(self, file_bytes, prec):

@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/rational.ru.txt lib/nd.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt
 """
 import re
 import subprocess
@@ -50,6 +50,9 @@ RULES = [
     # keeps two projected leaves of a site next to one rolled path product: no scratch, two waves per SIMD
     (r"^void flowhip::flow_stage_kernel<[012]>", "flow stage", 2),
     (r"^(void )?flowhip::field_strength_kernel", "field strength", 2),
+    # the online measurements (meas.hip): the slice sums hold one spinor and up to six accumulators, the Polyakov line three matrices, the
+    # oriented plaquettes the four of plaquette_sum_kernel and six sums: no scratch, two waves per SIMD, the final pass included
+    (r"^(void )?meaship::\w+_kernel", "online measurements", 2),
     # the batched hopping force of the rational monomials (rational.hip): no scratch, two waves per SIMD
     (r"^(void )?rathip::deriv_Sb_batch_kernel", "batched hopping force", 2),
     # the clover doublet (nd.hip): the doublet stencil with the clover mixing as its epilogue, and the site-local form of the same
