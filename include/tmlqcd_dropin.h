@@ -196,7 +196,9 @@ int rg_mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params solve
  * g_mubar, g_epsbar (global.h:202) and phmc_invmaxev (phmc.h:31) are read at every call (weak references: a host program
  * without them gets 0, 0, 1).  Unsplit lattices only: with g_nproc_t > 1 every symbol below ends the program with a message.
  * The output pair may be the input pair where the reference allows it (Qtm_pm_ndpsi, M_ee_inv_ndpsi, H_eo_tm_ndpsi,
- * mul_one_pm_itau2).  The polynomial helpers (P_ndpsi, Qtau1_P_ndpsi, ...) are not here; the clover doublet follows below. */
+ * mul_one_pm_itau2).  Of the polynomial helpers Ptilde_ndpsi is here (with the monomial NDPOLY, further down); those of the
+ * phmc_exact_poly == 1 branches (P_ndpsi, Qtau1_P_ndpsi, Qtm_pm_sub_const_nrm_psi, Ptm_pm_psi) and Qtm_pm_ndbipsi are not built.
+ * The clover doublet follows below. */
 typedef void (*matrix_mult_nd)(spinor *const, spinor *const, spinor *const, spinor *const);   /* solver/matrix_mult_typedef.h:33 */
 void Qtm_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);          /* :68-89 */
 void Qtm_dagger_ndpsi(spinor *const l_strange, spinor *const l_charm, spinor *const k_strange, spinor *const k_charm);   /* :130-152 */
@@ -384,6 +386,27 @@ int tmlqcd_hip_ndrat_heatbath(spinor *const pf, spinor *const pf2, const double 
                               const int max_iter, const double eps_sq, const int rel_prec, double *energy0);
 int tmlqcd_hip_ndrat_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const int np, const int max_iter,
                          const double eps_sq, const int rel_prec, double *energy1);
+/* ---- the polynomial monomial NDPOLY (monomial/ndpoly_monomial.c, Ptilde_nd.h, linalg/assign_mul_add_mul_add_mul_add_mul_r.h) ----
+ * fp64, unsplit lattices, the branch g_epsbar != 0 || phmc_exact_poly == 0.  Not built: type NDCLOVER (cloverndpoly), the phmc_exact_poly == 1
+ * branches, the eigenvalue measurement (phmc_compute_ev stays the caller's), fp32 twins, T-split ranks.
+ * assign_mul_add_mul_add_mul_add_mul_r: N = VOLUME/2 (or 0).  Ptilde_ndpsi: Qsq = &Qtm_pm_ndpsi or &Qsw_pm_ndpsi, any other ends the program
+ * with a message; phmc_cheb_evmin / phmc_cheb_evmax are read at call time (weak references: a host program without them cannot call it).
+ * The three bodies take what the reference's bodies read from the monomial; the caller keeps ndpoly_set_global_parameter (g_mubar, g_epsbar)
+ * and, for the heatbath, draws the Gaussian field into pf / pf2 itself.  They end the program with a message when phmc_exact_poly == 1.
+ *   _derivative  ndpoly_monomial.c:69-117, added to hf->derivative under the flush rules of tmlqcd_hip_ndrat_derivative; returns 0
+ *   _heatbath    :179-209, 255-256: pf / pf2 = Ptilde B^dagger Q eta, *energy0 = |eta|^2; returns 0
+ *   _acc         :282-368: *energy1 = mnl->energy1; returns the number of correction steps taken */
+void assign_mul_add_mul_add_mul_add_mul_r(spinor *const R, spinor *const S, spinor *const U, spinor *const V, const double c1, const double c2,
+                                          const double c3, const double c4, const int N);
+void Ptilde_ndpsi(spinor *R_s, spinor *R_c, double *dd, int n, spinor *S_s, spinor *S_c, matrix_mult_nd Qsq);
+int tmlqcd_hip_ndpoly_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const _Complex double *MDPolyRoots,
+                                 const int MDPolyDegree, const double MDPolyLocNormConst, const double EVMaxInv);
+int tmlqcd_hip_ndpoly_heatbath(spinor *const pf, spinor *const pf2, const _Complex double *MDPolyRoots, const int MDPolyDegree,
+                               const double MDPolyLocNormConst, const double EVMaxInv, const double *PtildeCoefs, const int PtildeDegree,
+                               const double EVMin, double *energy0);
+int tmlqcd_hip_ndpoly_acc(spinor *const pf, spinor *const pf2, const _Complex double *MDPolyRoots, const int MDPolyDegree, const double MDPolyLocNormConst,
+                          const double EVMaxInv, const double *MDPolyCoefs, const double *PtildeCoefs, const int PtildeDegree, const double EVMin,
+                          const double PrecisionHfinal, double *energy1);
 /* type NDCLOVERRAT: the same three bodies on the clover doublet (Qsw_pm_ndpsi, Qsw_tau1_sub_const_ndpsi, H_eo_sw_ndpsi).  The derivative also
  * does the clover part of ndrat_monomial.c:80-86, :162-184 on the device: swm / swp zeroed, four sw_spinor_eo per shift, sw_deriv_nd(EE)
  * when trlog is set, sw_all(kappa, c_sw).  The caller runs tmlqcd_hip_sw_term and sw_invert_nd(mubar^2 - epsbar^2) first (:89-91).  The

@@ -338,6 +338,48 @@ int tmhip_cloverrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, 
 int tmhip_cloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
                         double *energy1, int *iters);
 
+/* ---- polynomial monomial (monomial/ndpoly_monomial.c type NDPOLY, Ptilde_nd.c) ----------------------------------------------------
+ * The PHMC monomial of the Wilson twisted-mass doublet, branch g_epsbar != 0 || phmc_exact_poly == 0 of its three bodies.  fp64 one-parity
+ * fields of this context, unsplit lattices only.  n = MDPolyDegree (polynomial degree + 1), roots = the 2n - 2 complex MDPolyRoots as
+ * (re, im) pairs, Cpol = sqrt(MDPolyLocNormConst), invmaxev = EVMaxInv.  Q_tau1_sub_const_ndpsi takes invmaxev from the argument, Qtm_ndpsi /
+ * Qtm_dagger_ndpsi / Qtm_pm_ndpsi inside the bodies from tmhip_set_nd: the three bodies refuse, before any launch, an invmaxev that is not
+ * the one of tmhip_set_nd.
+ * Not built: type NDCLOVER (cloverndpoly), the phmc_exact_poly == 1 branches (P_ndpsi, Qtau1_P_ndpsi, Qtm_pm_sub_const_nrm_psi, Ptm_pm_psi),
+ * Qtm_pm_ndbipsi, the eigenvalue measurement, fp32 twins, T-split ranks; degree_of_polynomial_nd / degree_of_Ptilde and the Chebyshev
+ * coefficient routines are host scalar code and stay the reference's. */
+/* assign_mul_add_mul_add_mul_add_mul_r(R,S,U,V,c1,c2,c3,c4,VOLUME/2): R = c1 R + c2 S + c3 U + c4 V in that order; the fields may alias */
+int tmhip_assign_mul_add_mul_add_mul_add_mul_r(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, tmhip_field *U, tmhip_field *V, double c1, double c2,
+                                               double c3, double c4);
+/* the same kernel as the monomial uses it: out = c1 A + c2 B + c3 C + c4 D for both flavours of a doublet in one launch; out_s may be any of
+ * A_s .. D_s and out_c any of A_c .. D_c; an output that is an input of the OTHER flavour is refused (other blocks of the launch read it) */
+int tmhip_comb4_ndpsi(tmhip_ctx *ctx, tmhip_field *out_s, tmhip_field *out_c, tmhip_field *A_s, tmhip_field *A_c, tmhip_field *B_s, tmhip_field *B_c,
+                      tmhip_field *C_s, tmhip_field *C_c, tmhip_field *D_s, tmhip_field *D_c, double c1, double c2, double c3, double c4);
+/* Ptilde_ndpsi(R_s,R_c,dd,n,S_s,S_c,Qsq)   Ptilde_nd.c:102-203: Clenshaw's recursion over the n Chebyshev coefficients on [evmin, evmax]
+ * (phmc_cheb_evmin / phmc_cheb_evmax), Qsq = op (TMHIP_ND_OP_QTM_PM or TMHIP_ND_OP_QSW_PM, the latter with a valid sw_inv_nd).  The copies of
+ * the reference are a rotation of three work doublets the context owns: a step is one Qsq and one launch of the four-term kernel.  S is not
+ * modified, R may be S flavour by flavour (R_s = S_s, R_c = S_c; R_s = S_c or R_c = S_s is refused).  n < 1 is refused. */
+int tmhip_Ptilde_ndpsi(tmhip_ctx *ctx, tmhip_field *R_s, tmhip_field *R_c, const double *coefs, int n, tmhip_field *S_s, tmhip_field *S_c, double evmin,
+                       double evmax, int op);
+/* ndpoly_derivative   ndpoly_monomial.c:79-117, ADDED to the accumulator of tmhip_deriv_Sb with forcefactor = -Cpol invmaxev.  pf is only read.
+ * The ascending chain chi[1 .. n-2] stays in HBM (2 (n - 2) fields; chi[0] is pf).  The descending loop runs in groups of G = "poly_batch"
+ * steps (tmhip_set_option): 6 G + 2 work fields per group (G + 1 running chi_hi doublets, the H_eo_tm_ndpsi of chi[j-1] and of chi_hi per
+ * step) and ONE tmhip_deriv_Sb_batch launch per parity with 2 G pairs; "poly_batch" 1 is the reference's call order on tmhip_deriv_Sb.
+ * Work fields that a call with a smaller G or n no longer needs are freed at its start.
+ * Refused before the first launch, the accumulator untouched: a failed allocation (the force then frees all of its work fields, so a retry
+ * with a smaller "poly_batch" starts from nothing), n < 3, a T-split context or its loopback rehearsal, fp32 / FULL fields or fields of
+ * another stride, no gauge field, an invmaxev other than that of tmhip_set_nd. */
+int tmhip_ndpoly_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *roots, int n, double Cpol, double invmaxev);
+/* ndpoly_heatbath   :179-209, 255-256 without the RANLUX lines and phmc_compute_ev (the caller's, as for tmhip_ndrat_heatbath): pf holds
+ * the Gaussian field on entry and Ptilde B^dagger Q eta on exit, *energy0 = |eta|^2; the chain ping-pongs between two doublets */
+int tmhip_ndpoly_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *roots, int n, double Cpol, double invmaxev,
+                          const double *ptilde_coefs, int ptilde_n, double evmin, double evmax, double *energy0);
+/* ndpoly_acc   :282-368: the chain, Ener[0] = |B pf|^2, then up to seven correction steps in the reference's alternating order with its
+ * binomial bookkeeping and its stop rule |Ener[j] - Ener[j-1]| < precision_hfinal; *energy1 = Ener at the index the reference ends with,
+ * *corrections = steps taken (1 .. 7).  md_coefs: the n MDPolyCoefs.  ener (may be NULL): Ener[0 .. 7], zero beyond the last step taken. */
+int tmhip_ndpoly_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *roots, int n, double Cpol, double invmaxev,
+                     const double *md_coefs, const double *ptilde_coefs, int ptilde_n, double evmin, double evmax, double precision_hfinal,
+                     double *energy1, int *corrections, double *ener /* 8 */);
+
 /* Clover part of the force (monomial/cloverdet_monomial.c:110-147): the insertion matrices swm / swp (clover_leaf.c:141) are
  * device-resident; zero them, accumulate the spinor outer products (operator/clover_deriv.c:252) and the tr-log term
  * (clover_deriv.c:72; needs sw_inv of that parity), then tmhip_sw_all (operator/clover_accumulate_deriv.c:58) adds the sixteen
@@ -623,6 +665,12 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                measured at 16^4 and 32^4 with np = 12, profiles/r08_rat_speed.log): one tmhip_deriv_Sb_batch launch per parity and group
  *                and, for the clover types (ndcloverrat, cloverrat), one tmhip_sw_spinor_eo_batch launch per parity and group; 1: the per-call
  *                tmhip_sw_spinor_eo kernel in the reference's order
+ *   "poly_batch" steps of the descending loop per group of tmhip_ndpoly_derivative (clamped to [1, 32], default 12: with n = 49 the fastest
+ *                of 1 / 2 / 4 / 12 / 32 at 16^4; at 32^4 32 is 2.7 % faster but holds 194 work fields instead of 74, 12 GB more,
+ *                profiles/r14_poly_speed.log): one tmhip_deriv_Sb_batch launch per parity and group; 1: tmhip_deriv_Sb per pair in the
+ *                reference's order
+ *   "poly_fail_alloc" k (tests only; default 0 = off): the k-th work-field allocation of the polynomial monomial from now on fails, once,
+ *                the way an exhausted device makes it fail
  *   "gauge_global_sums" 0 (default) | 1: tmhip_measure_plaquette / _gauge_action / _rectangles return the rank's own share (0: the reference's value
  *                before its MPI_Allreduce) or the sum over the ranks of a T split (1: its return value; needs the communicator, like parallel = 1)
  *   "csg_batch" 1 (default) | 0: tmhip_chrono_guess on the batched kernels (tmhip_multi_scalar_prod, tmhip_multi_assign_diff_mul, tmhip_lincomb)

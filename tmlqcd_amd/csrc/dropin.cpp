@@ -27,6 +27,9 @@ extern double g_c_sw __attribute__((weak));                       /* global.h:19
 extern double g_mubar __attribute__((weak));                       /* global.h:202: the doublet's twist ... */
 extern double g_epsbar __attribute__((weak));                      /* ... and its flavour splitting */
 extern double phmc_invmaxev __attribute__((weak));                 /* phmc.h:31 */
+extern double phmc_cheb_evmin __attribute__((weak));               /* phmc.h:29: the interval of the Chebyshev sums (Ptilde_ndpsi) */
+extern double phmc_cheb_evmax __attribute__((weak));
+extern int phmc_exact_poly __attribute__((weak));                  /* phmc.c: 1 selects the branches of ndpoly_monomial.c that are not built */
 extern double mixcg_innereps __attribute__((weak));               /* read_input.h:112 (only needed by mixed_cg_her) */
 extern int mixcg_maxinnersolverit __attribute__((weak));          /* read_input.h:113 */
 extern int g_sloppy_precision __attribute__((weak));              /* global.h:95 */
@@ -1159,6 +1162,70 @@ int tmlqcd_hip_polyakov_loop_dir(const int nstore, const int dir) {
   fprintf(ofs, "%4d\t%2d\t%25.16e\t%25.16e\n", nstore, dir, pl[0], pl[1]);
   fclose(ofs);
   return 0;
+}
+
+// ------------------------------------------------------------------ polynomial monomial NDPOLY (poly.hip)
+/* linalg/assign_mul_add_mul_add_mul_add_mul_r.c: R = c1 R + c2 S + c3 U + c4 V, N = VOLUME/2 (the only length its callers use) */
+void assign_mul_add_mul_add_mul_add_mul_r(spinor *const R, spinor *const S, spinor *const U, spinor *const V, const double c1, const double c2,
+                                          const double c3, const double c4, const int N) {
+  tmhip_ctx *c = ses.refresh(false);
+  if (N == 0) return;
+  if (N != VOLUME / 2) die("assign_mul_add_mul_add_mul_add_mul_r: N must be VOLUME/2");
+  tmhip_field *fs = in(c, S, TMHIP_FIELD_EO), *fu = in(c, U, TMHIP_FIELD_EO), *fv = in(c, V, TMHIP_FIELD_EO), *fr = in(c, R, TMHIP_FIELD_EO);
+  CK(tmhip_assign_mul_add_mul_add_mul_add_mul_r(c, fr, fs, fu, fv, c1, c2, c3, c4));
+  done(c, R);
+}
+/* Ptilde_nd.c:102-203 with Qsq = Qtm_pm_ndpsi or Qsw_pm_ndpsi; the interval is phmc_cheb_evmin / phmc_cheb_evmax at call time */
+void Ptilde_ndpsi(spinor *R_s, spinor *R_c, double *dd, int n, spinor *S_s, spinor *S_c, matrix_mult_nd Qsq) {
+  if (Qsq != &Qtm_pm_ndpsi && Qsq != &Qsw_pm_ndpsi) die("Ptilde_ndpsi: only Qsq = Qtm_pm_ndpsi / Qsw_pm_ndpsi runs on the device");
+  if (!&phmc_cheb_evmin || !&phmc_cheb_evmax) die("Ptilde_ndpsi: the host program has no phmc_cheb_evmin / phmc_cheb_evmax");
+  const double evmin = phmc_cheb_evmin, evmax = phmc_cheb_evmax;
+  apply2(ses.refresh_nd("Ptilde_ndpsi"), R_s, R_c, S_s, S_c, [&](Ctx c, Fld frs, Fld frc, Fld fss, Fld fsc) {
+    CK(tmhip_Ptilde_ndpsi(c, frs, frc, dd, n, fss, fsc, evmin, evmax, Qsq == &Qsw_pm_ndpsi ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM));
+  });
+}
+// the three bodies run with g_mubar / g_epsbar of the host (ndpoly_set_global_parameter has set them) and phmc_invmaxev = the monomial's EVMaxInv
+static tmhip_ctx *ndpoly_refresh(const char *who, const double EVMaxInv) {
+  if (&phmc_exact_poly && phmc_exact_poly == 1) {
+    char m[160];
+    snprintf(m, sizeof(m), "%s: the phmc_exact_poly == 1 branches are not built", who);
+    die(m);
+  }
+  tmhip_ctx *c = ses.refresh_nd(who);
+  CK(tmhip_set_nd(c, &g_mubar ? g_mubar : 0., &g_epsbar ? g_epsbar : 0., EVMaxInv));
+  return c;
+}
+/* ndpoly_monomial.c:69-117; Cpol = sqrt(MDPolyLocNormConst) (:552) */
+int tmlqcd_hip_ndpoly_derivative(hamiltonian_field_t *const hf, spinor *const pf, spinor *const pf2, const _Complex double *MDPolyRoots,
+                                 const int MDPolyDegree, const double MDPolyLocNormConst, const double EVMaxInv) {
+  tmhip_ctx *c = ndpoly_refresh("tmlqcd_hip_ndpoly_derivative", EVMaxInv);
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  force_begin(c);
+  CK(tmhip_ndpoly_derivative(c, fu, fd, (const double *)MDPolyRoots, MDPolyDegree, sqrt(MDPolyLocNormConst), EVMaxInv));
+  force_end(hf);
+  return 0;
+}
+/* ndpoly_monomial.c:179-209, 255-256 on the Gaussian field the caller has drawn into pf / pf2; phmc_cheb_evmax = 1 (:561) */
+int tmlqcd_hip_ndpoly_heatbath(spinor *const pf, spinor *const pf2, const _Complex double *MDPolyRoots, const int MDPolyDegree,
+                               const double MDPolyLocNormConst, const double EVMaxInv, const double *PtildeCoefs, const int PtildeDegree,
+                               const double EVMin, double *energy0) {
+  tmhip_ctx *c = ndpoly_refresh("tmlqcd_hip_ndpoly_heatbath", EVMaxInv);
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  CK(tmhip_ndpoly_heatbath(c, fu, fd, (const double *)MDPolyRoots, MDPolyDegree, sqrt(MDPolyLocNormConst), EVMaxInv, PtildeCoefs, PtildeDegree, EVMin, 1.0,
+                           energy0));
+  done(c, pf); done(c, pf2);
+  return 0;
+}
+/* ndpoly_monomial.c:282-368; returns the number of correction steps taken */
+int tmlqcd_hip_ndpoly_acc(spinor *const pf, spinor *const pf2, const _Complex double *MDPolyRoots, const int MDPolyDegree, const double MDPolyLocNormConst,
+                          const double EVMaxInv, const double *MDPolyCoefs, const double *PtildeCoefs, const int PtildeDegree, const double EVMin,
+                          const double PrecisionHfinal, double *energy1) {
+  tmhip_ctx *c = ndpoly_refresh("tmlqcd_hip_ndpoly_acc", EVMaxInv);
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  int corrections = 0;
+  CK(tmhip_ndpoly_acc(c, fu, fd, (const double *)MDPolyRoots, MDPolyDegree, sqrt(MDPolyLocNormConst), EVMaxInv, MDPolyCoefs, PtildeCoefs, PtildeDegree, EVMin,
+                      1.0, PrecisionHfinal, energy1, &corrections, nullptr));
+  return corrections;
 }
 
 // ------------------------------------------------------------------ rational monomials (rational.hip)

@@ -206,6 +206,9 @@ struct tmhip_ctx {
   void *nd; int nd_active_shifts;
   void *rat;                          // rational monomials (rational.hip): solution and work fields
   int opt_rat_batch;                  // shifts per deriv_Sb_batch launch of the rat / ndrat force
+  void *poly;                         // polynomial monomial NDPOLY (poly.hip): the Clenshaw work doublets, the chi chain and the group work fields
+  int opt_poly_batch;                 // steps of the descending loop per deriv_Sb_batch launch of tmhip_ndpoly_derivative
+  int opt_poly_fail_alloc;            // tests: > 0 counts down the work-field allocations of poly.hip, the one that reaches 0 fails (once)
   void *mms; int mms_active_shifts;   // single-flavour multi-shift CG (mms.hip): work fields and solver state
   void *flow;                         // gradient flow in progress (flow.hip): two link buffers and Z, from tmhip_flow_begin to tmhip_flow_end
   void *meas;                         // online measurements (meas.hip): partial sums and the pinned results of a call, allocated on first use
@@ -392,6 +395,7 @@ int tmhip_resort_gauge(tmhip_ctx *ctx);   // md_update.hip: stencil gauge copy f
 int tmhip_prepare_clover32(tmhip_ctx *ctx);  // fp32 gauge copy + fp32 scratch / solver fields
 void tmhip_nd_destroy(tmhip_ctx *ctx);   // nd.hip: work fields and state of the doublet
 void tmhip_rat_destroy(tmhip_ctx *ctx);  // rational.hip: solution and work fields of the rational monomials
+void tmhip_poly_destroy(tmhip_ctx *ctx); // poly.hip: work fields of the polynomial monomial
 void tmhip_mms_destroy(tmhip_ctx *ctx);  // mms.hip: work fields and state of the single-flavour multi-shift CG
 void tmhip_flow_destroy(tmhip_ctx *ctx); // flow.hip: the buffers of a gradient flow in progress
 void tmhip_meas_destroy(tmhip_ctx *ctx); // meas.hip: the reduction buffers of the online measurements

@@ -209,6 +209,12 @@ def load_library():
         "tmhip_cloverrat_derivative": [vp, vp, pd, pd, i, d, d, i, i, d, i, C.POINTER(i)],
         "tmhip_cloverrat_heatbath": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
         "tmhip_cloverrat_acc": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
+        "tmhip_assign_mul_add_mul_add_mul_add_mul_r": [vp, vp, vp, vp, vp, d, d, d, d],
+        "tmhip_comb4_ndpsi": [vp] + [vp] * 10 + [d, d, d, d],
+        "tmhip_Ptilde_ndpsi": [vp, vp, vp, pd, i, vp, vp, d, d, i],
+        "tmhip_ndpoly_derivative": [vp, vp, vp, pd, i, d, d],
+        "tmhip_ndpoly_heatbath": [vp, vp, vp, pd, i, d, d, pd, i, d, d, pd],
+        "tmhip_ndpoly_acc": [vp, vp, vp, pd, i, d, d, pd, pd, i, d, d, d, pd, C.POINTER(i), pd],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -1050,6 +1056,52 @@ class Lattice:
         it, e = C.c_int(), C.c_double()
         _ck(self.lib.tmhip_ndrat_acc(self.h, pf_up.h, pf_dn.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "ndrat_acc")
         return e.value, it.value
+
+    # --- polynomial monomial (monomial/ndpoly_monomial.c NDPOLY, Ptilde_nd.c; poly.hip) ----------------------------------
+    @staticmethod
+    def _ca(z):
+        """complex numbers as (re, im) pairs of doubles"""
+        z = np.ascontiguousarray(np.asarray(z, dtype=np.complex128))
+        return z.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), len(z), z
+
+    def assign_mul_add_mul_add_mul_add_mul_r(self, R, S, U, V, c1, c2, c3, c4):
+        """linalg/assign_mul_add_mul_add_mul_add_mul_r.c with N = VOLUME/2: R = c1 R + c2 S + c3 U + c4 V"""
+        _ck(self.lib.tmhip_assign_mul_add_mul_add_mul_add_mul_r(self.h, R.h, S.h, U.h, V.h, c1, c2, c3, c4), "assign_mul_add_mul_add_mul_add_mul_r")
+
+    def comb4_ndpsi(self, out, A, B, Cc, D, c1, c2, c3, c4):
+        """out = c1 A + c2 B + c3 C + c4 D for both flavours of a doublet (pairs of fields) in one launch; out may be an input pair"""
+        h = [f.h for p in (out, A, B, Cc, D) for f in p]
+        _ck(self.lib.tmhip_comb4_ndpsi(self.h, *h, c1, c2, c3, c4), "comb4_ndpsi")
+
+    def Ptilde_ndpsi(self, R_s, R_c, coefs, S_s, S_c, evmin, evmax, op="Qtm_pm_ndpsi"):
+        """Ptilde_nd.c:102-203 with Qsq = op and phmc_cheb_evmin / evmax = evmin / evmax; R may be S"""
+        c, n = self._da(coefs)
+        _ck(self.lib.tmhip_Ptilde_ndpsi(self.h, R_s.h, R_c.h, c, n, S_s.h, S_c.h, evmin, evmax, ND_OPS[op]), "Ptilde_ndpsi")
+
+    def ndpoly_derivative(self, pf_up, pf_dn, roots, Cpol, invmaxev, n=None):
+        """ndpoly_monomial.c:79-117, added to the derivative accumulator; roots: the 2n - 2 complex MDPolyRoots (n = MDPolyDegree)."""
+        r, nr, _keep = self._ca(roots)
+        n = nr // 2 + 1 if n is None else n
+        _ck(self.lib.tmhip_ndpoly_derivative(self.h, pf_up.h, pf_dn.h, r, n, Cpol, invmaxev), "ndpoly_derivative")
+
+    def ndpoly_heatbath(self, pf_up, pf_dn, roots, Cpol, invmaxev, ptilde_coefs, evmin, evmax):
+        """ndpoly_monomial.c:179-209, 255-256: pf holds eta on entry, Ptilde B^dagger Q eta on exit; returns energy0."""
+        r, nr, _keep = self._ca(roots)
+        c, nc = self._da(ptilde_coefs)
+        e = C.c_double()
+        _ck(self.lib.tmhip_ndpoly_heatbath(self.h, pf_up.h, pf_dn.h, r, nr // 2 + 1, Cpol, invmaxev, c, nc, evmin, evmax, C.byref(e)), "ndpoly_heatbath")
+        return e.value
+
+    def ndpoly_acc(self, pf_up, pf_dn, roots, Cpol, invmaxev, md_coefs, ptilde_coefs, evmin, evmax, precision_hfinal):
+        """ndpoly_monomial.c:282-368; returns (energy1, corrections, Ener[0 .. 7])."""
+        r, nr, _keep = self._ca(roots)
+        (m, nm), (c, nc) = self._da(md_coefs), self._da(ptilde_coefs)
+        if nm != nr // 2 + 1:
+            raise TmHipError("ndpoly_acc: %d MDPolyCoefs for %d roots" % (nm, nr))
+        e, k, ener = C.c_double(), C.c_int(), (C.c_double * 8)()
+        _ck(self.lib.tmhip_ndpoly_acc(self.h, pf_up.h, pf_dn.h, r, nm, Cpol, invmaxev, m, c, nc, evmin, evmax, precision_hfinal, C.byref(e), C.byref(k), ener),
+            "ndpoly_acc")
+        return e.value, k.value, list(ener)
 
     def ndcloverrat_force(self, chi, mu, rmu, invmaxev, kappa, c_sw, trlog):
         """ndrat_monomial.c:80-86, :114-184 for NDCLOVERRAT given the solutions; needs sw_term + sw_invert_nd on the current links."""

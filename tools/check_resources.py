@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/poly.ru.txt
 """
 import re
 import subprocess
@@ -70,6 +70,8 @@ RULES = [
     (r"^void csg_dot_kernel<\d+>", "batched scalar_prod", 8),
     (r"^void csg_axpy_kernel<\d+>", "batched assign_diff_mul", 8),
     (r"^void csg_lincomb_kernel<\d+, (true|false)>", "lincomb", 8),
+    # the four-term combination of the polynomial monomial (poly.hip), both flavours of a doublet per launch: a stream like the ones above
+    (r"^(void )?polyhip::comb4_kernel", "four-term combination", 8),
 ]
 
 
