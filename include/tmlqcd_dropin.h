@@ -436,6 +436,33 @@ int tmlqcd_hip_rat_heatbath(spinor *const pf, const double *nu, const double *rn
                             const int rel_prec, double *energy0);
 int tmlqcd_hip_rat_acc(spinor *const pf, const double *mu, const double *rmu, const int np, const int max_iter, const double eps_sq,
                        const int rel_prec, double *energy1);
+/* ---- correction monomials (monomial/ratcor_monomial.c types RATCOR / CLOVERRATCOR, monomial/ndratcor_monomial.c types NDRATCOR /
+ * NDCLOVERRATCOR): the series loops of the heatbath (ratcor_monomial.c:85-110, ndratcor_monomial.c:88-123) and of the acceptance step
+ * (:151-168, :166-187) with apply_Z_psi / apply_Z_ndpsi inside, everything but pf (pf2) in HBM.  mu / rmu / A: rational_t::mu, rmu, A with np
+ * entries; accprec is the solver's squared precision and the stopping threshold of the series (mnl->accprec); max_iter = mnl->maxiter,
+ * rel_prec = g_relative_precision_flag.  The caller draws the Gaussian field into pf (pf2) before the heatbath, which returns *energy0 =
+ * |eta|^2; the acceptance step returns *energy1.  *napp (may be NULL): applications of Z.  Return value: what the call adds to mnl->iter0.
+ * The single-flavour bodies run at g_mu = g_mu3 = 0, the doublet bodies at g_mu3 = 0 and with g_mubar, g_epsbar as the doublet operators read
+ * them; the globals are left alone.  Clover types: the caller runs tmlqcd_hip_sw_term and tmlqcd_hip_sw_invert(EE, 0.), respectively
+ * sw_invert_nd(mubar^2 - epsbar^2), first, as the reference's bodies do; otherwise the call ends the program with a message.
+ * The reference's loops can apply Z a seventh time and then read past coefs[6]; these bodies end the program with a message naming delta and
+ * accprec when the sixth application leaves delta >= accprec.  Unsplit lattices only.  Not built: check_C_psi / check_C_ndpsi, phmc_compute_ev. */
+int tmlqcd_hip_ratcor_heatbath(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                               const double accprec, const int rel_prec, double *energy0, int *napp);
+int tmlqcd_hip_ratcor_acc(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter, const double accprec,
+                          const int rel_prec, double *energy1, int *napp);
+int tmlqcd_hip_cloverratcor_heatbath(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                                     const double accprec, const int rel_prec, double *energy0, int *napp);
+int tmlqcd_hip_cloverratcor_acc(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                                const double accprec, const int rel_prec, double *energy1, int *napp);
+int tmlqcd_hip_ndratcor_heatbath(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np,
+                                 const int max_iter, const double accprec, const int rel_prec, double *energy0, int *napp);
+int tmlqcd_hip_ndratcor_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                            const double accprec, const int rel_prec, double *energy1, int *napp);
+int tmlqcd_hip_ndcloverratcor_heatbath(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np,
+                                       const int max_iter, const double accprec, const int rel_prec, double *energy0, int *napp);
+int tmlqcd_hip_ndcloverratcor_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np,
+                                  const int max_iter, const double accprec, const int rel_prec, double *energy1, int *napp);
 
 /* ---- ILDG gauge configurations: replaces io/gauge_read.o and io/gauge_write.o of libio.a -- */
 typedef struct { unsigned int suma, sumb; } DML_Checksum;                        /* io/dml.h:34-37 */

@@ -338,6 +338,55 @@ int tmhip_cloverrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, 
 int tmhip_cloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
                         double *energy1, int *iters);
 
+/* ---- correction monomials (monomial/ratcor_monomial.c types RATCOR / CLOVERRATCOR, monomial/ndratcor_monomial.c types NDRATCOR /
+ * NDCLOVERRATCOR) -----------------------------------------------------------------------------------------------------------------
+ * fp64 one-parity fields of this context, unsplit lattices only: a T-split context or its loopback rehearsal, fp32 or FULL fields and np
+ * outside [1, 32] are refused with a message, before any launch.  The two streams first:
+ *   tmhip_rat_sum[_nd]     out = c (in + rmu_{np-1} chi_{np-1} + ... + rmu_0 chi_0) in ONE launch for one flavour or both, added in that order
+ *                          (ratcor_monomial.c:192-196): the bits of tmhip_assign, np tmhip_assign_add_mul_r and, for c != 1, tmhip_mul_r
+ *                          (:205, c = A^2).  out may be in; out may not be a chi_j.
+ *   tmhip_diff_sqnorm[_nd] k = k - l and *out = |k_up|^2 (+ |k_dn|^2) in one launch and one synchronisation (:211-212,
+ *                          ndratcor_monomial.c:238-240): the bits of tmhip_diff and tmhip_square_norm (their sum for two flavours),
+ *                          the same bits from call to call.  Rank-local (a context that sums over ranks is refused).
+ * tmhip_apply_Z / tmhip_apply_Z_nd: k = Z l = (Q^2 (A R)^2 - 1) l with R phi = phi + sum_j rmu_j (Q^2 + mu_j^2)^-1 phi, the statements of
+ * ratcor_monomial.c:183-218 / ndratcor_monomial.c:202-245: solve, R, solve, R, times A^2, Q^2, minus l, norm.  op = TMHIP_OP_QTM_PM /
+ * TMHIP_OP_QSW_PM (Qtm_pm_psi / Qsw_pm_psi), for _nd TMHIP_ND_OP_QTM_PM / TMHIP_ND_OP_QSW_PM (Qtm_pm_ndpsi / Qsw_pm_ndpsi); the solves are
+ * tmhip_cg_mms_tm / tmhip_cg_mms_tm_nd_op with max_iter, eps_sq, rel_prec, into fields the context owns (those of the rat monomials).
+ * *delta = |k|^2, *iters = the first solve's return value (what mnl->iter0 accumulates).  They run with the context's mu / mu3 as they are;
+ * k may not be l.  Option "ratcor_fused" (tmhip_set_option) 1 (default): tmhip_rat_sum per application of R, the second with c = A^2, and
+ * tmhip_diff_sqnorm; 0: the reference's call sequence on the single entry points.  Both give the same bits.
+ * The four bodies, op as above (the clover types are the same functions with the clover operator):
+ *   *_heatbath  ratcor_monomial.c:85-110 / ndratcor_monomial.c:88-123 without the random numbers: pf (and pf_dn) hold the Gaussian field eta on
+ *               entry and B eta on exit, *energy0 = |eta|^2
+ *   *_acc       :151-168 / :166-187: *energy1 = pf . (1 + sum_i c_i Z^i) pf; the caller forms energy1 - energy0
+ * with the reference's coefficient tables, its up0 / up1 swap and its break rule.  accprec is both the solver's eps_sq and the stopping
+ * threshold of the series, as in the reference (:90,106).  *napp = applications of Z, *iters = the sum of their first solves' return
+ * values.  The single-flavour bodies run at twisted mass 0 (mu = mu3 = 0, :67-68,131-132), the doublet bodies with mu3 = 0 (:73,144); the
+ * context's values are back on every path out, errors included.
+ * The reference's loops run to i < 8 over coefs[6]: its seventh application of Z reads past the table.  These bodies apply Z at most SIX times;
+ * if delta >= accprec after the sixth they fail with a message that names delta and accprec.
+ * Clover types: the clover term is the caller's, as for tmhip_cloverrat_* / tmhip_ndcloverrat_*: tmhip_sw_term and tmhip_sw_invert(EE, 0.)
+ * (ratcor_monomial.c:75-76,137-138), respectively tmhip_sw_term and tmhip_sw_invert_nd(mubar^2 - epsbar^2) (ndratcor_monomial.c:77-78,146-147),
+ * on the current links before the call; a missing or foreign clover term is refused exactly as those functions refuse it.
+ * Not built: check_C_psi / check_C_ndpsi, fp32 fields, T-split lattices, phmc_compute_ev. */
+int tmhip_rat_sum(tmhip_ctx *ctx, tmhip_field *out, tmhip_field *in, tmhip_field *const *chi, const double *rmu, int np, double c);
+int tmhip_rat_sum_nd(tmhip_ctx *ctx, tmhip_field *out_up, tmhip_field *out_dn, tmhip_field *in_up, tmhip_field *in_dn, tmhip_field *const *chi_up,
+                     tmhip_field *const *chi_dn, const double *rmu, int np, double c);
+int tmhip_diff_sqnorm(tmhip_ctx *ctx, tmhip_field *k, tmhip_field *l, double *out);
+int tmhip_diff_sqnorm_nd(tmhip_ctx *ctx, tmhip_field *k_up, tmhip_field *k_dn, tmhip_field *l_up, tmhip_field *l_dn, double *out);
+int tmhip_apply_Z(tmhip_ctx *ctx, tmhip_field *k, tmhip_field *l, const double *mu, const double *rmu, double A, int np, int max_iter, double eps_sq,
+                  int rel_prec, int op, double *delta, int *iters);
+int tmhip_apply_Z_nd(tmhip_ctx *ctx, tmhip_field *k_up, tmhip_field *k_dn, tmhip_field *l_up, tmhip_field *l_dn, const double *mu, const double *rmu, double A,
+                     int np, int max_iter, double eps_sq, int rel_prec, int op, double *delta, int *iters);
+int tmhip_ratcor_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, double A, int np, int max_iter, double accprec, int rel_prec,
+                          int op, double *energy0, int *napp, int *iters);
+int tmhip_ratcor_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, double A, int np, int max_iter, double accprec, int rel_prec, int op,
+                     double *energy1, int *napp, int *iters);
+int tmhip_ndratcor_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, double A, int np, int max_iter,
+                            double accprec, int rel_prec, int op, double *energy0, int *napp, int *iters);
+int tmhip_ndratcor_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, double A, int np, int max_iter,
+                       double accprec, int rel_prec, int op, double *energy1, int *napp, int *iters);
+
 /* ---- polynomial monomial (monomial/ndpoly_monomial.c type NDPOLY, Ptilde_nd.c) ----------------------------------------------------
  * The PHMC monomial of the Wilson twisted-mass doublet, branch g_epsbar != 0 || phmc_exact_poly == 0 of its three bodies.  fp64 one-parity
  * fields of this context, unsplit lattices only.  n = MDPolyDegree (polynomial degree + 1), roots = the 2n - 2 complex MDPolyRoots as
@@ -669,6 +718,9 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                of 1 / 2 / 4 / 12 / 32 at 16^4; at 32^4 32 is 2.7 % faster but holds 194 work fields instead of 74, 12 GB more,
  *                profiles/r14_poly_speed.log): one tmhip_deriv_Sb_batch launch per parity and group; 1: tmhip_deriv_Sb per pair in the
  *                reference's order
+ *   "ratcor_fused" 1 (default) | 0: tmhip_apply_Z[_nd] and the bodies of the correction monomials -- 1: one tmhip_rat_sum launch per application
+ *                of R (all np solutions of both flavours, A^2 folded into the second) and one tmhip_diff_sqnorm launch with one synchronisation;
+ *                0: the reference's call sequence on tmhip_assign / _assign_add_mul_r / _mul_r / _diff / _square_norm.  The same bits either way.
  *   "poly_fail_alloc" k (tests only; default 0 = off): the k-th work-field allocation of the polynomial monomial from now on fails, once,
  *                the way an exhausted device makes it fail
  *   "gauge_global_sums" 0 (default) | 1: tmhip_measure_plaquette / _gauge_action / _rectangles return the rank's own share (0: the reference's value

@@ -158,6 +158,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
   ctx->opt_nd_fused = 1; ctx->invmaxev = 1.0;
   ctx->opt_rat_batch = 12;
   ctx->opt_poly_batch = 12;
+  ctx->opt_ratcor_fused = 1;
   ctx->opt_csg_batch = 1;
   ctx->gauge_recon_dev = -1.0;
   ctx->opt_gauge_pack = -1; ctx->opt_gauge_pack_rot = -1;
@@ -341,6 +342,7 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "nd_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_fused must be 0 (two single-flavour stencils + a mixing pass) or 1 (doublet stencil)"); ctx->opt_nd_fused = value; }
   else if (!strcmp(name, "rat_batch")) ctx->opt_rat_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
   else if (!strcmp(name, "poly_batch")) ctx->opt_poly_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
+  else if (!strcmp(name, "ratcor_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("ratcor_fused must be 0 (the reference's call sequence on the single kernels) or 1 (rat_sum and diff_sqnorm)"); ctx->opt_ratcor_fused = value; }
   else if (!strcmp(name, "poly_fail_alloc")) ctx->opt_poly_fail_alloc = value < 0 ? 0 : value;
   else if (!strcmp(name, "csg_batch")) { if (value < 0 || value > 1) TMHIP_FAIL("csg_batch must be 0 (complex singles) or 1 (batched kernels)"); ctx->opt_csg_batch = value; }
   else if (!strcmp(name, "gauge_global_sums")) { if (value < 0 || value > 1) TMHIP_FAIL("gauge_global_sums must be 0 (the rank's share) or 1 (summed over the ranks)"); ctx->opt_gauge_global_sums = value; }

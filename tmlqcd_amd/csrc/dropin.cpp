@@ -1333,6 +1333,67 @@ int tmlqcd_hip_cloverrat_acc(spinor *const pf, const double *mu, const double *r
   return iters;
 }
 
+// ------------------------------------------------------------------ correction monomials (ratcor_monomial.c, ndratcor_monomial.c; rational.hip)
+// heatbath: pf (pf2) are updated in place; acc only reads them.  All return the summed return values of the first solve of every Z.
+static int ratcor_call(const char *who, bool heatbath, int op, spinor *const pf, const double *mu, const double *rmu, const double A, const int np,
+                       const int max_iter, const double accprec, const int rel_prec, double *energy, int *napp) {
+  tmhip_ctx *c = ses.refresh_rat(who);
+  tmhip_field *f = in(c, pf, TMHIP_FIELD_EO);
+  int iters = -1, n = 0;
+  CK((heatbath ? tmhip_ratcor_heatbath : tmhip_ratcor_acc)(c, f, mu, rmu, A, np, max_iter, accprec, rel_prec, op, energy, &n, &iters));
+  if (heatbath) done(c, pf);
+  if (napp) *napp = n;
+  return iters;
+}
+static int ndratcor_call(const char *who, bool heatbath, int op, spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A,
+                         const int np, const int max_iter, const double accprec, const int rel_prec, double *energy, int *napp) {
+  tmhip_ctx *c = ses.refresh_nd(who);
+  tmhip_field *fu = in(c, pf, TMHIP_FIELD_EO), *fd = in(c, pf2, TMHIP_FIELD_EO);
+  int iters = -1, n = 0;
+  CK((heatbath ? tmhip_ndratcor_heatbath : tmhip_ndratcor_acc)(c, fu, fd, mu, rmu, A, np, max_iter, accprec, rel_prec, op, energy, &n, &iters));
+  if (heatbath) { done(c, pf); done(c, pf2); }
+  if (napp) *napp = n;
+  return iters;
+}
+/* ratcor_monomial.c:85-110 */
+int tmlqcd_hip_ratcor_heatbath(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                               const double accprec, const int rel_prec, double *energy0, int *napp) {
+  return ratcor_call("tmlqcd_hip_ratcor_heatbath", true, TMHIP_OP_QTM_PM, pf, mu, rmu, A, np, max_iter, accprec, rel_prec, energy0, napp);
+}
+/* ratcor_monomial.c:151-168 */
+int tmlqcd_hip_ratcor_acc(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter, const double accprec,
+                          const int rel_prec, double *energy1, int *napp) {
+  return ratcor_call("tmlqcd_hip_ratcor_acc", false, TMHIP_OP_QTM_PM, pf, mu, rmu, A, np, max_iter, accprec, rel_prec, energy1, napp);
+}
+/* type CLOVERRATCOR, after the caller's tmlqcd_hip_sw_term + tmlqcd_hip_sw_invert(EE, 0.) (:75-76,137-138) */
+int tmlqcd_hip_cloverratcor_heatbath(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                                     const double accprec, const int rel_prec, double *energy0, int *napp) {
+  return ratcor_call("tmlqcd_hip_cloverratcor_heatbath", true, TMHIP_OP_QSW_PM, pf, mu, rmu, A, np, max_iter, accprec, rel_prec, energy0, napp);
+}
+int tmlqcd_hip_cloverratcor_acc(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                                const double accprec, const int rel_prec, double *energy1, int *napp) {
+  return ratcor_call("tmlqcd_hip_cloverratcor_acc", false, TMHIP_OP_QSW_PM, pf, mu, rmu, A, np, max_iter, accprec, rel_prec, energy1, napp);
+}
+/* ndratcor_monomial.c:88-123 */
+int tmlqcd_hip_ndratcor_heatbath(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np,
+                                 const int max_iter, const double accprec, const int rel_prec, double *energy0, int *napp) {
+  return ndratcor_call("tmlqcd_hip_ndratcor_heatbath", true, TMHIP_ND_OP_QTM_PM, pf, pf2, mu, rmu, A, np, max_iter, accprec, rel_prec, energy0, napp);
+}
+/* ndratcor_monomial.c:166-187 */
+int tmlqcd_hip_ndratcor_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
+                            const double accprec, const int rel_prec, double *energy1, int *napp) {
+  return ndratcor_call("tmlqcd_hip_ndratcor_acc", false, TMHIP_ND_OP_QTM_PM, pf, pf2, mu, rmu, A, np, max_iter, accprec, rel_prec, energy1, napp);
+}
+/* type NDCLOVERRATCOR, after the caller's tmlqcd_hip_sw_term + sw_invert_nd(mubar^2 - epsbar^2) (:77-78,146-147) */
+int tmlqcd_hip_ndcloverratcor_heatbath(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np,
+                                       const int max_iter, const double accprec, const int rel_prec, double *energy0, int *napp) {
+  return ndratcor_call("tmlqcd_hip_ndcloverratcor_heatbath", true, TMHIP_ND_OP_QSW_PM, pf, pf2, mu, rmu, A, np, max_iter, accprec, rel_prec, energy0, napp);
+}
+int tmlqcd_hip_ndcloverratcor_acc(spinor *const pf, spinor *const pf2, const double *mu, const double *rmu, const double A, const int np,
+                                  const int max_iter, const double accprec, const int rel_prec, double *energy1, int *napp) {
+  return ndratcor_call("tmlqcd_hip_ndcloverratcor_acc", false, TMHIP_ND_OP_QSW_PM, pf, pf2, mu, rmu, A, np, max_iter, accprec, rel_prec, energy1, napp);
+}
+
 // ------------------------------------------------------------------ molecular dynamics with the links in HBM
 /* update_gauge(step, hf) (update_gauge.c:51-110): U <- restoresu3(exposu3(step P)) U for every link, on the device-resident
  * links; the stencil's gauge copy is re-sorted there too (update_backward_gauge.c:185-242), so an MD step moves no gauge

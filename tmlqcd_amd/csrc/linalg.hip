@@ -256,6 +256,50 @@ __global__ __launch_bounds__(LA_BS, 8) void csg_lincomb_kernel(v2d *P, const Csg
   }
 }
 
+// ---- the two streams of the correction monomials (rational.hip; monomial/ratcor_monomial.c:192-206,211-212, ndratcor_monomial.c:212-240)
+// out = c (in + rmu_{np-1} chi_{np-1} + ... + rmu_0 chi_0) for one flavour or both (blockIdx.z): the accumulator stays in a register,
+// `in` and every chi_j are read once, out is written once.  The additions are those of stream_kernel<0> in the reference's order
+// (j downwards) and the factor is the product of stream_kernel<5>, so the result carries the bits of tmhip_assign, np calls of
+// tmhip_assign_add_mul_r and (c != 1) tmhip_mul_r; c = 1 multiplies by one, which changes nothing.  One site per thread: the np
+// loads of a thread are independent of its sum and the loop is unrolled by four to keep them in flight.  Element-wise: out may be in.
+struct RatSumArgs {
+  const v2d *in[2], *chi[2][TMHIP_RAT_SUM_MAX];
+  v2d *out[2];
+  double rmu[TMHIP_RAT_SUM_MAX], c;
+  int np, ns, N;
+};
+__global__ __launch_bounds__(LA_BS, 8) void rat_sum_kernel(const RatSumArgs a) {
+  const int i = blockIdx.x * LA_BS + threadIdx.x;
+  if (i >= a.N) return;
+  const int f = blockIdx.z;
+  const size_t off = (size_t)blockIdx.y * a.ns + i;
+  v2d acc = a.in[f][off];
+#pragma unroll 4
+  for (int j = a.np - 1; j >= 0; j--) {
+    const double c = a.rmu[j];
+    const v2d b = a.chi[f][j][off];
+    acc = v2d{acc.x + c * b.x, acc.y + c * b.y};
+  }
+  a.out[f][off] = v2d{a.c * acc.x, a.c * acc.y};
+}
+
+// K_f = K_f - L_f and the block sums of |K_f|^2, flavour f = blockIdx.z: the subtraction of stream_kernel<2> and then, on the value just
+// stored, the lines of sqnorm_kernel -- the same per-thread order, block sum and partials layout (flavour f at partials + f * 12 *
+// gridDim.x), so that the final pass below returns the bits of tmhip_diff followed by tmhip_square_norm
+struct DiffSqArgs { v2d *k[2]; const v2d *l[2]; };
+__global__ __launch_bounds__(LA_BS) void diff_sqnorm_kernel(const DiffSqArgs a, int ns, int N, double *partials) {
+  v2d *k = a.k[blockIdx.z] + (size_t)blockIdx.y * ns;
+  const v2d *l = a.l[blockIdx.z] + (size_t)blockIdx.y * ns;
+  double acc = 0.0;
+  const int base = blockIdx.x * LA_BS * LA_UNROLL + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < LA_UNROLL; u++) {
+    const int i = base + u * LA_BS;
+    if (i < N) { const v2d d = k[i] - l[i]; k[i] = d; acc += d.x * d.x + d.y * d.y; }
+  }
+  block_reduce_store(acc, partials + (size_t)blockIdx.z * 12 * gridDim.x);
+}
+
 
 static int check_eo(const tmhip_field *f, const char *who) {
   if (!f || f->kind != TMHIP_FIELD_EO || f->prec != 0) { fprintf(stderr, "[tmlqcd_hip] %s: needs a one-parity (EO) field\n", who); return 1; }
@@ -406,6 +450,66 @@ int tmhip_assign(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, int N) {
   TMHIP_CHECK(hipGetLastError());
   return 0;
 }
+
+int tmhip_rat_sum_nd(tmhip_ctx *ctx, tmhip_field *out_up, tmhip_field *out_dn, tmhip_field *in_up, tmhip_field *in_dn, tmhip_field *const *chi_up,
+                     tmhip_field *const *chi_dn, const double *rmu, int np, double c) {
+  const int nf = out_dn || in_dn || chi_dn ? 2 : 1;
+  const char *who = nf == 2 ? "rat_sum_nd" : "rat_sum";
+  if (np < 1 || np > TMHIP_RAT_SUM_MAX) TMHIP_FAIL("%s: np = %d is outside [1, %d]", who, np, TMHIP_RAT_SUM_MAX);
+  if (!chi_up || !rmu || (nf == 2 && !chi_dn)) TMHIP_FAIL("%s: null argument", who);
+  if (check_eo(out_up, who) || check_eo(in_up, who) || (nf == 2 && (check_eo(out_dn, who) || check_eo(in_dn, who)))) return 1;
+  RatSumArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in[0] = in_up->d; a.out[0] = out_up->d;
+  if (nf == 2) { a.in[1] = in_dn->d; a.out[1] = out_dn->d; }
+  for (int f = 0; f < nf; f++) {
+    tmhip_field *const *chi = f ? chi_dn : chi_up;
+    tmhip_field *o = f ? out_dn : out_up, *in = f ? in_dn : in_up;
+    if (in->ns != out_up->ns || o->ns != out_up->ns) TMHIP_FAIL("%s: fields with different strides", who);
+    for (int j = 0; j < np; j++) {
+      if (check_eo(chi[j], who)) return 1;
+      if (chi[j]->ns != out_up->ns) TMHIP_FAIL("%s: fields with different strides (chi[%d])", who, j);
+      if (chi[j]->d == o->d) TMHIP_FAIL("%s: out is chi[%d] (only `in` may be the output)", who, j);
+      a.chi[f][j] = chi[j]->d;
+    }
+  }
+  if (nf == 2 && (out_up->d == out_dn->d || out_up->d == in_dn->d || out_dn->d == in_up->d)) TMHIP_FAIL("%s: the two flavours share a field", who);
+  for (int j = 0; j < np; j++) a.rmu[j] = rmu[j];
+  a.c = c; a.np = np; a.ns = out_up->ns; a.N = ctx->Vh;
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(rat_sum_kernel, dim3((ctx->Vh + LA_BS - 1) / LA_BS, 12, nf), dim3(LA_BS), 0, ctx->stream, a);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_rat_sum(tmhip_ctx *ctx, tmhip_field *out, tmhip_field *in, tmhip_field *const *chi, const double *rmu, int np, double c) {
+  return tmhip_rat_sum_nd(ctx, out, nullptr, in, nullptr, chi, nullptr, rmu, np, c);
+}
+
+int tmhip_diff_sqnorm_nd(tmhip_ctx *ctx, tmhip_field *k_up, tmhip_field *k_dn, tmhip_field *l_up, tmhip_field *l_dn, double *out) {
+  const int nf = k_dn || l_dn ? 2 : 1;
+  const char *who = nf == 2 ? "diff_sqnorm_nd" : "diff_sqnorm";
+  if (!out) TMHIP_FAIL("%s: null argument", who);
+  if (check_eo(k_up, who) || check_eo(l_up, who) || (nf == 2 && (check_eo(k_dn, who) || check_eo(l_dn, who)))) return 1;
+  if (l_up->ns != k_up->ns || (nf == 2 && (k_dn->ns != k_up->ns || l_dn->ns != k_up->ns))) TMHIP_FAIL("%s: fields with different strides", who);
+  if (nf == 2 && (k_up->d == k_dn->d || k_up->d == l_dn->d || k_dn->d == l_up->d)) TMHIP_FAIL("%s: the two flavours share a field", who);
+  if (tmhip_reduce_over_ranks(ctx)) TMHIP_FAIL("%s: rank-local; on a rank that sums over ranks call tmhip_diff and tmhip_square_norm", who);
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (csg_buffers(ctx)) return 1;
+  DiffSqArgs a;
+  a.k[0] = k_up->d; a.l[0] = l_up->d;
+  a.k[1] = nf == 2 ? k_dn->d : nullptr; a.l[1] = nf == 2 ? l_dn->d : nullptr;
+  const dim3 g = la_grid(ctx->Vh);
+  hipLaunchKernelGGL(diff_sqnorm_kernel, dim3(g.x, g.y, nf), dim3(LA_BS), 0, ctx->stream, a, k_up->ns, ctx->Vh, ctx->csg_partials);
+  hipLaunchKernelGGL(reduce_final_multi_kernel, dim3(nf), dim3(256), 0, ctx->stream, (const double *)ctx->csg_partials, (int)(g.x * g.y), ctx->csg_res_dev);
+  TMHIP_CHECK(hipGetLastError());
+  TMHIP_CHECK(hipMemcpyAsync(ctx->csg_res_host, ctx->csg_res_dev, nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  *out = nf == 2 ? ctx->csg_res_host[0] + ctx->csg_res_host[1] : ctx->csg_res_host[0];   // square_norm(k_up) + square_norm(k_dn), ndratcor_monomial.c:240
+  return tmhip_check_async_error(ctx);
+}
+
+int tmhip_diff_sqnorm(tmhip_ctx *ctx, tmhip_field *k, tmhip_field *l, double *out) { return tmhip_diff_sqnorm_nd(ctx, k, nullptr, l, nullptr, out); }
 
 int tmhip_multi_scalar_prod(tmhip_ctx *ctx, int n, tmhip_field *const *S, tmhip_field *R, int N, double *out) {
   if (csg_check(ctx, n, S, R, "multi_scalar_prod")) return 1;

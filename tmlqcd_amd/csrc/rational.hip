@@ -1,5 +1,5 @@
 // Rational monomials on the device: rat (monomial/rat_monomial.c, types RAT and CLOVERRAT) and ndrat (monomial/ndrat_monomial.c, types
-// NDRAT and NDCLOVERRAT), fp64, unsplit lattices.
+// NDRAT and NDCLOVERRAT), fp64, unsplit lattices; at the end of the file the correction monomials ratcor / ndratcor on top of them.
 //
 // The hot path is the hopping force.  ndrat_derivative calls deriv_Sb four times per shift (ndrat_monomial.c:140-160), rat_derivative
 // twice (rat_monomial.c:124-131); every call reads the same four links per site and does a read-modify-write of the same 32
@@ -492,6 +492,203 @@ int tmhip_cloverrat_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *nu, 
 int tmhip_cloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, int np, int max_iter, double eps_sq, int rel_prec,
                         double *energy1, int *iters) {
   return rat_acc_body(ctx, true, pf, mu, rmu, np, max_iter, eps_sq, rel_prec, energy1, iters);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- correction monomials: RATCOR / CLOVERRATCOR (monomial/ratcor_monomial.c)
+// and NDRATCOR / NDCLOVERRATCOR (monomial/ndratcor_monomial.c)
+// Z = Q^2 (A R)^2 - 1 with R phi = phi + sum_j rmu_j chi_j: two multi-shift solves on the stored solutions, then either the reference's
+// call sequence on the single kernels ("ratcor_fused" 0: 2 np + 2 assign_add_mul_r passes, mul_r, diff and the square_norm per flavour) or
+// one rat_sum launch per application of R (the second with the factor A^2 folded in) and one diff_sqnorm launch with one
+// synchronisation (linalg.hip) -- both kernels reproduce the single calls bit for bit, so the two paths return the same delta and fields.
+// Work fields: w[0..5] are the reference's w_fields[0..5], w[6], w[7] stand for g_chi_up/dn_spinor_field[np].
+//
+// The series loops of the reference run to i < 8 over coefs[6]: a seventh application of Z would read past the table.  The bodies here
+// apply Z at most six times and fail, naming delta and accprec, when the sixth still leaves delta >= accprec.
+static_assert(TMHIP_RAT_SUM_MAX == MSHIFT_MAX_SHIFTS, "tmhip_rat_sum carries one pointer per shift of the multi-shift solvers");
+static const double ratcor_hb_coefs[6] = {1. / 4., -3. / 32., 7. / 128., -77. / 2048., 231. / 8192., -1463. / 65536.};   // ratcor_monomial.c:64, ndratcor_monomial.c:70
+static const double ratcor_acc_coefs[6] = {-1. / 2., 3. / 8., -5. / 16., 35. / 128., -63. / 256., 231. / 1024.};         // ratcor_monomial.c:128, ndratcor_monomial.c:141
+
+// the doublet bodies run with g_mu3 = 0 (ndratcor_monomial.c:73,144): the context's mu3 is put back on every path out
+struct RatMu3Zero {
+  tmhip_ctx *ctx; double mu3;
+  explicit RatMu3Zero(tmhip_ctx *c) : ctx(c), mu3(c->mu3) { c->mu3 = 0.0; }
+  ~RatMu3Zero() { ctx->mu3 = mu3; }
+};
+
+// nd: both flavours (the _dn arguments are used), op: TMHIP_OP_QTM_PM / TMHIP_OP_QSW_PM, with nd TMHIP_ND_OP_QTM_PM / TMHIP_ND_OP_QSW_PM
+struct RatcorZ { bool nd; int op; const double *mu, *rmu; double A; int np, max_iter; double eps_sq; int rel_prec; };
+
+static int ratcor_op_check(tmhip_ctx *ctx, const char *who, bool nd, int op, int np) {
+  const bool sw = nd ? op == TMHIP_ND_OP_QSW_PM : op == TMHIP_OP_QSW_PM;
+  if (!sw && op != (nd ? (int)TMHIP_ND_OP_QTM_PM : (int)TMHIP_OP_QTM_PM))
+    TMHIP_FAIL("%s: operator id %d is not %s", who, op, nd ? "Qtm_pm_ndpsi or Qsw_pm_ndpsi" : "Qtm_pm_psi or Qsw_pm_psi");
+  if (!sw) return rat_prepare(ctx, who, np);
+  return nd ? ndcloverrat_prepare(ctx, who, np) : cloverrat_prepare(ctx, who, np);
+}
+
+// ratcor_monomial.c:183-218 / ndratcor_monomial.c:202-245; k = Z l, *delta = |k|^2, *it0 = the first solve's return value
+static int ratcor_apply_Z(tmhip_ctx *ctx, const RatcorZ &z, tmhip_field *k_up, tmhip_field *k_dn, tmhip_field *l_up, tmhip_field *l_dn, double *delta, int *it0) {
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  const int N = ctx->Vh, np = z.np;
+  if (rat_need(ctx, r->chi_up, np) || (z.nd && rat_need(ctx, r->chi_dn, np)) || rat_need(ctx, r->w + 6, z.nd ? 2 : 1)) return 1;
+  tmhip_field *t_up = r->w[6], *t_dn = r->w[7];
+  const double A2 = z.A * z.A;
+  int it1;
+  auto solve = [&](tmhip_field *q_up, tmhip_field *q_dn, int *it) {
+    return z.nd ? tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, q_up, q_dn, z.mu, np, z.max_iter, z.eps_sq, z.rel_prec, z.op, it)
+                : tmhip_cg_mms_tm(ctx, r->chi_up, q_up, z.mu, np, z.max_iter, z.eps_sq, z.rel_prec, N, z.op, it, nullptr);
+  };
+  auto Qsq = [&]() {   // :209 / :236-237
+    if (!z.nd) return tmhip_apply_op(ctx, z.op, k_up, t_up);
+    return z.op == TMHIP_ND_OP_QSW_PM ? tmhip_Qsw_pm_ndpsi(ctx, k_up, k_dn, t_up, t_dn) : tmhip_Qtm_pm_ndpsi(ctx, k_up, k_dn, t_up, t_dn);
+  };
+  if (solve(l_up, l_dn, it0)) return 1;                                                       // :188 / :208
+  if (ctx->opt_ratcor_fused) {
+    if (tmhip_rat_sum_nd(ctx, k_up, z.nd ? k_dn : nullptr, l_up, z.nd ? l_dn : nullptr, r->chi_up, z.nd ? r->chi_dn : nullptr, z.rmu, np, 1.0)) return 1;
+    if (solve(k_up, k_dn, &it1)) return 1;
+    if (tmhip_rat_sum_nd(ctx, t_up, z.nd ? t_dn : nullptr, k_up, z.nd ? k_dn : nullptr, r->chi_up, z.nd ? r->chi_dn : nullptr, z.rmu, np, A2)) return 1;
+    if (Qsq()) return 1;
+    return tmhip_diff_sqnorm_nd(ctx, k_up, z.nd ? k_dn : nullptr, l_up, z.nd ? l_dn : nullptr, delta);
+  }
+  auto addR = [&]() {   // :193-196, 201-204 / :214-219, 225-230
+    for (int j = np - 1; j >= 0; j--) {
+      if (tmhip_assign_add_mul_r(ctx, k_up, r->chi_up[j], z.rmu[j], N)) return 1;
+      if (z.nd && tmhip_assign_add_mul_r(ctx, k_dn, r->chi_dn[j], z.rmu[j], N)) return 1;
+    }
+    return 0;
+  };
+  if (tmhip_assign(ctx, k_up, l_up, N) || (z.nd && tmhip_assign(ctx, k_dn, l_dn, N))) return 1;   // :192 / :212-213
+  if (addR()) return 1;
+  if (solve(k_up, k_dn, &it1)) return 1;                                                      // :199 / :222
+  if (addR()) return 1;
+  if (tmhip_mul_r(ctx, t_up, A2, k_up, N) || (z.nd && tmhip_mul_r(ctx, t_dn, A2, k_dn, N))) return 1;   // :205 / :231-234
+  if (Qsq()) return 1;
+  if (tmhip_diff(ctx, k_up, k_up, l_up, N) || (z.nd && tmhip_diff(ctx, k_dn, k_dn, l_dn, N))) return 1;   // :211 / :238-239
+  double a, b = 0.0;
+  if (tmhip_square_norm(ctx, k_up, N, 1, &a) || (z.nd && tmhip_square_norm(ctx, k_dn, N, 1, &b))) return 1;   // :212 / :240
+  *delta = z.nd ? a + b : a;
+  return 0;
+}
+
+static int ratcor_args_check(const char *who, bool nd, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, const void *e, const void *napp,
+                             const void *iters) {
+  if (!mu || !rmu || !e || !napp || !iters || !rat_eo(pf_up) || (nd && !rat_eo(pf_dn))) TMHIP_FAIL("%s: null argument or not an fp64 one-parity field", who);
+  if (nd && pf_up->d == pf_dn->d) TMHIP_FAIL("%s: the two flavours share a field", who);
+  return 0;
+}
+static int ratcor_not_converged(const char *who, double delta, double accprec) {
+  TMHIP_FAIL("%s: delta = %.6e is not below accprec = %.6e after the six applications of Z the coefficient table allows", who, delta, accprec);
+}
+
+// ratcor_monomial.c:85-110 / ndratcor_monomial.c:88-123 without the random numbers: pf holds eta on entry
+static int ratcor_heatbath_body(tmhip_ctx *ctx, const char *who, const RatcorZ &z, tmhip_field *pf_up, tmhip_field *pf_dn, double accprec, double *energy0,
+                                int *napp, int *iters) {
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  const int N = ctx->Vh;
+  if (rat_need(ctx, r->w, z.nd ? 4 : 3)) return 1;
+  double ea, eb = 0.0, delta = 0.0;
+  if (tmhip_square_norm(ctx, pf_up, N, 1, &ea) || (z.nd && tmhip_square_norm(ctx, pf_dn, N, 1, &eb))) return 1;   // :87 / :90,93
+  *energy0 = z.nd ? ea + eb : ea;
+  *napp = 0; *iters = 0;
+  if (tmhip_assign(ctx, r->w[0], pf_up, N) || (z.nd && tmhip_assign(ctx, r->w[1], pf_dn, N))) return 1;          // :99 / :110-111
+  tmhip_field *up0 = r->w[0], *dn0 = r->w[1], *up1 = r->w[2], *dn1 = r->w[3];
+  for (int i = 1; i <= 6; i++) {                                                                                  // :103-110 / :115-123
+    int it0;
+    if (ratcor_apply_Z(ctx, z, up1, dn1, up0, dn0, &delta, &it0)) return 1;
+    *napp += 1; *iters += it0;
+    if (tmhip_assign_add_mul_r(ctx, pf_up, up1, ratcor_hb_coefs[i - 1], N) || (z.nd && tmhip_assign_add_mul_r(ctx, pf_dn, dn1, ratcor_hb_coefs[i - 1], N))) return 1;
+    if (delta < accprec) return 0;
+    tmhip_field *t = up0; up0 = up1; up1 = t;
+    t = dn0; dn0 = dn1; dn1 = t;
+  }
+  return ratcor_not_converged(who, delta, accprec);
+}
+
+// ratcor_monomial.c:151-168 / ndratcor_monomial.c:166-187
+static int ratcor_acc_body(tmhip_ctx *ctx, const char *who, const RatcorZ &z, tmhip_field *pf_up, tmhip_field *pf_dn, double accprec, double *energy1, int *napp,
+                           int *iters) {
+  TmhipRat *r = (TmhipRat *)ctx->rat;
+  const int N = ctx->Vh;
+  if (rat_need(ctx, r->w, 6)) return 1;
+  double ea, eb = 0.0, delta = 0.0;
+  int it0;
+  *napp = 0; *iters = 0;
+  if (tmhip_assign(ctx, r->w[4], pf_up, N) || (z.nd && tmhip_assign(ctx, r->w[5], pf_dn, N))) return 1;          // :152 / :167-168
+  tmhip_field *up0 = r->w[0], *dn0 = r->w[1], *up1 = r->w[2], *dn1 = r->w[3];
+  if (ratcor_apply_Z(ctx, z, up0, dn0, pf_up, pf_dn, &delta, &it0)) return 1;                                     // :156 / :172
+  *napp = 1; *iters = it0;
+  if (tmhip_assign_add_mul_r(ctx, r->w[4], up0, ratcor_acc_coefs[0], N) || (z.nd && tmhip_assign_add_mul_r(ctx, r->w[5], dn0, ratcor_acc_coefs[0], N))) return 1;
+  for (int i = 2; i <= 6; i++) {                                                                                  // :159-166 / :176-184
+    if (delta < accprec) break;
+    if (ratcor_apply_Z(ctx, z, up1, dn1, up0, dn0, &delta, &it0)) return 1;
+    *napp += 1; *iters += it0;
+    if (tmhip_assign_add_mul_r(ctx, r->w[4], up1, ratcor_acc_coefs[i - 1], N) || (z.nd && tmhip_assign_add_mul_r(ctx, r->w[5], dn1, ratcor_acc_coefs[i - 1], N))) return 1;
+    tmhip_field *t = up0; up0 = up1; up1 = t;
+    t = dn0; dn0 = dn1; dn1 = t;
+  }
+  if (!(delta < accprec)) return ratcor_not_converged(who, delta, accprec);
+  if (tmhip_scalar_prod_r(ctx, pf_up, r->w[4], N, 1, &ea) || (z.nd && tmhip_scalar_prod_r(ctx, pf_dn, r->w[5], N, 1, &eb))) return 1;   // :168 / :186-187
+  *energy1 = z.nd ? ea + eb : ea;
+  return 0;
+}
+
+extern "C" {
+
+int tmhip_apply_Z(tmhip_ctx *ctx, tmhip_field *k, tmhip_field *l, const double *mu, const double *rmu, double A, int np, int max_iter, double eps_sq,
+                  int rel_prec, int op, double *delta, int *iters) {
+  if (ratcor_op_check(ctx, "apply_Z", false, op, np)) return 1;
+  if (!mu || !rmu || !delta || !iters || !rat_eo(k) || !rat_eo(l)) TMHIP_FAIL("apply_Z: null argument or not an fp64 one-parity field");
+  if (k->d == l->d) TMHIP_FAIL("apply_Z: k is l (l is read again after k has been written)");
+  const RatcorZ z = {false, op, mu, rmu, A, np, max_iter, eps_sq, rel_prec};
+  return ratcor_apply_Z(ctx, z, k, nullptr, l, nullptr, delta, iters);
+}
+
+int tmhip_apply_Z_nd(tmhip_ctx *ctx, tmhip_field *k_up, tmhip_field *k_dn, tmhip_field *l_up, tmhip_field *l_dn, const double *mu, const double *rmu, double A,
+                     int np, int max_iter, double eps_sq, int rel_prec, int op, double *delta, int *iters) {
+  if (ratcor_op_check(ctx, "apply_Z_nd", true, op, np)) return 1;
+  if (!mu || !rmu || !delta || !iters || !rat_eo(k_up) || !rat_eo(k_dn) || !rat_eo(l_up) || !rat_eo(l_dn)) TMHIP_FAIL("apply_Z_nd: null argument or not an fp64 one-parity field");
+  if (k_up->d == l_up->d || k_up->d == l_dn->d || k_dn->d == l_up->d || k_dn->d == l_dn->d || k_up->d == k_dn->d)
+    TMHIP_FAIL("apply_Z_nd: k is l or the two flavours of k share a field (l is read again after k has been written)");
+  const RatcorZ z = {true, op, mu, rmu, A, np, max_iter, eps_sq, rel_prec};
+  return ratcor_apply_Z(ctx, z, k_up, k_dn, l_up, l_dn, delta, iters);
+}
+
+int tmhip_ratcor_heatbath(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, double A, int np, int max_iter, double accprec, int rel_prec,
+                          int op, double *energy0, int *napp, int *iters) {
+  const char *who = op == TMHIP_OP_QSW_PM ? "cloverratcor_heatbath" : "ratcor_heatbath";
+  if (ratcor_op_check(ctx, who, false, op, np) || ratcor_args_check(who, false, pf, nullptr, mu, rmu, energy0, napp, iters)) return 1;
+  RatMuZero mz(ctx, true);   // ratcor_monomial.c:67-68
+  const RatcorZ z = {false, op, mu, rmu, A, np, max_iter, accprec, rel_prec};
+  return ratcor_heatbath_body(ctx, who, z, pf, nullptr, accprec, energy0, napp, iters);
+}
+
+int tmhip_ratcor_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const double *rmu, double A, int np, int max_iter, double accprec, int rel_prec, int op,
+                     double *energy1, int *napp, int *iters) {
+  const char *who = op == TMHIP_OP_QSW_PM ? "cloverratcor_acc" : "ratcor_acc";
+  if (ratcor_op_check(ctx, who, false, op, np) || ratcor_args_check(who, false, pf, nullptr, mu, rmu, energy1, napp, iters)) return 1;
+  RatMuZero mz(ctx, true);   // ratcor_monomial.c:131-132
+  const RatcorZ z = {false, op, mu, rmu, A, np, max_iter, accprec, rel_prec};
+  return ratcor_acc_body(ctx, who, z, pf, nullptr, accprec, energy1, napp, iters);
+}
+
+int tmhip_ndratcor_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, double A, int np, int max_iter,
+                            double accprec, int rel_prec, int op, double *energy0, int *napp, int *iters) {
+  const char *who = op == TMHIP_ND_OP_QSW_PM ? "ndcloverratcor_heatbath" : "ndratcor_heatbath";
+  if (ratcor_op_check(ctx, who, true, op, np) || ratcor_args_check(who, true, pf_up, pf_dn, mu, rmu, energy0, napp, iters)) return 1;
+  RatMu3Zero mz(ctx);   // ndratcor_monomial.c:73
+  const RatcorZ z = {true, op, mu, rmu, A, np, max_iter, accprec, rel_prec};
+  return ratcor_heatbath_body(ctx, who, z, pf_up, pf_dn, accprec, energy0, napp, iters);
+}
+
+int tmhip_ndratcor_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *mu, const double *rmu, double A, int np, int max_iter,
+                       double accprec, int rel_prec, int op, double *energy1, int *napp, int *iters) {
+  const char *who = op == TMHIP_ND_OP_QSW_PM ? "ndcloverratcor_acc" : "ndratcor_acc";
+  if (ratcor_op_check(ctx, who, true, op, np) || ratcor_args_check(who, true, pf_up, pf_dn, mu, rmu, energy1, napp, iters)) return 1;
+  RatMu3Zero mz(ctx);   // ndratcor_monomial.c:144
+  const RatcorZ z = {true, op, mu, rmu, A, np, max_iter, accprec, rel_prec};
+  return ratcor_acc_body(ctx, who, z, pf_up, pf_dn, accprec, energy1, napp, iters);
 }
 
 }  // extern "C"

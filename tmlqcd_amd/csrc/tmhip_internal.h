@@ -206,6 +206,7 @@ struct tmhip_ctx {
   void *nd; int nd_active_shifts;
   void *rat;                          // rational monomials (rational.hip): solution and work fields
   int opt_rat_batch;                  // shifts per deriv_Sb_batch launch of the rat / ndrat force
+  int opt_ratcor_fused;               // 1 (default): apply_Z of the correction monomials on tmhip_rat_sum / tmhip_diff_sqnorm; 0: the reference's call sequence on the singles
   void *poly;                         // polynomial monomial NDPOLY (poly.hip): the Clenshaw work doublets, the chi chain and the group work fields
   int opt_poly_batch;                 // steps of the descending loop per deriv_Sb_batch launch of tmhip_ndpoly_derivative
   int opt_poly_fail_alloc;            // tests: > 0 counts down the work-field allocations of poly.hip, the one that reaches 0 fails (once)
@@ -343,6 +344,7 @@ bool tmhip_fused_dot32_ok(const tmhip_ctx *ctx);
 int tmhip_reduce_finish(tmhip_ctx *ctx, int nblocks, int parallel, double *out);
 int tmhip_rank_sum(tmhip_ctx *ctx);   // linalg.hip: *ctx->result_dev summed over the ranks in place, enqueued on ctx->stream (callers check tmhip_reduce_over_ranks)
 #define RAT_MAX_PAIRS 64   // pairs per launch of the batched force kernels (rational.hip deriv_Sb_batch, clover.hip sw_spinor_eo_batch)
+#define TMHIP_RAT_SUM_MAX 32   // fields per launch of tmhip_rat_sum (linalg.hip): MSHIFT_MAX_SHIFTS of the solvers that make them
 // After a host-visible synchronisation of a T-split rank: non-zero (with a message) when a bounded device-side wait for the
 // neighbours' faces gave up ("flag_timeout_ms") or the communicator reports an asynchronous error, i.e. the result just
 // synchronised cannot be trusted.  Reported once per occurrence -- the error word is cleared, the next call starts clean.

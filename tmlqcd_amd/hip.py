@@ -209,6 +209,15 @@ def load_library():
         "tmhip_cloverrat_derivative": [vp, vp, pd, pd, i, d, d, i, i, d, i, C.POINTER(i)],
         "tmhip_cloverrat_heatbath": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
         "tmhip_cloverrat_acc": [vp, vp, pd, pd, i, i, d, i, pd, C.POINTER(i)],
+        "tmhip_rat_sum": [vp, vp, vp, C.POINTER(vp), pd, i, d],
+        "tmhip_rat_sum_nd": [vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), pd, i, d],
+        "tmhip_diff_sqnorm": [vp, vp, vp, pd], "tmhip_diff_sqnorm_nd": [vp, vp, vp, vp, vp, pd],
+        "tmhip_apply_Z": [vp, vp, vp, pd, pd, d, i, i, d, i, i, pd, C.POINTER(i)],
+        "tmhip_apply_Z_nd": [vp, vp, vp, vp, vp, pd, pd, d, i, i, d, i, i, pd, C.POINTER(i)],
+        "tmhip_ratcor_heatbath": [vp, vp, pd, pd, d, i, i, d, i, i, pd, C.POINTER(i), C.POINTER(i)],
+        "tmhip_ratcor_acc": [vp, vp, pd, pd, d, i, i, d, i, i, pd, C.POINTER(i), C.POINTER(i)],
+        "tmhip_ndratcor_heatbath": [vp, vp, vp, pd, pd, d, i, i, d, i, i, pd, C.POINTER(i), C.POINTER(i)],
+        "tmhip_ndratcor_acc": [vp, vp, vp, pd, pd, d, i, i, d, i, i, pd, C.POINTER(i), C.POINTER(i)],
         "tmhip_assign_mul_add_mul_add_mul_add_mul_r": [vp, vp, vp, vp, vp, d, d, d, d],
         "tmhip_comb4_ndpsi": [vp] + [vp] * 10 + [d, d, d, d],
         "tmhip_Ptilde_ndpsi": [vp, vp, vp, pd, i, vp, vp, d, d, i],
@@ -1177,6 +1186,68 @@ class Lattice:
         it, e = C.c_int(), C.c_double()
         _ck(self.lib.tmhip_cloverrat_acc(self.h, pf.h, m, r, n, max_iter, eps_sq, rel_prec, C.byref(e), C.byref(it)), "cloverrat_acc")
         return e.value, it.value
+
+    # --- correction monomials (monomial/ratcor_monomial.c, monomial/ndratcor_monomial.c; rational.hip, linalg.hip) -------
+    def rat_sum(self, out, inp, chi, rmu, c=1.0):
+        """out = c (in + sum_j rmu_j chi_j), added from j = np - 1 down to 0, in one launch; out may be in."""
+        r, n = self._da(rmu)
+        _ck(self.lib.tmhip_rat_sum(self.h, out.h, inp.h, self._handles(chi), r, n, c), "rat_sum")
+
+    def rat_sum_nd(self, out, inp, chi, rmu, c=1.0):
+        """rat_sum for both flavours in one launch: out, inp = (up, dn) pairs, chi = [(up_j, dn_j) ...]."""
+        r, n = self._da(rmu)
+        _ck(self.lib.tmhip_rat_sum_nd(self.h, out[0].h, out[1].h, inp[0].h, inp[1].h, self._handles([p[0] for p in chi]),
+                                      self._handles([p[1] for p in chi]), r, n, c), "rat_sum_nd")
+
+    def diff_sqnorm(self, k, l):
+        """k = k - l; returns |k|^2 (one launch, one synchronisation)."""
+        out = C.c_double()
+        _ck(self.lib.tmhip_diff_sqnorm(self.h, k.h, l.h, C.byref(out)), "diff_sqnorm")
+        return out.value
+
+    def diff_sqnorm_nd(self, k, l):
+        """diff_sqnorm for both flavours, k, l = (up, dn) pairs; returns |k_up|^2 + |k_dn|^2."""
+        out = C.c_double()
+        _ck(self.lib.tmhip_diff_sqnorm_nd(self.h, k[0].h, k[1].h, l[0].h, l[1].h, C.byref(out)), "diff_sqnorm_nd")
+        return out.value
+
+    def apply_Z(self, k, l, mu, rmu, A, max_iter, eps_sq, rel_prec, op="Qtm_pm_psi"):
+        """ratcor_monomial.c:183-218: k = (Q^2 (A R)^2 - 1) l; returns (delta, the first solve's return value)."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it, dl = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_apply_Z(self.h, k.h, l.h, m, r, A, n, max_iter, eps_sq, rel_prec, MMS_OPS[op], C.byref(dl), C.byref(it)), "apply_Z")
+        return dl.value, it.value
+
+    def apply_Z_nd(self, k, l, mu, rmu, A, max_iter, eps_sq, rel_prec, op="Qtm_pm_ndpsi"):
+        """ndratcor_monomial.c:202-245 on (up, dn) pairs k, l; returns (delta, the first solve's return value)."""
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it, dl = C.c_int(), C.c_double()
+        _ck(self.lib.tmhip_apply_Z_nd(self.h, k[0].h, k[1].h, l[0].h, l[1].h, m, r, A, n, max_iter, eps_sq, rel_prec, ND_OPS[op], C.byref(dl), C.byref(it)),
+            "apply_Z_nd")
+        return dl.value, it.value
+
+    def _ratcor(self, fn, what, pfs, mu, rmu, A, max_iter, accprec, rel_prec, op):
+        (m, n), (r, _) = self._da(mu), self._da(rmu)
+        it, na, e = C.c_int(), C.c_int(), C.c_double()
+        _ck(fn(self.h, *[f.h for f in pfs], m, r, A, n, max_iter, accprec, rel_prec, op, C.byref(e), C.byref(na), C.byref(it)), what)
+        return e.value, na.value, it.value
+
+    def ratcor_heatbath(self, pf, mu, rmu, A, max_iter, accprec, rel_prec, op="Qtm_pm_psi"):
+        """ratcor_monomial.c:85-110 (op Qsw_pm_psi: CLOVERRATCOR): pf holds eta on entry, B eta on exit; returns (energy0, applications
+        of Z, summed first-solve iterations)."""
+        return self._ratcor(self.lib.tmhip_ratcor_heatbath, "ratcor_heatbath", [pf], mu, rmu, A, max_iter, accprec, rel_prec, MMS_OPS[op])
+
+    def ratcor_acc(self, pf, mu, rmu, A, max_iter, accprec, rel_prec, op="Qtm_pm_psi"):
+        """ratcor_monomial.c:151-168; returns (energy1, applications of Z, summed first-solve iterations)."""
+        return self._ratcor(self.lib.tmhip_ratcor_acc, "ratcor_acc", [pf], mu, rmu, A, max_iter, accprec, rel_prec, MMS_OPS[op])
+
+    def ndratcor_heatbath(self, pf_up, pf_dn, mu, rmu, A, max_iter, accprec, rel_prec, op="Qtm_pm_ndpsi"):
+        """ndratcor_monomial.c:88-123 (op Qsw_pm_ndpsi: NDCLOVERRATCOR); returns (energy0, applications of Z, iterations)."""
+        return self._ratcor(self.lib.tmhip_ndratcor_heatbath, "ndratcor_heatbath", [pf_up, pf_dn], mu, rmu, A, max_iter, accprec, rel_prec, ND_OPS[op])
+
+    def ndratcor_acc(self, pf_up, pf_dn, mu, rmu, A, max_iter, accprec, rel_prec, op="Qtm_pm_ndpsi"):
+        """ndratcor_monomial.c:166-187; returns (energy1, applications of Z, iterations)."""
+        return self._ratcor(self.lib.tmhip_ndratcor_acc, "ndratcor_acc", [pf_up, pf_dn], mu, rmu, A, max_iter, accprec, rel_prec, ND_OPS[op])
 
     # --- multi-GPU --------------------------------------------------------
     def comm_unique_id(self):

@@ -70,6 +70,10 @@ RULES = [
     (r"^void csg_dot_kernel<\d+>", "batched scalar_prod", 8),
     (r"^void csg_axpy_kernel<\d+>", "batched assign_diff_mul", 8),
     (r"^void csg_lincomb_kernel<\d+, (true|false)>", "lincomb", 8),
+    # the two streams of the correction monomials (linalg.hip): one accumulator per thread whatever np is, and the subtraction with
+    # the block sums of sqnorm_kernel: no scratch, eight waves per SIMD
+    (r"^(void )?rat_sum_kernel", "rat_sum", 8),
+    (r"^(void )?diff_sqnorm_kernel", "diff_sqnorm", 8),
     # the four-term combination of the polynomial monomial (poly.hip), both flavours of a doublet per launch: a stream like the ones above
     (r"^(void )?polyhip::comb4_kernel", "four-term combination", 8),
 ]
