@@ -124,10 +124,23 @@ void mul_r(spinor *const R, const double c, spinor *const S, const int N);      
 _Complex double scalar_prod(const spinor *const S, const spinor *const R, const int N, const int parallel);   /* linalg/scalar_prod.h: sum conj(S) R */
 void assign_diff_mul(spinor *const S, spinor *const R, const _Complex double c, const int N);                /* linalg/assign_diff_mul.h: S -= c R */
 void mul(spinor *const R, const _Complex double c, spinor *const S, const int N);                            /* linalg/mul.h: R = c S, R may be S */
+void assign_add_mul_add_mul(spinor *const R, spinor *const S, spinor *const U, const _Complex double c1, const _Complex double c2,
+                            const int N);                                                                    /* linalg/assign_add_mul_add_mul.h: R += c1 S + c2 U */
+void assign_mul_bra_add_mul_ket_add(spinor *const R, spinor *const S, spinor *const U, const _Complex double c1, const _Complex double c2,
+                                    const int N);                                                            /* linalg/assign_mul_bra_add_mul_ket_add.h: R = c2 (R + c1 S) + U */
 
 /* ---- solver/cg_her.h ------------------------------------------------------- */
 int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec,
            const int N, matrix_mult f);
+
+/* ---- solver/bicgstab_complex.h -----------------------------------------------
+ * P is the starting guess and receives the solution; returns the iteration count, or -1 after max_iter iterations or on a breakdown.
+ * f = Qtm_plus_psi, Qtm_minus_psi, Mtm_plus_psi, Mtm_minus_psi, Mtm_plus_sym_psi, Mtm_minus_sym_psi, Qsw_plus_psi, Qsw_minus_psi or
+ * Msw_plus_psi with N = VOLUME/2, or D_psi (g_c_sw <= 0) with N = VOLUME, on an unsplit lattice: the whole solve runs on the device
+ * (tmhip_bicgstab_complex).  Any other f, N or a T-split run: the reference's loop over the drop-in linalg, one call at a time in
+ * coherent mode, f called through host pointers. */
+int bicgstab_complex(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec,
+                     const int N, matrix_mult f);
 
 /* ---- solver/chrono_guess.h: the chronological guess of the det / cloverdet / detratio / cloverdetratio monomials -----------
  * chrono_guess: trial = the Galerkin solution of f x = phi in the span of the _n stored vectors v[index_array[0 .. _n-1]]; the stored

@@ -152,13 +152,51 @@ int tmhip_lincomb(tmhip_ctx *ctx, tmhip_field *P, int n, tmhip_field *const *V, 
 /* ---- solver --------------------------------------------------------------- */
 enum { TMHIP_OP_QTM_PM = 0, TMHIP_OP_QTM_PLUS = 1, TMHIP_OP_QTM_MINUS = 2, TMHIP_OP_MTM_PLUS = 3, TMHIP_OP_MTM_MINUS = 4,
        TMHIP_OP_QSW_PM = 5 /* clover: Qsw_pm_psi, needs tmhip_set_clover */,
-       TMHIP_OP_Q_PM_FULL = 6 /* Q_pm_psi on FULL fields (tm_operators.c:380-388): tmhip_cg_mms_tm only, tmhip_cg_her refuses it */ };
+       TMHIP_OP_Q_PM_FULL = 6 /* Q_pm_psi on FULL fields (tm_operators.c:380-388): tmhip_cg_mms_tm only, tmhip_cg_her refuses it */,
+       /* the non-hermitian operators of tmhip_bicgstab_complex (which also takes ids 1-4); every other solver refuses them */
+       TMHIP_OP_MTM_PLUS_SYM = 7, TMHIP_OP_MTM_MINUS_SYM = 8 /* Mtm_plus/minus_sym_psi */,
+       TMHIP_OP_QSW_PLUS = 9, TMHIP_OP_QSW_MINUS = 10, TMHIP_OP_MSW_PLUS = 11 /* clover: Qsw_plus/minus_psi, Msw_plus_psi */,
+       TMHIP_OP_D_PSI = 12 /* D_psi on FULL fields, N = VOLUME */ };
 /* cg_her(P,Q,max_iter,eps_sq,rel_prec,N,f)   solver/cg_her.c:62-141.
  * Device-resident: P, Q and the three work fields never leave HBM.  Returns the
  * iteration count in *iters (-1 if not converged); res_hist (may be NULL) gets
  * err after each iteration, up to hist_len entries. */
 int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec,
                  int N, int op, int *iters, double *res_hist, int hist_len);
+
+/* ---- BiCGstab (solver/bicgstab_complex.c:49-116) ------------------------------
+ * The two three-field complex singles of its loop, on fp64 fields of one kind: EO fields with 0 <= N <= VOLUME/2 or FULL fields with
+ * N = VOLUME.  Element-wise, so R may be S or U.  The four products of a complex product are rounded one by one: every element carries
+ * the bits of the reference's statement.
+ *   assign_add_mul_add_mul          R += c1 S + c2 U          (linalg/assign_add_mul_add_mul.c:42-60)
+ *   assign_mul_bra_add_mul_ket_add  R = c2 (R + c1 S) + U     (linalg/assign_mul_bra_add_mul_ket_add.c:44-63) */
+int tmhip_assign_add_mul_add_mul(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, tmhip_field *U, double c1_re, double c1_im, double c2_re,
+                                 double c2_im, int N);
+int tmhip_assign_mul_bra_add_mul_ket_add(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, tmhip_field *U, double c1_re, double c1_im, double c2_re,
+                                         double c2_im, int N);
+/* bicgstab_complex(P,Q,max_iter,eps_sq,rel_prec,N,f): P is the starting guess and receives the solution, *iters the reference's return
+ * value (i, or -1 after max_iter iterations or on the breakdown of :102).  op: TMHIP_OP_QTM_PLUS .. TMHIP_OP_MTM_MINUS and
+ * TMHIP_OP_MTM_PLUS_SYM .. TMHIP_OP_MSW_PLUS on EO fields with N = VOLUME/2, TMHIP_OP_D_PSI on FULL fields with N = VOLUME.  res_hist (may
+ * be NULL) gets |r|^2 at the top of every iteration the reference runs, entry 0 being the starting residual: up to iters + 1 entries.
+ * Six work fields of the context per field kind are allocated on first use and freed with the context.
+ * Option "bicg_fused" (tmhip_set_option) 1 (default): the five fused kernels K1-K5 of bicgstab.hip with the scalars in a device state block
+ * and no host synchronisation but the poll; 0: the reference's statement sequence on the singles, one host round trip per scalar.
+ * Refused with a message, P and *iters untouched: a T-split context or its loopback rehearsal, fp32 fields, a field kind or an N that does
+ * not match the operator, a clover operator without a valid clover term. */
+int tmhip_bicgstab_complex(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec, int N, int op,
+                           int *iters, double *res_hist, int hist_len);
+/* The fused kernels alone, with the scalars handed over by the host (the solver's kernels read them from its device state): given the same
+ * scalars each leaves the bits of the singles it replaces, each sum the bits of tmhip_scalar_prod / tmhip_square_norm of the same fields
+ * (FULL fields: of the two halves, added even first).  Fields of one kind, N as for the solver, no two fields of a call may be one.
+ *   bicg_update    K4: P += alpha p + omega s ; r = s - omega t ; out = {Re <hatr, r>, Im <hatr, r>, <r, r>}
+ *   bicg_pair_dot  K3: out = {Re <t, s>, Im <t, s>, <t, t>} in one pass over t
+ *   bicg_sub       K2: s = r - alpha v
+ *   bicg_dir       K5: p = beta (p - omega v) + r */
+int tmhip_bicg_update(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *r, tmhip_field *p, tmhip_field *s, tmhip_field *t, tmhip_field *hatr,
+                      const double alpha[2], const double omega[2], int N, double out[3]);
+int tmhip_bicg_pair_dot(tmhip_ctx *ctx, tmhip_field *t, tmhip_field *s, int N, double out[3]);
+int tmhip_bicg_sub(tmhip_ctx *ctx, tmhip_field *s, tmhip_field *r, tmhip_field *v, const double alpha[2], int N);
+int tmhip_bicg_dir(tmhip_ctx *ctx, tmhip_field *p, tmhip_field *v, tmhip_field *r, const double omega[2], const double beta[2], int N);
 
 /* ---- chronological solver guess (solver/chrono_guess.c) ---------------------
  * tmhip_chrono_guess: the starting vector of A x = phi from the last n normalised solutions v[0..n-1] (oldest first, i.e. already in

@@ -1,0 +1,34 @@
+"""GPU: bicgstab_complex and its two linalg symbols through the drop-in, in a process of their own (tests/bicg_dropin_child.py): host
+arrays, coherent and lazy residency, the device-resident path for the operators the library knows and the host loop for a foreign f."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("mode", ["coherent", "lazy"])
+def test_dropin_symbols(mode):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bicg_dropin_child.py"), mode], cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    print(out)
+    for k, v in out["linalg"].items():
+        assert v is True or v <= 8, (k, v)                     # eps times the sum of the magnitudes of an element's terms, as tests/test_gpu_bicg.py
+    assert out["linalg"]["N0_unchanged"] is True
+    for name in ("mtm_plus_sym", "mtm_plus_sym_guess", "d_psi"):
+        s = out["solves"][name]
+        assert s["iters"] == s["ref_iters"] and s["q_unchanged"], (name, s)
+        assert s["calls"] == 1, (name, s)                      # the resident path: one entry point served, no linalg call came back to the library
+        assert s["true"] <= s["bound"] * out["margin"], (name, s)
+        assert s["dist"] <= 2.0 * np.sqrt(s["bound"]) / s["sigma_min"], (name, s)
+    g = out["solves"]["foreign"]
+    assert 0 < g["iters"] <= 10 * g["restated_iters"] and g["q_unchanged"], g   # (no count is pinned for an operator the fixtures do not cover)
+    assert g["calls"] > 10 * g["iters"], g                      # the host loop: every statement of every iteration is a call of its own
+    assert g["true"] <= g["bound"] * out["margin"], g

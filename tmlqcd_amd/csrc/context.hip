@@ -160,6 +160,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
   ctx->opt_poly_batch = 12;
   ctx->opt_ratcor_fused = 1;
   ctx->opt_csg_batch = 1;
+  ctx->opt_bicg_fused = 1;
   ctx->gauge_recon_dev = -1.0;
   ctx->opt_gauge_pack = -1; ctx->opt_gauge_pack_rot = -1;
   TMHIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
@@ -227,6 +228,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   tmhip_mms_destroy(ctx);
   tmhip_flow_destroy(ctx);
   tmhip_meas_destroy(ctx);
+  tmhip_bicg_destroy(ctx);
   for (int i = 0; i < 3; i++) { tmhip_field_free(ctx, ctx->scratch[i]); tmhip_field_free(ctx, ctx->sf[i]); }
   tmhip_field_free(ctx, ctx->sf_extra);
   for (int i = 0; i < 2; i++) tmhip_field_free(ctx, ctx->scratch32[i]);
@@ -345,6 +347,7 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "ratcor_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("ratcor_fused must be 0 (the reference's call sequence on the single kernels) or 1 (rat_sum and diff_sqnorm)"); ctx->opt_ratcor_fused = value; }
   else if (!strcmp(name, "poly_fail_alloc")) ctx->opt_poly_fail_alloc = value < 0 ? 0 : value;
   else if (!strcmp(name, "csg_batch")) { if (value < 0 || value > 1) TMHIP_FAIL("csg_batch must be 0 (complex singles) or 1 (batched kernels)"); ctx->opt_csg_batch = value; }
+  else if (!strcmp(name, "bicg_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("bicg_fused must be 0 (the reference's statement sequence on the singles) or 1 (fused kernels, scalars on the device)"); ctx->opt_bicg_fused = value; }
   else if (!strcmp(name, "gauge_global_sums")) { if (value < 0 || value > 1) TMHIP_FAIL("gauge_global_sums must be 0 (the rank's share) or 1 (summed over the ranks)"); ctx->opt_gauge_global_sums = value; }
   else if (!strcmp(name, "cg_batch")) ctx->opt_cg_batch = value > 0 ? value : 1;
   else TMHIP_FAIL("unknown option %s", name);

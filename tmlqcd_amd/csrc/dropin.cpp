@@ -283,6 +283,22 @@ int op_of(matrix_mult f) {
   return -1;
 }
 int cg_her_generic(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f);
+// the operators tmhip_bicgstab_complex knows by address, with the N they act on; -1 for any other pair (op_of above keeps cg_her's set)
+int bicg_op_of(matrix_mult f, const int N) {
+  if (N == VOLUME) return f == &D_psi && !(&g_c_sw && g_c_sw > 0.) ? TMHIP_OP_D_PSI : -1;   // (with g_c_sw > 0 D_psi is Msw_full: d_psi_core)
+  if (N != VOLUME / 2) return -1;
+  if (f == &Qtm_plus_psi) return TMHIP_OP_QTM_PLUS;
+  if (f == &Qtm_minus_psi) return TMHIP_OP_QTM_MINUS;
+  if (f == &Mtm_plus_psi) return TMHIP_OP_MTM_PLUS;
+  if (f == &Mtm_minus_psi) return TMHIP_OP_MTM_MINUS;
+  if (f == &Mtm_plus_sym_psi) return TMHIP_OP_MTM_PLUS_SYM;
+  if (f == &Mtm_minus_sym_psi) return TMHIP_OP_MTM_MINUS_SYM;
+  if (f == &Qsw_plus_psi) return TMHIP_OP_QSW_PLUS;
+  if (f == &Qsw_minus_psi) return TMHIP_OP_QSW_MINUS;
+  if (f == &Msw_plus_psi) return TMHIP_OP_MSW_PLUS;
+  return -1;
+}
+int bicgstab_complex_generic(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f);
 int cg_mms_tm_generic(spinor **const P, spinor *const Q, tmlqcd_solver_params *sp, double *cgmms_reached_prec);
 
 }  // namespace
@@ -746,6 +762,18 @@ void assign_diff_mul(spinor *const S, spinor *const R, const _Complex double cc,
 void mul(spinor *const R, const _Complex double cc, spinor *const S, const int N) {
   lin_op(N, rd(S), wr(R), none(), [&](Ctx c, Fld fs, Fld fr, Fld, int n) { CK(tmhip_mul(c, fr, __real__ cc, __imag__ cc, fs, n)); });
 }
+/* linalg/assign_add_mul_add_mul.c:42-60: R += c1 S + c2 U */
+void assign_add_mul_add_mul(spinor *const R, spinor *const S, spinor *const U, const _Complex double c1, const _Complex double c2, const int N) {
+  lin_op(N, rw(R), rd(S), rd(U), [&](Ctx c, Fld fr, Fld fs, Fld fu, int n) {
+    CK(tmhip_assign_add_mul_add_mul(c, fr, fs, fu, __real__ c1, __imag__ c1, __real__ c2, __imag__ c2, n));
+  });
+}
+/* linalg/assign_mul_bra_add_mul_ket_add.c:44-63: R = c2 (R + c1 S) + U */
+void assign_mul_bra_add_mul_ket_add(spinor *const R, spinor *const S, spinor *const U, const _Complex double c1, const _Complex double c2, const int N) {
+  lin_op(N, rw(R), rd(S), rd(U), [&](Ctx c, Fld fr, Fld fs, Fld fu, int n) {
+    CK(tmhip_assign_mul_bra_add_mul_ket_add(c, fr, fs, fu, __real__ c1, __imag__ c1, __real__ c2, __imag__ c2, n));
+  });
+}
 /* linalg/assign.c:42-46 */
 void assign(spinor *const R, spinor *const S, const int N) {
   lin_op(N, rd(S), wr(R), none(), [&](Ctx c, Fld fs, Fld fr, Fld, int n) { CK(tmhip_assign(c, fr, fs, n)); });
@@ -865,6 +893,20 @@ int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, 
   int iters = -1;
   CK(tmhip_cg_her(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, &iters, nullptr, 0));
   done(c, P);          // coherent mode: the solution is on the host when we return; resident mode: after tmlqcd_hip_sync_to_host
+  return iters;
+}
+
+/* solver/bicgstab_complex.c:49-116.  For the operators of bicg_op_of on an unsplit lattice the whole solve runs device-resident
+ * (tmhip_bicgstab_complex); for any other f the reference's loop runs over the drop-in linalg in coherent mode (bicgstab_complex_generic). */
+int bicgstab_complex(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f) {
+  const int op = bicg_op_of(f, N);
+  if (op < 0 || g_nproc_t > 1) return bicgstab_complex_generic(P, Q, max_iter, eps_sq, rel_prec, N, f);
+  tmhip_ctx *c = op >= TMHIP_OP_QSW_PLUS && op <= TMHIP_OP_MSW_PLUS ? ses.refresh_clover() : ses.refresh(true);
+  const int kind = op == TMHIP_OP_D_PSI ? TMHIP_FIELD_FULL : TMHIP_FIELD_EO;
+  tmhip_field *fq = in(c, Q, kind), *fp = in(c, P, kind);
+  int iters = -1;
+  CK(tmhip_bicgstab_complex(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, &iters, nullptr, 0));
+  done(c, P);
   return iters;
 }
 
@@ -1545,6 +1587,44 @@ int cg_her_generic(spinor *const P, spinor *const Q, const int max_iter, double 
   free(blk);
   if (iteration > max_iter) return -1;
   return iteration;
+}
+
+// generic path of bicgstab_complex: the reference's statements on host-visible fields
+int bicgstab_complex_generic(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f) {
+  CoherentScope coherent;
+  const size_t Vf = (size_t)(N == VOLUME ? VOLUMEPLUSRAND : VOLUMEPLUSRAND / 2);
+  spinor *blk = (spinor *)calloc(6 * Vf + 1, sizeof(spinor));   /* solver_field.c:31-71 */
+  if (!blk) die("bicgstab_complex: out of memory");
+  spinor *hatr = blk, *r = blk + Vf, *v = blk + 2 * Vf, *p = blk + 3 * Vf, *s = blk + 4 * Vf, *t = blk + 5 * Vf;
+  int ret = -1;
+  f(r, P);
+  diff(p, Q, r, N);
+  assign(r, p, N);
+  assign(hatr, p, N);
+  _Complex double rho0 = scalar_prod(hatr, r, N, 1);
+  const double squarenorm = square_norm(Q, N, 1);
+  for (int i = 0; i < max_iter; i++) {
+    const double err = square_norm(r, N, 1);
+    if ((((err <= eps_sq) && (rel_prec == 0)) || ((err <= eps_sq * squarenorm) && (rel_prec == 1))) && i > 0) { ret = i; break; }
+    f(v, p);
+    const _Complex double alpha = rho0 / scalar_prod(hatr, v, N, 1);
+    assign(s, r, N);
+    assign_diff_mul(s, v, alpha, N);
+    f(t, s);
+    _Complex double omega = scalar_prod(t, s, N, 1);
+    omega /= square_norm(t, N, 1);
+    assign_add_mul_add_mul(P, p, s, alpha, omega, N);
+    assign(r, s, N);
+    assign_diff_mul(r, t, omega, N);
+    const _Complex double rho1 = scalar_prod(hatr, r, N, 1);
+    if (fabs(__real__ rho1) < 1.e-25 && fabs(__imag__ rho1) < 1.e-25) break;
+    const _Complex double beta = (alpha * rho1) / (omega * rho0);
+    assign_mul_bra_add_mul_ket_add(p, v, r, -omega, beta, N);
+    rho0 = rho1;
+  }
+  for (int i = 0; i < 6; i++) tmlqcd_hip_forget(blk + i * Vf);  // addresses are about to be recycled
+  free(blk);
+  return ret;
 }
 
 // chrono_guess with an operator the library does not know: f runs on host arrays, so everything around it runs in coherent mode, one

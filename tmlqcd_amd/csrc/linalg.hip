@@ -301,6 +301,41 @@ __global__ __launch_bounds__(LA_BS) void diff_sqnorm_kernel(const DiffSqArgs a, 
 }
 
 
+// ---- the two three-field complex singles of BiCGstab (solver/bicgstab_complex.c:98,111).  grid.y = the planes of the field: twelve of
+// an EO field, twenty-four of a FULL one (its odd half follows its even half at the same stride), n sites per plane.  Element-wise: R may
+// be S or U.  MODE 0: R += c1 S + c2 U   (linalg/assign_add_mul_add_mul.c:42-60)   1: R = c2 (R + c1 S) + U   (linalg/assign_mul_bra_add_mul_ket_add.c:44-63)
+template <int MODE>
+__global__ __launch_bounds__(LA_BS, 8) void cplx3_kernel(v2d *R, const v2d *S, const v2d *U, double c1re, double c1im, double c2re, double c2im,
+                                                         int ns, int n) {
+  const size_t off = (size_t)blockIdx.y * ns;
+  v2d *r = R + off;
+  const v2d *s = S + off, *u = U + off;
+  const int base = blockIdx.x * LA_BS * LA_UNROLL + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < LA_UNROLL; k++) {
+    const int i = base + k * LA_BS;
+    if (i < n) {
+      const v2d a = r[i], b = s[i], c = u[i];
+      r[i] = MODE == 0 ? tmhip_add_mul_add_mul(a, c1re, c1im, b, c2re, c2im, c) : tmhip_mul_bra_add_mul_ket_add(a, c1re, c1im, b, c2re, c2im, c);
+    }
+  }
+}
+
+// fp64 fields of one kind and stride; N = VOLUME for FULL fields, 0 <= N <= VOLUME/2 for EO fields.  *planes, *n: the launch shape
+static int check_cplx3(tmhip_ctx *ctx, const char *who, tmhip_field *R, tmhip_field *S, tmhip_field *U, int N, int *planes, int *n) {
+  if (!R || !S || !U) TMHIP_FAIL("%s: null field", who);
+  if (R->prec || S->prec || U->prec) TMHIP_FAIL("%s: fp64 fields only", who);
+  if (S->kind != R->kind || U->kind != R->kind || S->ns != R->ns || U->ns != R->ns) TMHIP_FAIL("%s: the three fields must be of one kind", who);
+  if (R->kind == TMHIP_FIELD_FULL) {
+    if (N != ctx->V) TMHIP_FAIL("%s: N = %d, FULL fields take N = VOLUME = %d", who, N, ctx->V);
+    *planes = 24; *n = ctx->Vh;
+  } else {
+    if (N < 0 || N > ctx->Vh) TMHIP_FAIL("%s: N = %d is outside [0, VOLUME/2 = %d]", who, N, ctx->Vh);
+    *planes = 12; *n = N;
+  }
+  return 0;
+}
+
 static int check_eo(const tmhip_field *f, const char *who) {
   if (!f || f->kind != TMHIP_FIELD_EO || f->prec != 0) { fprintf(stderr, "[tmlqcd_hip] %s: needs a one-parity (EO) field\n", who); return 1; }
   return 0;
@@ -556,6 +591,28 @@ int tmhip_multi_assign_diff_mul(tmhip_ctx *ctx, int n, tmhip_field *const *R, tm
 int tmhip_assign_diff_mul(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, double c_re, double c_im, int N) {
   const double c[2] = {c_re, c_im};
   return tmhip_multi_assign_diff_mul(ctx, 1, &R, S, c, N);
+}
+
+int tmhip_assign_add_mul_add_mul(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, tmhip_field *U, double c1_re, double c1_im, double c2_re,
+                                 double c2_im, int N) {
+  int planes, n;
+  if (check_cplx3(ctx, "assign_add_mul_add_mul", R, S, U, N, &planes, &n)) return 1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(cplx3_kernel<0>, dim3(la_grid(n).x, planes), dim3(LA_BS), 0, ctx->stream, R->d, (const v2d *)S->d, (const v2d *)U->d, c1_re, c1_im,
+                     c2_re, c2_im, R->ns, n);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tmhip_assign_mul_bra_add_mul_ket_add(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, tmhip_field *U, double c1_re, double c1_im, double c2_re,
+                                         double c2_im, int N) {
+  int planes, n;
+  if (check_cplx3(ctx, "assign_mul_bra_add_mul_ket_add", R, S, U, N, &planes, &n)) return 1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(cplx3_kernel<1>, dim3(la_grid(n).x, planes), dim3(LA_BS), 0, ctx->stream, R->d, (const v2d *)S->d, (const v2d *)U->d, c1_re, c1_im,
+                     c2_re, c2_im, R->ns, n);
+  TMHIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 int tmhip_lincomb(tmhip_ctx *ctx, tmhip_field *P, int n, tmhip_field *const *V, const double *c, int N) {

@@ -230,6 +230,8 @@ struct tmhip_ctx {
   // complex scalar products (linalg.hip): [2 TMHIP_CSG_MAX][12 blocks] block sums, the 2 TMHIP_CSG_MAX results on the device and, pinned, on the host; allocated on first use
   double *csg_partials, *csg_res_dev, *csg_res_host;
   int opt_csg_batch;        // 1 (default): tmhip_chrono_guess on the batched kernels; 0: a sequence of the complex singles
+  void *bicg;               // BiCGstab (bicgstab.hip): six work fields per field kind, the device state and the block sums, allocated on first use
+  int opt_bicg_fused;       // 1 (default): tmhip_bicgstab_complex on the fused kernels with its scalars on the device; 0: the reference's statement sequence on the singles
 };
 
 // N is a site count of a one-parity field: 0 is a legal empty loop in the reference (linalg/*.c), anything outside [0, V/2] would
@@ -387,6 +389,38 @@ static int tmhip_poll_loop(tmhip_ctx *ctx, int cap, bool clamp, int batch, doubl
   if (enq_out) *enq_out = enq;
   return 0;
 }
+// ---- element operations of the complex linalg shared by linalg.hip and bicgstab.hip: one piece of code per operation, so that a fused
+// kernel carries the bits of the single it replaces.  (Both files are built with -ffp-contract=fast, which fuses across statements: a
+// product that has passed through an empty asm statement is a value the compiler cannot fuse into the addition behind it.)
+// c b with its four products rounded one by one: the complex product of the reference's C statement
+__device__ __forceinline__ v2d tmhip_cmul(double cre, double cim, v2d b) {
+  double rr = cre * b.x, ii = cim * b.y, ri = cre * b.y, ir = cim * b.x;
+  asm("" : "+v"(rr), "+v"(ii), "+v"(ri), "+v"(ir));
+  return v2d{rr - ii, ri + ir};
+}
+// r + (c1 s + c2 u)   (linalg/assign_add_mul_add_mul.c:60)
+__device__ __forceinline__ v2d tmhip_add_mul_add_mul(v2d r, double c1re, double c1im, v2d s, double c2re, double c2im, v2d u) {
+  const v2d t = tmhip_cmul(c1re, c1im, s) + tmhip_cmul(c2re, c2im, u);
+  return r + t;
+}
+// u + c2 (r + c1 s)   (linalg/assign_mul_bra_add_mul_ket_add.c:63)
+__device__ __forceinline__ v2d tmhip_mul_bra_add_mul_ket_add(v2d r, double c1re, double c1im, v2d s, double c2re, double c2im, v2d u) {
+  const v2d w = r + tmhip_cmul(c1re, c1im, s);
+  return u + tmhip_cmul(c2re, c2im, w);
+}
+// a - c b with the contraction the compiler chose for csg_axpy_kernel (linalg.hip), written out: the bits of tmhip_assign_diff_mul
+__device__ __forceinline__ v2d tmhip_sub_cmul(v2d a, double cre, double cim, v2d b) {
+  return v2d{__builtin_fma(cim, b.y, __builtin_fma(-cre, b.x, a.x)), __builtin_fma(-cim, b.x, __builtin_fma(-cre, b.y, a.y))};
+}
+// |a|^2 as sqnorm_kernel (linalg.hip) adds it up
+__device__ __forceinline__ double tmhip_norm2(v2d a) { return __builtin_fma(a.x, a.x, a.y * a.y); }
+// += conj(a) b   (scalar_prod_body.c:52): the four products of a term rounded one by one, <S, S> has an imaginary part of exactly zero
+__device__ __forceinline__ void tmhip_cdot_add(double &re, double &im, const v2d a, const v2d b) {
+  double rr = a.x * b.x, ii = a.y * b.y, ri = a.x * b.y, ir = a.y * b.x;
+  asm("" : "+v"(rr), "+v"(ii), "+v"(ri), "+v"(ir));
+  re += rr + ii;
+  im += ri - ir;
+}
 int tmhip_stage_reserve(tmhip_ctx *ctx, size_t bytes);
 int tmhip_field_alloc_prec(tmhip_ctx *ctx, int kind, int prec, tmhip_field **out);
 int tmhip_halo_exchange(tmhip_ctx *ctx);
@@ -401,6 +435,7 @@ void tmhip_poly_destroy(tmhip_ctx *ctx); // poly.hip: work fields of the polynom
 void tmhip_mms_destroy(tmhip_ctx *ctx);  // mms.hip: work fields and state of the single-flavour multi-shift CG
 void tmhip_flow_destroy(tmhip_ctx *ctx); // flow.hip: the buffers of a gradient flow in progress
 void tmhip_meas_destroy(tmhip_ctx *ctx); // meas.hip: the reduction buffers of the online measurements
+void tmhip_bicg_destroy(tmhip_ctx *ctx); // bicgstab.hip: work fields and state of BiCGstab
 // launch geometry shared by linalg.hip and cg.hip
 #define LA_BS 256
 #define LA_UNROLL 4

@@ -12,6 +12,9 @@ EO, OE = 0, 1
 FIELD_EO, FIELD_FULL = 0, 1
 OPS = {"Qtm_pm_psi": 0, "Qtm_plus_psi": 1, "Qtm_minus_psi": 2, "Mtm_plus_psi": 3, "Mtm_minus_psi": 4, "Qsw_pm_psi": 5}
 MMS_OPS = {"Qtm_pm_psi": 0, "Qsw_pm_psi": 5, "Q_pm_psi": 6}   # cg_mms_tm's operators (Q_pm_psi: FULL fields, TMHIP_OP_Q_PM_FULL)
+# bicgstab_complex's operators (D_psi: FULL fields, N = VOLUME; the others EO fields, N = VOLUME/2)
+BICG_OPS = {"Qtm_plus_psi": 1, "Qtm_minus_psi": 2, "Mtm_plus_psi": 3, "Mtm_minus_psi": 4, "Mtm_plus_sym_psi": 7, "Mtm_minus_sym_psi": 8,
+            "Qsw_plus_psi": 9, "Qsw_minus_psi": 10, "Msw_plus_psi": 11, "D_psi": 12}
 ND_OPS = {"Qtm_pm_ndpsi": 0, "Qsw_pm_ndpsi": 1}         # the doublet solvers' operators (TMHIP_ND_OP_*)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -92,6 +95,13 @@ def load_library():
         "tmhip_add": [vp, vp, vp, vp, i],
         "tmhip_mul_r": [vp, vp, d, vp, i],
         "tmhip_cg_her": [vp, vp, vp, i, d, i, i, i, C.POINTER(i), pd, i],
+        "tmhip_assign_add_mul_add_mul": [vp, vp, vp, vp, d, d, d, d, i],
+        "tmhip_assign_mul_bra_add_mul_ket_add": [vp, vp, vp, vp, d, d, d, d, i],
+        "tmhip_bicgstab_complex": [vp, vp, vp, i, d, i, i, i, C.POINTER(i), pd, i],
+        "tmhip_bicg_update": [vp, vp, vp, vp, vp, vp, vp, pd, pd, i, pd],
+        "tmhip_bicg_pair_dot": [vp, vp, vp, i, pd],
+        "tmhip_bicg_sub": [vp, vp, vp, vp, pd, i],
+        "tmhip_bicg_dir": [vp, vp, vp, vp, pd, pd, i],
         "tmhip_set_clover": [vp, vp, vp],
         "tmhip_sw_term": [vp, vp, d, d],
         "tmhip_momenta_upload": [vp, vp], "tmhip_momenta_download": [vp, vp], "tmhip_update_momenta": [vp, d],
@@ -900,6 +910,52 @@ class Lattice:
         _ck(self.lib.tmhip_cg_her(self.h, P.h, Q.h, max_iter, eps_sq, rel_prec, N, OPS[op], C.byref(it),
                                   hist.ctypes.data_as(C.POINTER(C.c_double)), hist.size), "cg_her")
         n = it.value if it.value > 0 else max_iter
+        return it.value, hist[:n]
+
+    # --- BiCGstab (solver/bicgstab_complex.c) -------------------------------
+    @staticmethod
+    def _c2(z):
+        z = complex(z)
+        return (C.c_double * 2)(z.real, z.imag)
+
+    def assign_add_mul_add_mul(self, R, S, U, c1, c2, N):
+        """R += c1 S + c2 U (EO fields, or FULL fields with N = VOLUME)"""
+        c1, c2 = complex(c1), complex(c2)
+        _ck(self.lib.tmhip_assign_add_mul_add_mul(self.h, R.h, S.h, U.h, c1.real, c1.imag, c2.real, c2.imag, N), "assign_add_mul_add_mul")
+
+    def assign_mul_bra_add_mul_ket_add(self, R, S, U, c1, c2, N):
+        """R = c2 (R + c1 S) + U"""
+        c1, c2 = complex(c1), complex(c2)
+        _ck(self.lib.tmhip_assign_mul_bra_add_mul_ket_add(self.h, R.h, S.h, U.h, c1.real, c1.imag, c2.real, c2.imag, N),
+            "assign_mul_bra_add_mul_ket_add")
+
+    def bicg_update(self, P, r, p, s, t, hatr, alpha, omega, N):
+        """K4 of the fused iteration: P += alpha p + omega s; r = s - omega t.  Returns (<hatr, r>, <r, r>)."""
+        out = (C.c_double * 3)()
+        _ck(self.lib.tmhip_bicg_update(self.h, P.h, r.h, p.h, s.h, t.h, hatr.h, self._c2(alpha), self._c2(omega), N, out), "bicg_update")
+        return complex(out[0], out[1]), out[2]
+
+    def bicg_pair_dot(self, t, s, N):
+        """K3: (<t, s>, <t, t>) from one pass over t"""
+        out = (C.c_double * 3)()
+        _ck(self.lib.tmhip_bicg_pair_dot(self.h, t.h, s.h, N, out), "bicg_pair_dot")
+        return complex(out[0], out[1]), out[2]
+
+    def bicg_sub(self, s, r, v, alpha, N):
+        """K2: s = r - alpha v"""
+        _ck(self.lib.tmhip_bicg_sub(self.h, s.h, r.h, v.h, self._c2(alpha), N), "bicg_sub")
+
+    def bicg_dir(self, p, v, r, omega, beta, N):
+        """K5: p = beta (p - omega v) + r"""
+        _ck(self.lib.tmhip_bicg_dir(self.h, p.h, v.h, r.h, self._c2(omega), self._c2(beta), N), "bicg_dir")
+
+    def bicgstab_complex(self, P, Q, max_iter, eps_sq, rel_prec, N, op="Mtm_plus_sym_psi"):
+        """Returns (the reference's return value, |r|^2 at the top of every iteration run, the starting residual first)."""
+        it = C.c_int(-2)
+        hist = np.zeros(max(max_iter, 0) + 1, dtype=np.float64)
+        _ck(self.lib.tmhip_bicgstab_complex(self.h, P.h, Q.h, max_iter, eps_sq, rel_prec, N, BICG_OPS[op], C.byref(it),
+                                            hist.ctypes.data_as(C.POINTER(C.c_double)), hist.size), "bicgstab_complex")
+        n = it.value + 1 if it.value > 0 else hist.size
         return it.value, hist[:n]
 
     # --- non-degenerate doublet (operator/tm_operators_nd.c; strange = up = first field of a pair) ---

@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/poly.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/bicgstab.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/poly.ru.txt
 """
 import re
 import subprocess
@@ -74,6 +74,10 @@ RULES = [
     # the block sums of sqnorm_kernel: no scratch, eight waves per SIMD
     (r"^(void )?rat_sum_kernel", "rat_sum", 8),
     (r"^(void )?diff_sqnorm_kernel", "diff_sqnorm", 8),
+    # BiCGstab (linalg.hip, bicgstab.hip): the two three-field singles and the five fused kernels between the two stencils of an
+    # iteration -- K4 walks six fields with three accumulators --: streams like the ones above, no scratch, eight waves per SIMD
+    (r"^void cplx3_kernel<[01]>", "three-field complex singles", 8),
+    (r"^(void )?bicghip::(dot_kernel<(true|false)>|sub_kernel|update_kernel|dir_kernel)", "fused BiCGstab", 8),
     # the four-term combination of the polynomial monomial (poly.hip), both flavours of a doublet per launch: a stream like the ones above
     (r"^(void )?polyhip::comb4_kernel", "four-term combination", 8),
 ]
