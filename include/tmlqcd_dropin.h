@@ -304,6 +304,39 @@ void tmlqcd_hip_sync_gauge_to_host(hamiltonian_field_t *const hf);
 void tmlqcd_hip_update_momenta(const double step, hamiltonian_field_t *const hf);
 void tmlqcd_hip_sync_momenta_to_host(hamiltonian_field_t *const hf);
 
+/* The frame of a trajectory with links and momenta resident in HBM: replace the host loops of update_tm.c around the integrator and the
+ * norm loop of monitor_forces.c (INTEGRATION.md section 2.3c has the listing).  All under tmlqcd_hip_ names: moment_energy and
+ * monitor_forces stay the reference's own symbols.  Residency rules as tmlqcd_hip_update_gauge / tmlqcd_hip_update_momenta:
+ *   _gauge_snapshot       the loop update_tm.c:109-121.  The device links are brought up to date first (a raised g_update_gauge_copy is
+ *                         honoured: the host's links go up), then copied into the device's gauge_tmp.  The host's gauge_tmp is not needed.
+ *   _moment_energy        moment_energy(hf->momenta): uploads hf->momenta unless the momenta are resident (after tmlqcd_hip_update_momenta);
+ *                         returns the sum over all ranks, the same bits on every rank.
+ *   _gauge_snapshot_diff  update_tm.c:233-277: ret_gauge_diff between the device links and the snapshot, summed over all ranks.
+ *   _accept_links         :313-328 (reunitarize = !bc_flag: restoresu3_in_place on every link; 0: the links stay) and :344-346.
+ *   _reject_links         :329-339 (links <- snapshot) and :344-346.  The snapshot wins, as gauge_tmp does: a g_update_gauge_copy raised by
+ *                         the host since tmlqcd_hip_gauge_snapshot is dropped, not answered with an upload.
+ *                         After both, coherent and lazy mode: hf->gaugefield holds the device's links, the host's backward copy is refreshed,
+ *                         g_update_gauge_copy and hf->update_gauge_copy are down, g_update_gauge_copy_32 is up, and the next operator
+ *                         uploads nothing.  Resident mode: the host's links stay behind until tmlqcd_hip_sync_gauge_to_host.  In every
+ *                         mode the clover blocks are stale (sw_term / sw_invert again, as after update_gauge), and the device's momenta are
+ *                         given up without a download: the trajectory is over, the next tmlqcd_hip_update_momenta / _update_gauge /
+ *                         _moment_energy uploads hf->momenta, which random_su3adj_field has drawn anew by then.
+ *   _force_norms          monitor_forces.c:64-97: sum and maximum over the links of all ranks of _su3adj_square_norm of the DEVICE's derivative
+ *                         accumulator.  Meant for a force accumulated on the device and not yet flushed (resident mode, between the
+ *                         derivative functions and tmlqcd_hip_flush_derivative / tmlqcd_hip_update_momenta).  Otherwise it returns the norms
+ *                         of what the accumulator still holds -- the force last flushed or consumed, never contributions other code added to
+ *                         hf->derivative on the host -- and 0, 0 if no force has run on the device yet.
+ * What stays on the host: random_su3adj_field (ranlxd is sequential and its numbers must be the reference's; enep stays the value it
+ * returns) and the acceptance draw ranlxd(yy, 1). */
+void tmlqcd_hip_gauge_snapshot(hamiltonian_field_t *const hf);
+double tmlqcd_hip_moment_energy(hamiltonian_field_t *const hf);
+double tmlqcd_hip_gauge_snapshot_diff(hamiltonian_field_t *const hf);
+void tmlqcd_hip_accept_links(hamiltonian_field_t *const hf, const int reunitarize);
+void tmlqcd_hip_reject_links(hamiltonian_field_t *const hf);
+void tmlqcd_hip_force_norms(hamiltonian_field_t *const hf, double *sum, double *max);
+/* whole-field copies across the bus so far: gauge uploads, gauge downloads, momenta uploads, momenta downloads (tmhip_transfer_counts) */
+void tmlqcd_hip_transfer_counts(unsigned long out[4]);
+
 /* ---- residency control (additions; not in the reference) ------------------- */
 /* COHERENT (default): every call uploads its inputs and downloads its outputs -- exact drop-in, PCIe-bound.
  * RESIDENT: outputs stay in HBM until tmlqcd_hip_sync_to_host; the host program says when it touches a field.

@@ -573,6 +573,39 @@ int tmhip_update_gauge(tmhip_ctx *ctx, double step);     /* update_gauge.c:51-11
 int tmhip_multi_update_gauge(int n, tmhip_ctx **ctxs, double step);   /* the same for n contexts of one process holding a T-split lattice (peer copies) */
 int tmhip_gauge_download(tmhip_ctx *ctx, void *host_gauge);   /* [VOLUMEPLUSRAND][4] su3, e.g. at the end of a trajectory */
 
+/* ---- the frame of a trajectory around the integrator (update_tm.c, monomial/moment_energy.c, monomial/monitor_forces.c) --------
+ * fp64, on the resident links, momenta and derivative; nothing crosses the bus but the scalars.
+ * The snapshot is the reference's gauge_tmp: a device buffer of its own in the layout of the resident links (own sites and, on a
+ * T-split rank, the two halo slabs), allocated by the first tmhip_gauge_snapshot (576 bytes per site) and freed by
+ * tmhip_gauge_snapshot_free or tmhip_destroy; tmhip_set_gauge leaves it alone.  _snapshot without resident links, _restore and
+ * _snapshot_diff without a snapshot return non-zero with a message.
+ * tmhip_gauge_restore and tmhip_gauge_reunitarize change the links and leave every derived state as tmhip_update_gauge leaves it
+ * (stencil gauge copy, fp32 and packed twins stale, "gauge_recon" 12 guard re-run, clover blocks stale); the flow buffers and the
+ * snapshot are not touched.  _reunitarize is ONE pass: links read, restoresu3 (expo.c:118-137), written back and scattered into the
+ * stencil's copy.  restoresu3 is a function of the single link, so a T-split rank reunitarises its halo slabs itself and no exchange
+ * follows; the snapshot holds the slabs, so _restore needs none either.
+ * The three sums are over the rank's own links (with the option "gauge_global_sums" 1 over all ranks of a T split; the maximum is
+ * then the maximum over the ranks); fixed-order block sums, two calls on the same data return the same bits.  They do not reproduce
+ * the order of the reference's serial Kahan loops: every term is non-negative and the result lies within a few dozen ulp of the exact
+ * sum (tests/test_gpu_trajectory_frame.py derives the bound from the launch geometry).
+ * tmhip_derivative_norms returns non-zero if no force has created the derivative field yet. */
+int tmhip_gauge_snapshot(tmhip_ctx *ctx);                   /* update_tm.c:109-121  gauge_tmp <- links */
+int tmhip_gauge_restore(tmhip_ctx *ctx);                    /* update_tm.c:329-339  links <- gauge_tmp (reject) */
+int tmhip_gauge_snapshot_free(tmhip_ctx *ctx);
+int tmhip_gauge_reunitarize(tmhip_ctx *ctx);                /* update_tm.c:313-328  restoresu3_in_place on every link (accept) */
+int tmhip_gauge_snapshot_diff(tmhip_ctx *ctx, double *out); /* update_tm.c:233-272  sum over own links of sqrt(|U - U_tmp|_F^2) */
+int tmhip_moment_energy(tmhip_ctx *ctx, double *out);       /* moment_energy.c:46-74 0.5 * sum over own links of |P|^2 */
+int tmhip_derivative_norms(tmhip_ctx *ctx, double *sum, double *max);   /* monitor_forces.c:64-89 over own links: sum and maximum of d1^2 + ... + d8^2 */
+/* device time per call (HIP events over reps calls) of one form of the reject / accept pass, for tools/traj_speed.py: form 0 restore as copy +
+ * re-sort, 1 restore in one pass, 2 accept as a restoresu3 pass + re-sort, 3 accept in one pass.  Needs resident links and a snapshot;
+ * leaves the links restored (0, 1) or reunitarised (2, 3). */
+int tmhip_bench_trajectory_forms(tmhip_ctx *ctx, int form, int reps, double *ms);
+/* whole-field copies across the bus this context has made so far: out[0] tmhip_set_gauge, [1] tmhip_gauge_download, [2] tmhip_momenta_upload,
+ * [3] tmhip_momenta_download -- what a test of "nothing crosses the bus between the snapshot and the acceptance step" reads */
+int tmhip_transfer_counts(tmhip_ctx *ctx, long long out[4]);
+/* su3adj df[VOLUME][4] (host) -> the device derivative field, replacing what it holds: the inverse of tmhip_derivative_download(..., 0) */
+int tmhip_derivative_upload(tmhip_ctx *ctx, const void *df);
+
 /* ---- gauge monomial on the device-resident links (monomial/gauge_monomial.c; gauge.hip) --------------------------------
  * tmhip_gauge_derivative ADDS gauge_derivative (glambda = 0) / gauge_EMderivative of the reference to the derivative accumulator of
  * tmhip_deriv_Sb / tmhip_sw_all (created and zeroed if no force has done so yet): for every link factor trlambda(U staple^dagger) with

@@ -245,6 +245,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   if (ctx->sw_trace_fail) (void)hipFree(ctx->sw_trace_fail);
   if (ctx->swpm) (void)hipFree(ctx->swpm);
   if (ctx->gauge_raw) (void)hipFree(ctx->gauge_raw);
+  if (ctx->gauge_snap) (void)hipFree(ctx->gauge_snap);
   if (ctx->deriv) (void)hipFree(ctx->deriv);
   if (ctx->momenta) (void)hipFree(ctx->momenta);
   if (ctx->force_send) (void)hipFree(ctx->force_send);
@@ -270,6 +271,12 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   for (int i = 0; i < 16; i++) (void)hipEventDestroy(ctx->ev_slots[i]);
   (void)hipStreamDestroy(ctx->stream); (void)hipStreamDestroy(ctx->comm_stream);
   delete ctx;
+}
+
+int tmhip_transfer_counts(tmhip_ctx *ctx, long long out[4]) {
+  if (!out) TMHIP_FAIL("tmhip_transfer_counts: null argument");
+  for (int k = 0; k < 4; k++) out[k] = ctx->xfer[k];
+  return 0;
 }
 
 int tmhip_sync(tmhip_ctx *ctx) {
@@ -363,6 +370,7 @@ int tmhip_set_gauge(tmhip_ctx *ctx, const void *host) {
   if (!ctx->gauge_raw) TMHIP_CHECK(hipMalloc((void **)&ctx->gauge_raw, bytes));
   TMHIP_CHECK(hipMemcpyAsync(ctx->gauge_raw, host, bytes, hipMemcpyHostToDevice, ctx->stream));
   ctx->gauge_raw_valid = true;
+  ctx->xfer[0]++;
   if (tmhip_resort_gauge(ctx)) return 1;      // (with "gauge_recon" 12 in force: and the guard's measurement of the new links)
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return 0;

@@ -63,6 +63,7 @@ struct Session {
   bool clover_uploaded = false;
   bool sw_on_device = false;       // the device's 1+T belongs to the current links (tmlqcd_hip_sw_term, or the host's sw uploaded)
   bool deriv_pending = false;      // a force is accumulating in the device's derivative, not yet in hf->derivative
+  bool deriv_made = false;         // some force has run on the device: its derivative accumulator exists
   tmhip_field *full_tmp = nullptr; // FULL-lattice scratch of Q_pm_psi / D_dagg_psi (tm_operators.c:380-397)
   tmhip_field *f32[3] = {nullptr, nullptr, nullptr};   // device fields of the fp32 host-pointer symbols (Hopping_Matrix_32 ...)
 
@@ -226,7 +227,7 @@ void q_pm_full(spinor *l, spinor *k, const double first_mu) {
 
 // A force accumulates on the device: the first contribution since the last flush / tmlqcd_hip_update_momenta starts from zero; after
 // each one hf->derivative receives the sum unless the mode is resident (lazy mode watches spinor arrays only).
-void force_begin(tmhip_ctx *c) { if (!ses.deriv_pending) CK(tmhip_derivative_zero(c)); }
+void force_begin(tmhip_ctx *c) { if (!ses.deriv_pending) CK(tmhip_derivative_zero(c)); ses.deriv_made = true; }
 void force_end(hamiltonian_field_t *const hf) {
   ses.deriv_pending = true;
   if (!resident()) tmlqcd_hip_flush_derivative(hf);
@@ -324,6 +325,7 @@ void tmlqcd_hip_finalize(void) {
   ses.gauge_uploaded = false;
   ses.clover_stale();
   ses.dev_links_newer = ses.momenta_resident = false;
+  ses.deriv_pending = ses.deriv_made = false;
 }
 
 // ------------------------------------------------------------------ stencil
@@ -1486,6 +1488,73 @@ void tmlqcd_hip_sync_momenta_to_host(hamiltonian_field_t *const hf) {
   if (!ses.momenta_resident) return;
   CK(tmhip_momenta_download(ctx(), &hf->momenta[0][0]));
   ses.momenta_resident = false;
+}
+
+// ------------------------------------------------------------------ the frame of a trajectory (update_tm.c around the integrator)
+/* update_tm.c:109-121: gauge_tmp <- links, on the device */
+void tmlqcd_hip_gauge_snapshot(hamiltonian_field_t *const hf) {
+  (void)hf;
+  CK(tmhip_gauge_snapshot(ses.refresh(true)));
+}
+/* moment_energy(hf->momenta) (moment_energy.c:46-89), MPI_Allreduce included */
+double tmlqcd_hip_moment_energy(hamiltonian_field_t *const hf) {
+  tmhip_ctx *c = ses.refresh(false);
+  if (!ses.momenta_resident) CK(tmhip_momenta_upload(c, &hf->momenta[0][0]));
+  CK(tmhip_set_option(c, "gauge_global_sums", 1));
+  double e = 0.0;
+  CK(tmhip_moment_energy(c, &e));
+  return e;
+}
+/* update_tm.c:233-277: ret_gauge_diff */
+double tmlqcd_hip_gauge_snapshot_diff(hamiltonian_field_t *const hf) {
+  (void)hf;
+  tmhip_ctx *c = ses.refresh(true);
+  CK(tmhip_set_option(c, "gauge_global_sums", 1));
+  double d = 0.0;
+  CK(tmhip_gauge_snapshot_diff(c, &d));
+  return d;
+}
+// update_tm.c:344-352 after the links changed on the device: the two sides are brought to the same state (coherent, lazy) or the device is
+// marked ahead (resident); a flag the host raised in between belongs to links that no longer exist
+static void links_after_acceptance(tmhip_ctx *c, hamiltonian_field_t *const hf) {
+  ses.clover_stale();
+  ses.momenta_resident = false;   // the trajectory is over: its momenta are not needed again (no download), the next one's are drawn on the host
+  if (!resident()) {
+    CK(tmhip_gauge_download(c, &hf->gaugefield[0][0]));
+    links_in_step(hf->gaugefield, hf);
+    ses.dev_links_newer = false;
+  } else {
+    g_update_gauge_copy = 0;
+    hf->update_gauge_copy = 0;
+    ses.gauge_uploaded = true;
+    ses.dev_links_newer = true;
+  }
+}
+/* update_tm.c:313-328 and :344-346 */
+void tmlqcd_hip_accept_links(hamiltonian_field_t *const hf, const int reunitarize) {
+  tmhip_ctx *c = ses.refresh(true);
+  if (reunitarize) CK(tmhip_gauge_reunitarize(c));
+  links_after_acceptance(c, hf);
+}
+/* update_tm.c:329-339 and :344-346 */
+void tmlqcd_hip_reject_links(hamiltonian_field_t *const hf) {
+  tmhip_ctx *c = ses.refresh(false);                                // (no upload: the snapshot replaces whatever the host's links are)
+  CK(tmhip_gauge_restore(c));
+  links_after_acceptance(c, hf);
+}
+void tmlqcd_hip_transfer_counts(unsigned long out[4]) {
+  long long n[4] = {0, 0, 0, 0};
+  if (ses.c) CK(tmhip_transfer_counts(ses.c, n));
+  for (int k = 0; k < 4; k++) out[k] = (unsigned long)n[k];
+}
+/* monitor_forces.c:64-97 on the device's derivative accumulator */
+void tmlqcd_hip_force_norms(hamiltonian_field_t *const hf, double *sum, double *max) {
+  (void)hf;
+  tmhip_ctx *c = ses.refresh(false);
+  *sum = *max = 0.0;
+  if (!ses.deriv_made) return;
+  CK(tmhip_set_option(c, "gauge_global_sums", 1));
+  CK(tmhip_derivative_norms(c, sum, max));
 }
 
 // ------------------------------------------------------------------ ILDG gauge configurations

@@ -151,6 +151,23 @@ __global__ __launch_bounds__(256) void deriv_to_lexic_kernel(const double *__res
   for (int e = 0; e < 32; e++) dst[e] = src[(size_t)e * Vh];
 }
 
+// su3adj df[V][4] (lexicographic) -> deriv[par][mu][8][Vh]: the inverse of deriv_to_lexic_kernel
+__global__ __launch_bounds__(256) void deriv_from_lexic_kernel(double *__restrict__ d, const double *__restrict__ in, int Vh, int LX, int LY, int LZ, int toff) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Vh) return;
+  const int par = blockIdx.y;
+  const int LZh = LZ / 2;
+  int r = i / LZh;
+  const int y = r % LY;
+  r /= LY;
+  const int x = r % LX, t = r / LX;
+  const int o = (t + x + y + par + toff) & 1;
+  const double *src = in + (2 * (size_t)i + o) * 32;
+  double *dst = d + (size_t)par * 32 * Vh + i;
+#pragma unroll 8
+  for (int e = 0; e < 32; e++) dst[(size_t)e * Vh] = src[e];
+}
+
 extern "C" {
 
 int tmhip_derivative_zero(tmhip_ctx *ctx) {
@@ -264,6 +281,21 @@ int tmhip_derivative_download(tmhip_ctx *ctx, void *host_df, int accumulate) {
   double *h = (double *)host_df;
   for (size_t i = 0; i < n; i++) h[i] += tmp[i];
   free(tmp);
+  return 0;
+}
+
+/* The host's su3adj df[VOLUME][4] into the device derivative field (created if no force has done so yet), replacing what it holds */
+int tmhip_derivative_upload(tmhip_ctx *ctx, const void *host_df) {
+  if (!host_df) TMHIP_FAIL("tmhip_derivative_upload: null argument");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (!ctx->deriv && tmhip_derivative_zero(ctx)) return 1;
+  const size_t bytes = (size_t)ctx->V * 32 * sizeof(double);
+  if (tmhip_stage_reserve(ctx, bytes)) return 1;
+  TMHIP_CHECK(hipMemcpyAsync(ctx->stage, host_df, bytes, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(deriv_from_lexic_kernel, dim3((ctx->Vh + 255) / 256, 2), dim3(256), 0, ctx->stream, ctx->deriv, (const double *)ctx->stage,
+                     ctx->Vh, ctx->g.LX, ctx->g.LY, ctx->g.LZ, ctx->g.proc_t * ctx->g.T);
+  TMHIP_CHECK(hipGetLastError());
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 

@@ -66,10 +66,15 @@ __device__ __forceinline__ void restoresu3(cd (&vr)[9], const cd (&u)[9]) {
   vr[8] = cconj(cmul(vr[0], vr[4]) - cmul(vr[1], vr[3]));
 }
 
-// One kernel for "links -> stencil copy" with or without the molecular-dynamics update in front:
-//   UPDATE   U_mu(x) <- restoresu3(exposu3(step P_mu(x))) U_mu(x)  (update_gauge.c:51-110), written back to the lexicographic field
-//   always   the link goes straight to its TWO slots of the stencil's gauge copy g[par][dir][e][site]: dir 2 mu of its own site and
-//            dir 2 mu + 1 of the site at x + mu (update_backward_gauge.c:185-242 turned from a gather into a scatter)
+// One kernel for "links -> stencil copy" with or without a transform of the links in front:
+//   LINKS_UPDATE  U_mu(x) <- restoresu3(exposu3(step P_mu(x))) U_mu(x)  (update_gauge.c:51-110), written back to the lexicographic field
+//   LINKS_REUNIT  U_mu(x) <- restoresu3(U_mu(x))  (restoresu3_in_place on every link after an accept, update_tm.c:313-328), written back;
+//                 no momenta staged.  The halo slabs of a T-split rank are transformed with the own links (VT = VPR): restoresu3 is a
+//                 function of the single link, so the slabs stay the neighbours' slices bit for bit without an exchange
+//   LINKS_COPY    U_mu(x) <- the link of a second field in the same layout (aux: the snapshot, after a reject: update_tm.c:329-339),
+//                 written to the lexicographic field, halo slabs included -- restore and re-sort in one pass over the snapshot
+//   always        the link goes straight to its TWO slots of the stencil's gauge copy g[par][dir][e][site]: dir 2 mu of its own site and
+//                 dir 2 mu + 1 of the site at x + mu (update_backward_gauge.c:185-242 turned from a gather into a scatter)
 // so an MD step reads every link once and never re-reads the updated field for a separate re-sort (832 + 1152 -> 640 B per link
 // site-direction).  A block owns 64 consecutive lexicographic sites = 256 links: the host-layout arrays (144-byte links, 64-byte
 // momenta) are moved between HBM and LDS as whole contiguous rows, 16 bytes per lane (a lane-per-link access has a 144-byte lane
@@ -77,21 +82,25 @@ __device__ __forceinline__ void restoresu3(cd (&vr)[9], const cd (&u)[9]) {
 // conflict-free 16-byte reads; the momenta rows are padded to 80 bytes for the same reason).
 // T-split ranks: the link U_t at t = T-1 is the backward link of a site of the up neighbour (not stored here), and the backward
 // t-links of the t = 0 sites come from the t = -1 halo slab once the neighbours' slices have arrived (halo_backward_kernel).
-template <bool UPDATE>
-__global__ __launch_bounds__(256) void links_kernel(v2d *__restrict__ raw, const double *__restrict__ mom, v2d *__restrict__ g, int gs, int V, int Vh,
+// VT: the sites whose links are loaded (and transformed): V, or VPR in the LINKS_REUNIT form; only the V own sites are scattered.
+// aux: the momenta (LINKS_UPDATE) or the field to copy from (LINKS_COPY).
+enum { LINKS_RESORT = 0, LINKS_UPDATE = 1, LINKS_REUNIT = 2, LINKS_COPY = 3 };
+template <int MODE>
+__global__ __launch_bounds__(256) void links_kernel(v2d *__restrict__ raw, const double *__restrict__ aux, v2d *__restrict__ g, int gs, int V, int VT,
                                                     int T, int LX, int LY, int LZ, int toff, int split, double step) {
+  constexpr bool UPDATE = MODE == LINKS_UPDATE;
   __shared__ v2d sl[256 * 9];
   __shared__ v2d sm[UPDATE ? 256 * 5 : 1];
   const int tid = threadIdx.x;
   const size_t l0 = (size_t)blockIdx.x * 256;            // first link of the block
-  const int nl = (int)(((size_t)V * 4 - l0) < 256 ? ((size_t)V * 4 - l0) : 256);
+  const int nl = (int)(((size_t)VT * 4 - l0) < 256 ? ((size_t)VT * 4 - l0) : 256);
 #pragma unroll
   for (int j = 0; j < 9; j++) {
     const int idx = j * 256 + tid;
-    if (idx < nl * 9) sl[idx] = raw[l0 * 9 + idx];
+    if (idx < nl * 9) sl[idx] = MODE == LINKS_COPY ? reinterpret_cast<const v2d *>(aux)[l0 * 9 + idx] : raw[l0 * 9 + idx];
   }
   if (UPDATE) {
-    const v2d *m2 = reinterpret_cast<const v2d *>(mom) + l0 * 4;
+    const v2d *m2 = reinterpret_cast<const v2d *>(aux) + l0 * 4;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int idx = j * 256 + tid;
@@ -99,22 +108,26 @@ __global__ __launch_bounds__(256) void links_kernel(v2d *__restrict__ raw, const
     }
   }
   __syncthreads();
-  if (UPDATE) {
+  if (MODE == LINKS_UPDATE || MODE == LINKS_REUNIT) {
     if (tid < nl) {
       cd z[9], out[9];
 #pragma unroll
       for (int e = 0; e < 9; e++) z[e] = sl[tid * 9 + e];
-      double d[8];
+      if (UPDATE) {
+        double d[8];
 #pragma unroll
-      for (int k = 0; k < 4; k++) { const v2d m = sm[tid * 5 + k]; d[2 * k] = step * m.x; d[2 * k + 1] = step * m.y; }   // _su3adj_assign_const_times_su3adj, update_gauge.c:85
-      cd w[9], v[9];
-      exposu3(w, d);
-      restoresu3(v, w);
-      m3mul(out, v, z);
+        for (int k = 0; k < 4; k++) { const v2d m = sm[tid * 5 + k]; d[2 * k] = step * m.x; d[2 * k + 1] = step * m.y; }   // _su3adj_assign_const_times_su3adj, update_gauge.c:85
+        cd w[9], v[9];
+        exposu3(w, d);
+        restoresu3(v, w);
+        m3mul(out, v, z);
+      } else restoresu3(out, z);
 #pragma unroll
       for (int e = 0; e < 9; e++) sl[tid * 9 + e] = out[e];
     }
     __syncthreads();
+  }
+  if (MODE != LINKS_RESORT) {
 #pragma unroll
     for (int j = 0; j < 9; j++) {
       const int idx = j * 256 + tid;
@@ -151,7 +164,35 @@ __global__ __launch_bounds__(256) void links_kernel(v2d *__restrict__ raw, const
   v2d *gb = g + ((size_t)(1 - p) * 72 + (size_t)(2 * mu + 1) * 9) * gs + (jx >> 1);
 #pragma unroll
   for (int e = 0; e < 9; e++) __builtin_nontemporal_store(out[e], gb + (size_t)e * gs);
-  (void)Vh;
+}
+
+// restoresu3 on every link and nothing else: the first launch of the two-launch accept tmhip_bench_trajectory_forms measures against the
+// LINKS_REUNIT form of links_kernel (same row loads through LDS, no scatter)
+__global__ __launch_bounds__(256) void reunit_only_kernel(v2d *__restrict__ raw, size_t nlinks) {
+  __shared__ v2d sl[256 * 9];
+  const int tid = threadIdx.x;
+  const size_t l0 = (size_t)blockIdx.x * 256;
+  const int nl = (int)((nlinks - l0) < 256 ? (nlinks - l0) : 256);
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    const int idx = j * 256 + tid;
+    if (idx < nl * 9) sl[idx] = raw[l0 * 9 + idx];
+  }
+  __syncthreads();
+  if (tid < nl) {
+    cd z[9], out[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) z[e] = sl[tid * 9 + e];
+    restoresu3(out, z);
+#pragma unroll
+    for (int e = 0; e < 9; e++) sl[tid * 9 + e] = out[e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    const int idx = j * 256 + tid;
+    if (idx < nl * 9) raw[l0 * 9 + idx] = sl[idx];
+  }
 }
 
 // T-split rank: dir 1 (U_t(x - t)) of the t = 0 sites <- the t = -1 halo slab of the lexicographic field (geometry_eo.c:296-298)
@@ -222,14 +263,21 @@ int tmhip_exchange_gauge_halo(tmhip_ctx *ctx) {
 }
 
 // links (-> updated links) -> stencil copy on ctx->stream; `halo`: the halo slabs of a T-split rank are current, finish the t = 0 sites
-static int launch_links(tmhip_ctx *ctx, bool update, double step) {
+static int launch_links(tmhip_ctx *ctx, int mode, double step) {
   const int toff = ctx->g.proc_t * ctx->g.T, split = ctx->g.nproc_t > 1 ? 1 : 0;
-  const unsigned nb = (unsigned)(((size_t)ctx->V * 4 + 255) / 256);
-  if (update)
-    hipLaunchKernelGGL(links_kernel<true>, dim3(nb), dim3(256), 0, ctx->stream, ctx->gauge_raw, (const double *)ctx->momenta, ctx->gauge, ctx->gs, ctx->V, ctx->Vh,
+  const int VT = mode == LINKS_REUNIT || mode == LINKS_COPY ? ctx->VPR : ctx->V;
+  const unsigned nb = (unsigned)(((size_t)VT * 4 + 255) / 256);
+  if (mode == LINKS_UPDATE)
+    hipLaunchKernelGGL(links_kernel<LINKS_UPDATE>, dim3(nb), dim3(256), 0, ctx->stream, ctx->gauge_raw, (const double *)ctx->momenta, ctx->gauge, ctx->gs, ctx->V, VT,
                        ctx->g.T, ctx->g.LX, ctx->g.LY, ctx->g.LZ, toff, split, step);
+  else if (mode == LINKS_REUNIT)
+    hipLaunchKernelGGL(links_kernel<LINKS_REUNIT>, dim3(nb), dim3(256), 0, ctx->stream, ctx->gauge_raw, (const double *)nullptr, ctx->gauge, ctx->gs, ctx->V, VT,
+                       ctx->g.T, ctx->g.LX, ctx->g.LY, ctx->g.LZ, toff, split, 0.0);
+  else if (mode == LINKS_COPY)
+    hipLaunchKernelGGL(links_kernel<LINKS_COPY>, dim3(nb), dim3(256), 0, ctx->stream, ctx->gauge_raw, (const double *)ctx->gauge_snap, ctx->gauge, ctx->gs, ctx->V, VT,
+                       ctx->g.T, ctx->g.LX, ctx->g.LY, ctx->g.LZ, toff, split, 0.0);
   else
-    hipLaunchKernelGGL(links_kernel<false>, dim3(nb), dim3(256), 0, ctx->stream, ctx->gauge_raw, (const double *)nullptr, ctx->gauge, ctx->gs, ctx->V, ctx->Vh,
+    hipLaunchKernelGGL(links_kernel<LINKS_RESORT>, dim3(nb), dim3(256), 0, ctx->stream, ctx->gauge_raw, (const double *)nullptr, ctx->gauge, ctx->gs, ctx->V, VT,
                        ctx->g.T, ctx->g.LX, ctx->g.LY, ctx->g.LZ, toff, split, 0.0);
   TMHIP_CHECK(hipGetLastError());
   return 0;
@@ -259,7 +307,7 @@ static int links_changed(tmhip_ctx *ctx) {
 // the stencil's gauge copy (and everything derived from the links) from the device-resident lexicographic field, halo slabs included
 int tmhip_resort_gauge(tmhip_ctx *ctx) {
   if (!ctx->gauge_raw || !ctx->gauge_raw_valid) TMHIP_FAIL("no lexicographic gauge field on the device");
-  if (launch_links(ctx, false, 0.0) || launch_halo_backward(ctx)) return 1;
+  if (launch_links(ctx, LINKS_RESORT, 0.0) || launch_halo_backward(ctx)) return 1;
   return links_changed(ctx);
 }
 
@@ -405,6 +453,7 @@ int tmhip_momenta_upload(tmhip_ctx *ctx, const void *host) {
   if (!ctx->momenta) TMHIP_CHECK(hipMalloc((void **)&ctx->momenta, bytes));
   TMHIP_CHECK(hipMemcpyAsync(ctx->momenta, host, bytes, hipMemcpyHostToDevice, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ctx->xfer[2]++;
   return 0;
 }
 
@@ -414,6 +463,7 @@ int tmhip_momenta_download(tmhip_ctx *ctx, void *host) {
   TMHIP_CHECK(hipSetDevice(ctx->device));
   TMHIP_CHECK(hipMemcpyAsync(host, ctx->momenta, (size_t)ctx->V * 32 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ctx->xfer[3]++;
   return 0;
 }
 
@@ -434,10 +484,92 @@ int tmhip_update_gauge(tmhip_ctx *ctx, double step) {
   if (!ctx->gauge_raw || !ctx->gauge_raw_valid) TMHIP_FAIL("tmhip_update_gauge: the links are not resident (tmhip_set_gauge first)");
   if (!ctx->momenta) TMHIP_FAIL("tmhip_update_gauge: no momenta on the device (tmhip_momenta_upload)");
   TMHIP_CHECK(hipSetDevice(ctx->device));
-  if (launch_links(ctx, true, step)) return 1;                 // exp(step P) U, back to the lexicographic field and into the stencil copy
+  if (launch_links(ctx, LINKS_UPDATE, step)) return 1;                 // exp(step P) U, back to the lexicographic field and into the stencil copy
   if (tmhip_exchange_gauge_halo(ctx)) return 1;
   if (launch_halo_backward(ctx)) return 1;                     // T-split: the backward t-links of the t = 0 sites from the neighbour's updated slice
   // clover blocks belong to the old links: tmhip_sw_term (gauge = NULL: from the resident links) / tmhip_sw_invert again
+  ctx->sw_set = false; ctx->clover_set = false; ctx->sw_inv_ieo = -1; ctx->clover_nd_set = false; ctx->clover32_set = false;
+  return links_changed(ctx);
+}
+
+/* ---- the links around a trajectory: gauge_tmp of update_tm.c on the device ---- */
+/* update_tm.c:109-121: gauge_tmp <- links (halo slabs of a T-split rank included, so that a restore needs no exchange) */
+int tmhip_gauge_snapshot(tmhip_ctx *ctx) {
+  if (!ctx->gauge_raw || !ctx->gauge_raw_valid) TMHIP_FAIL("tmhip_gauge_snapshot: the links are not resident (tmhip_set_gauge first)");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)ctx->VPR * 36 * sizeof(v2d);
+  if (!ctx->gauge_snap) TMHIP_CHECK(hipMalloc((void **)&ctx->gauge_snap, bytes));
+  TMHIP_CHECK(hipMemcpyAsync(ctx->gauge_snap, ctx->gauge_raw, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  return 0;
+}
+
+int tmhip_gauge_snapshot_free(tmhip_ctx *ctx) {
+  if (!ctx->gauge_snap) return 0;
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  TMHIP_CHECK(hipFree(ctx->gauge_snap));
+  ctx->gauge_snap = nullptr;
+  return 0;
+}
+
+// The two ways to put the snapshot back.  tmhip_bench_trajectory_forms measures both (profiles/r17_traj_speed.log: 0.572 against 0.445 ms at
+// 32^4); tmhip_gauge_restore uses the one pass.
+static int restore_two_launches(tmhip_ctx *ctx) {   // device-to-device copy, then the plain re-sort: 576 + 576 + 576 + 1152 bytes per site
+  TMHIP_CHECK(hipMemcpyAsync(ctx->gauge_raw, ctx->gauge_snap, (size_t)ctx->VPR * 36 * sizeof(v2d), hipMemcpyDeviceToDevice, ctx->stream));
+  return launch_links(ctx, LINKS_RESORT, 0.0);
+}
+static int restore_one_pass(tmhip_ctx *ctx) {       // the re-sort reads the snapshot and writes the links as well: 576 + 576 + 1152
+  return launch_links(ctx, LINKS_COPY, 0.0);
+}
+
+/* update_tm.c:329-339 (reject): links <- gauge_tmp and the stencil's copy from them; everything derived from the links is left as
+ * tmhip_update_gauge leaves it */
+int tmhip_gauge_restore(tmhip_ctx *ctx) {
+  if (!ctx->gauge_snap) TMHIP_FAIL("tmhip_gauge_restore: no snapshot (tmhip_gauge_snapshot first)");
+  if (!ctx->gauge_raw) TMHIP_FAIL("tmhip_gauge_restore: the links are not resident (tmhip_set_gauge first)");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (restore_one_pass(ctx)) return 1;
+  ctx->gauge_raw_valid = true;
+  if (launch_halo_backward(ctx)) return 1;
+  ctx->sw_set = false; ctx->clover_set = false; ctx->sw_inv_ieo = -1; ctx->clover_nd_set = false; ctx->clover32_set = false;
+  return links_changed(ctx);
+}
+
+/* update_tm.c:313-328 (accept): restoresu3_in_place on every link, own and halo, and the stencil's copy from them, in one pass */
+int tmhip_gauge_reunitarize(tmhip_ctx *ctx) {
+  if (!ctx->gauge_raw || !ctx->gauge_raw_valid) TMHIP_FAIL("tmhip_gauge_reunitarize: the links are not resident (tmhip_set_gauge first)");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  if (launch_links(ctx, LINKS_REUNIT, 0.0) || launch_halo_backward(ctx)) return 1;
+  ctx->sw_set = false; ctx->clover_set = false; ctx->sw_inv_ieo = -1; ctx->clover_nd_set = false; ctx->clover32_set = false;
+  return links_changed(ctx);
+}
+
+/* Device time (HIP events, per call, over `reps` calls) of one form of the reject / accept pass, for tools/traj_speed.py:
+ *   form 0  restore as a device-to-device copy + the plain re-sort      1  restore as one pass (the re-sort reads the snapshot)
+ *   form 2  accept as restoresu3 pass + the plain re-sort               3  accept as one pass (LINKS_REUNIT)
+ * Needs resident links and a snapshot.  The links end up restored (0, 1) or reunitarised (2, 3), the derived state as after the call
+ * measured. */
+int tmhip_bench_trajectory_forms(tmhip_ctx *ctx, int form, int reps, double *ms) {
+  if (!ms || form < 0 || form > 3 || reps < 1) TMHIP_FAIL("tmhip_bench_trajectory_forms: bad argument");
+  if (!ctx->gauge_raw || !ctx->gauge_raw_valid || !ctx->gauge_snap) TMHIP_FAIL("tmhip_bench_trajectory_forms: needs resident links and a snapshot");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  const size_t nlinks = (size_t)ctx->VPR * 4;
+  for (int r = -1; r < reps; r++) {   // (one warm call)
+    if (r == 0) TMHIP_CHECK(hipEventRecord(ctx->ev_slots[14], ctx->stream));
+    int rc = 0;
+    if (form == 0) rc = restore_two_launches(ctx);
+    else if (form == 1) rc = restore_one_pass(ctx);
+    else if (form == 2) {
+      hipLaunchKernelGGL(reunit_only_kernel, dim3((unsigned)((nlinks + 255) / 256)), dim3(256), 0, ctx->stream, ctx->gauge_raw, nlinks);
+      rc = launch_links(ctx, LINKS_RESORT, 0.0);
+    } else rc = launch_links(ctx, LINKS_REUNIT, 0.0);
+    if (rc || launch_halo_backward(ctx)) return 1;
+  }
+  TMHIP_CHECK(hipEventRecord(ctx->ev_slots[15], ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  float t = 0.f;
+  TMHIP_CHECK(hipEventElapsedTime(&t, ctx->ev_slots[14], ctx->ev_slots[15]));
+  *ms = (double)t / reps;
   ctx->sw_set = false; ctx->clover_set = false; ctx->sw_inv_ieo = -1; ctx->clover_nd_set = false; ctx->clover32_set = false;
   return links_changed(ctx);
 }
@@ -451,7 +583,7 @@ int tmhip_multi_update_gauge(int n, tmhip_ctx **ctxs, double step) {
     if (c->g.nproc_t != n || c->g.proc_t != r) TMHIP_FAIL("context %d is not rank %d of a %d-way T split", r, r, n);
     if (!c->gauge_raw || !c->gauge_raw_valid || !c->momenta) TMHIP_FAIL("tmhip_multi_update_gauge: rank %d has no resident links / momenta", r);
     TMHIP_CHECK(hipSetDevice(c->device));
-    if (launch_links(c, true, step)) return 1;
+    if (launch_links(c, LINKS_UPDATE, step)) return 1;
   }
   for (int r = 0; r < n; r++) { TMHIP_CHECK(hipSetDevice(ctxs[r]->device)); TMHIP_CHECK(hipStreamSynchronize(ctxs[r]->stream)); }
   const size_t XYZ = (size_t)ctxs[0]->g.LX * ctxs[0]->g.LY * ctxs[0]->g.LZ, sb = XYZ * 36 * sizeof(v2d);
@@ -476,6 +608,7 @@ int tmhip_gauge_download(tmhip_ctx *ctx, void *host) {
   TMHIP_CHECK(hipSetDevice(ctx->device));
   TMHIP_CHECK(hipMemcpyAsync(host, ctx->gauge_raw, (size_t)ctx->VPR * 36 * sizeof(v2d), hipMemcpyDeviceToHost, ctx->stream));
   TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ctx->xfer[1]++;
   return 0;
 }
 

@@ -141,6 +141,8 @@ struct tmhip_ctx {
   v2d *gauge_raw;      // lexicographic gauge field [VPR][4][9] kept from the last tmhip_sw_term for tmhip_sw_all; gauge_raw_valid
   bool gauge_raw_valid;
   bool gauge_copy_current;   // the stencil's gauge copy was sorted from the links now in gauge_raw
+  long long xfer[4];   // host <-> device copies of whole fields so far: tmhip_set_gauge, tmhip_gauge_download, tmhip_momenta_upload, tmhip_momenta_download (tmhip_transfer_counts)
+  v2d *gauge_snap;     // tmhip_gauge_snapshot: gauge_tmp of update_tm.c, [VPR][4][9] as gauge_raw (nullptr: no snapshot)
   unsigned *io_sums;   // SciDAC checksum words A, B accumulated by the ILDG pack / unpack kernels (ildg.hip)
   int *sw_fail;        // device counter of near-singular pivots met by tmhip_sw_invert
   int *sw_trace_fail;  // the same for tmhip_sw_trace / tmhip_sw_trace_nd (six_det's ifail), and its value after the last call

@@ -106,6 +106,10 @@ def load_library():
         "tmhip_sw_term": [vp, vp, d, d],
         "tmhip_momenta_upload": [vp, vp], "tmhip_momenta_download": [vp, vp], "tmhip_update_momenta": [vp, d],
         "tmhip_update_gauge": [vp, d], "tmhip_gauge_download": [vp, vp],
+        "tmhip_gauge_snapshot": [vp], "tmhip_gauge_restore": [vp], "tmhip_gauge_snapshot_free": [vp], "tmhip_gauge_reunitarize": [vp],
+        "tmhip_gauge_snapshot_diff": [vp, pd], "tmhip_moment_energy": [vp, pd], "tmhip_derivative_norms": [vp, pd, pd],
+        "tmhip_derivative_upload": [vp, vp], "tmhip_transfer_counts": [vp, C.POINTER(C.c_longlong)],
+        "tmhip_bench_trajectory_forms": [vp, i, i, pd],
         "tmhip_gauge_derivative": [vp, d, d, d, i, d],
         "tmhip_measure_plaquette": [vp, pd], "tmhip_measure_gauge_action": [vp, d, pd], "tmhip_measure_rectangles": [vp, pd],
         "tmhip_measure_field_strength": [vp, pd, pd], "tmhip_flow_begin": [vp], "tmhip_flow_step": [vp, d],
@@ -531,6 +535,58 @@ class Lattice:
         out = np.zeros((self.VPR, 4, 3, 3, 2))
         _ck(self.lib.tmhip_gauge_download(self.h, _hp(out)), "tmhip_gauge_download")
         return out
+
+    # --- the frame of a trajectory on the resident fields (update_tm.c, moment_energy.c, monitor_forces.c) ---------------
+    def gauge_snapshot(self):
+        """gauge_tmp <- links (update_tm.c:109-121), in a device buffer of its own."""
+        _ck(self.lib.tmhip_gauge_snapshot(self.h), "gauge_snapshot")
+
+    def gauge_restore(self):
+        """links <- gauge_tmp (update_tm.c:329-339, reject); the stencil's copy follows, the clover blocks become stale."""
+        _ck(self.lib.tmhip_gauge_restore(self.h), "gauge_restore")
+
+    def gauge_snapshot_free(self):
+        _ck(self.lib.tmhip_gauge_snapshot_free(self.h), "gauge_snapshot_free")
+
+    def gauge_reunitarize(self):
+        """restoresu3_in_place on every link (update_tm.c:313-328, accept); derived state as after update_gauge."""
+        _ck(self.lib.tmhip_gauge_reunitarize(self.h), "gauge_reunitarize")
+
+    def gauge_snapshot_diff(self):
+        """sum over the own links of sqrt(|U - U_tmp|_F^2) (update_tm.c:233-272)."""
+        out = C.c_double(0.0)
+        _ck(self.lib.tmhip_gauge_snapshot_diff(self.h, C.byref(out)), "gauge_snapshot_diff")
+        return out.value
+
+    def moment_energy(self):
+        """0.5 * sum over the own links of |P|^2 of the resident momenta (moment_energy.c:46-74)."""
+        out = C.c_double(0.0)
+        _ck(self.lib.tmhip_moment_energy(self.h, C.byref(out)), "moment_energy")
+        return out.value
+
+    def derivative_norms(self):
+        """(sum, max) over the own links of d1^2 + ... + d8^2 of the resident derivative (monitor_forces.c:64-89)."""
+        s, m = C.c_double(0.0), C.c_double(0.0)
+        _ck(self.lib.tmhip_derivative_norms(self.h, C.byref(s), C.byref(m)), "derivative_norms")
+        return s.value, m.value
+
+    def transfer_counts(self):
+        """whole-field copies so far: (set_gauge, gauge_download, momenta_upload, momenta_download)"""
+        out = (C.c_longlong * 4)()
+        _ck(self.lib.tmhip_transfer_counts(self.h, out), "tmhip_transfer_counts")
+        return tuple(int(v) for v in out)
+
+    def bench_trajectory_forms(self, form, reps):
+        """device ms per call of one form of the reject / accept pass (tmhip_bench_trajectory_forms)"""
+        out = C.c_double(0.0)
+        _ck(self.lib.tmhip_bench_trajectory_forms(self.h, form, reps, C.byref(out)), "tmhip_bench_trajectory_forms")
+        return out.value
+
+    def derivative_upload(self, df):
+        """su3adj df[V][4][8] (host) replaces the device derivative field."""
+        if df.shape != (self.V, 4, 8):
+            raise TmHipError("derivative must be [V=%d][4][8]" % self.V)
+        _ck(self.lib.tmhip_derivative_upload(self.h, _hp(df)), "tmhip_derivative_upload")
 
     # --- gauge monomial on the resident links (monomial/gauge_monomial.c, measure_gauge_action.c, measure_rectangles.c) ---
     def gauge_derivative(self, beta, c0=1.0, c1=0.0, use_rectangles=False, glambda=0.0):
