@@ -150,12 +150,15 @@ int tmhip_multi_assign_diff_mul(tmhip_ctx *ctx, int n, tmhip_field *const *R, tm
 int tmhip_lincomb(tmhip_ctx *ctx, tmhip_field *P, int n, tmhip_field *const *V, const double *c /* 2n */, int N);
 
 /* ---- solver --------------------------------------------------------------- */
+/* The operators a solver takes as `op`, by the reference's function.  Which field kind an id acts on, whether it needs a valid clover
+ * term and which solvers take it is ONE list, tmlqcd_amd/csrc/op_table.h; a solver refuses, with a message and before it writes
+ * anything, an id outside that list, an id that is not in its column, fields of another kind than the row's, and a clover row on a
+ * context without a valid clover term. */
 enum { TMHIP_OP_QTM_PM = 0, TMHIP_OP_QTM_PLUS = 1, TMHIP_OP_QTM_MINUS = 2, TMHIP_OP_MTM_PLUS = 3, TMHIP_OP_MTM_MINUS = 4,
-       TMHIP_OP_QSW_PM = 5 /* clover: Qsw_pm_psi, needs tmhip_set_clover */,
-       TMHIP_OP_Q_PM_FULL = 6 /* Q_pm_psi on FULL fields (tm_operators.c:380-388): tmhip_cg_mms_tm only, tmhip_cg_her refuses it */,
-       /* the non-hermitian operators of tmhip_bicgstab_complex (which also takes ids 1-4); every other solver refuses them */
+       TMHIP_OP_QSW_PM = 5 /* Qsw_pm_psi */,
+       TMHIP_OP_Q_PM_FULL = 6 /* Q_pm_psi on FULL fields (tm_operators.c:380-388) */,
        TMHIP_OP_MTM_PLUS_SYM = 7, TMHIP_OP_MTM_MINUS_SYM = 8 /* Mtm_plus/minus_sym_psi */,
-       TMHIP_OP_QSW_PLUS = 9, TMHIP_OP_QSW_MINUS = 10, TMHIP_OP_MSW_PLUS = 11 /* clover: Qsw_plus/minus_psi, Msw_plus_psi */,
+       TMHIP_OP_QSW_PLUS = 9, TMHIP_OP_QSW_MINUS = 10, TMHIP_OP_MSW_PLUS = 11 /* Qsw_plus/minus_psi, Msw_plus_psi */,
        TMHIP_OP_D_PSI = 12 /* D_psi on FULL fields, N = VOLUME */ };
 /* cg_her(P,Q,max_iter,eps_sq,rel_prec,N,f)   solver/cg_her.c:62-141.
  * Device-resident: P, Q and the three work fields never leave HBM.  Returns the
@@ -175,8 +178,8 @@ int tmhip_assign_add_mul_add_mul(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S,
 int tmhip_assign_mul_bra_add_mul_ket_add(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, tmhip_field *U, double c1_re, double c1_im, double c2_re,
                                          double c2_im, int N);
 /* bicgstab_complex(P,Q,max_iter,eps_sq,rel_prec,N,f): P is the starting guess and receives the solution, *iters the reference's return
- * value (i, or -1 after max_iter iterations or on the breakdown of :102).  op: TMHIP_OP_QTM_PLUS .. TMHIP_OP_MTM_MINUS and
- * TMHIP_OP_MTM_PLUS_SYM .. TMHIP_OP_MSW_PLUS on EO fields with N = VOLUME/2, TMHIP_OP_D_PSI on FULL fields with N = VOLUME.  res_hist (may
+ * value (i, or -1 after max_iter iterations or on the breakdown of :102).  op: the rows of the operator table that name this solver,
+ * on EO fields with N = VOLUME/2 or on FULL fields with N = VOLUME as the row says.  res_hist (may
  * be NULL) gets |r|^2 at the top of every iteration the reference runs, entry 0 being the starting residual: up to iters + 1 entries.
  * Six work fields of the context per field kind are allocated on first use and freed with the context.
  * Option "bicg_fused" (tmhip_set_option) 1 (default): the five fused kernels K1-K5 of bicgstab.hip with the scalars in a device state block

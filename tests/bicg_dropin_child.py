@@ -6,6 +6,8 @@ libtmlqcd_dropin.so.  In the residency mode given on the command line (coherent 
   - bicgstab_complex with f = &Mtm_plus_sym_psi on VOLUME/2 sites and f = &D_psi on VOLUME sites, on the inputs of the 4^4 fixture
     (tests/golden/ref_bicg_*), counting the entry-point calls the library served meanwhile (tmlqcd_hip_calls),
   - bicgstab_complex with a foreign f (a callback: the drop-in's Mtm_plus_sym_psi plus 0.1 times the input), which takes the host loop,
+  - cg_her with f = &Mtm_plus_sym_psi and bicgstab_complex with f = &Qtm_pm_psi on VOLUME/2 sites, three iterations each: operators of
+    the library, but outside the respective solver's set, so both take the host loop too (only tmlqcd_hip_calls is counted),
 and prints the results as one JSON line."""
 import ctypes as C
 import json
@@ -50,6 +52,8 @@ def main(mode):
         getattr(d, name).argtypes = [VP, VP, VP, dbl, dbl, dbl, dbl, INT]      # _Complex double by value: (re, im) in two SSE registers
     d.bicgstab_complex.restype = INT
     d.bicgstab_complex.argtypes = [VP, VP, INT, dbl, INT, INT, VP]
+    d.cg_her.restype = INT
+    d.cg_her.argtypes = [VP, VP, INT, dbl, INT, INT, VP]
     d.Mtm_plus_sym_psi.restype = None
     d.Mtm_plus_sym_psi.argtypes = [VP, VP]
 
@@ -124,6 +128,16 @@ def main(mode):
         o += 0.1 * np.frombuffer((dbl * (N * 24)).from_address(k), dtype=np.float64)
     cb = C.CFUNCTYPE(None, VP, VP)(shifted)
     out["solves"]["foreign"] = solve("mtm_plus_sym", C.cast(cb, VP), shift=0.1)
+
+    # ---- operators the library knows, handed to a solver that does not take them: the host loop again, many entry-point calls
+    def routed(solver, fptr):
+        stub.stub_set_mu(0.02)
+        q, p = arr(random_spinor(4, N)), arr()
+        before = d.tmlqcd_hip_calls()
+        solver(p[1], q[1], 3, 1.0e-30, 0, N, fptr)
+        return int(d.tmlqcd_hip_calls() - before)
+    out["routing"] = {"cg_her_mtm_plus_sym": routed(d.cg_her, C.cast(d.Mtm_plus_sym_psi, VP)),
+                      "bicgstab_qtm_pm": routed(d.bicgstab_complex, C.cast(d.Qtm_pm_psi, VP))}
     out["margin"] = s["margin"]
     d.tmlqcd_hip_set_residency(0)
     print(json.dumps(out))

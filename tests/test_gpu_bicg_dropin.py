@@ -32,3 +32,7 @@ def test_dropin_symbols(mode):
     assert 0 < g["iters"] <= 10 * g["restated_iters"] and g["q_unchanged"], g   # (no count is pinned for an operator the fixtures do not cover)
     assert g["calls"] > 10 * g["iters"], g                      # the host loop: every statement of every iteration is a call of its own
     assert g["true"] <= g["bound"] * out["margin"], g
+    # an operator of the library outside the solver's set takes the host loop as well: more than one entry-point call served
+    assert set(out["routing"]) == {"cg_her_mtm_plus_sym", "bicgstab_qtm_pm"}
+    for name, calls in out["routing"].items():
+        assert calls > 1, (name, calls)

@@ -271,23 +271,6 @@ static int shape_of(tmhip_ctx *ctx, const char *who, int N, int nf, tmhip_field 
   return 0;
 }
 
-// the solver's own dispatch: tmhip_apply_op (cg.hip) keeps the set of the Hermitian solvers
-static int apply(tmhip_ctx *ctx, int op, tmhip_field *l, tmhip_field *k) {
-  switch (op) {
-    case TMHIP_OP_QTM_PLUS: return tmhip_Qtm_plus_psi(ctx, l, k);
-    case TMHIP_OP_QTM_MINUS: return tmhip_Qtm_minus_psi(ctx, l, k);
-    case TMHIP_OP_MTM_PLUS: return tmhip_Mtm_plus_psi(ctx, l, k);
-    case TMHIP_OP_MTM_MINUS: return tmhip_Mtm_minus_psi(ctx, l, k);
-    case TMHIP_OP_MTM_PLUS_SYM: return tmhip_Mtm_plus_sym_psi(ctx, l, k);
-    case TMHIP_OP_MTM_MINUS_SYM: return tmhip_Mtm_minus_sym_psi(ctx, l, k);
-    case TMHIP_OP_QSW_PLUS: return tmhip_Qsw_plus_psi(ctx, l, k);
-    case TMHIP_OP_QSW_MINUS: return tmhip_Qsw_minus_psi(ctx, l, k);
-    case TMHIP_OP_MSW_PLUS: return tmhip_Msw_plus_psi(ctx, l, k);
-    case TMHIP_OP_D_PSI: return tmhip_D_psi(ctx, l, k);
-  }
-  TMHIP_FAIL("bicgstab_complex: unknown operator id %d", op);
-}
-
 // ---- the singles on fields of either kind: a FULL field is its two halves, one call each, sums added even first
 static inline tmhip_field *part(tmhip_field *f, int h) { return f->kind == TMHIP_FIELD_FULL ? f->half[h] : f; }
 static int s_assign(tmhip_ctx *c, const Shape &sh, tmhip_field *R, tmhip_field *S) {
@@ -330,11 +313,11 @@ static int solve_singles(tmhip_ctx *ctx, const Shape &sh, Work *w, BicgState &h,
     if (s_square_norm(ctx, sh, r, &err)) return 1;
     if (res_hist && i < hist_len) res_hist[i] = err;
     if (converged(err, h.eps_sq, h.squarenorm, h.rel_prec) && i > 0) { h.done = 1; h.iters = i; return 0; }
-    if (apply(ctx, op, v, p)) return 1;
+    if (tmhip_apply_op(ctx, op, v, p)) return 1;
     if (s_scalar_prod(ctx, sh, hatr, v, denom)) return 1;
     after_K1(h, denom);
     if (s_assign(ctx, sh, s, r) || s_assign_diff_mul(ctx, sh, s, v, h.alpha)) return 1;
-    if (apply(ctx, op, t, s)) return 1;
+    if (tmhip_apply_op(ctx, op, t, s)) return 1;
     if (s_scalar_prod(ctx, sh, t, s, ts) || s_square_norm(ctx, sh, t, &tt)) return 1;
     after_K3(h, ts, tt);
     if (tmhip_assign_add_mul_add_mul(ctx, P, p, s, h.alpha[0], h.alpha[1], h.omega[0], h.omega[1], N)) return 1;
@@ -360,11 +343,11 @@ static int enqueue_iteration(tmhip_ctx *ctx, const Shape &sh, Work *w, tmhip_fie
   const int ns = P->ns;
   BicgState *st = w->st;
   const dim3 bs(LA_BS);
-  if (apply(ctx, op, f[2], f[3])) return 1;
+  if (tmhip_apply_op(ctx, op, f[2], f[3])) return 1;
   hipLaunchKernelGGL(dot_kernel<false>, sh.grid, bs, 0, ctx->stream, (const v2d *)hatr, (const v2d *)v, ns, sh.n, w->partials, (const BicgState *)st);
   hipLaunchKernelGGL(sum_scalar_kernel<1>, dim3(1), dim3(1024), 0, ctx->stream, (const double *)w->partials, sh.per, sh.halves, st, w->sums, w->hist, w->hist_len);
   hipLaunchKernelGGL(sub_kernel, sh.grid, bs, 0, ctx->stream, s, (const v2d *)r, (const v2d *)v, ns, sh.n, (const BicgState *)st);
-  if (apply(ctx, op, f[5], f[4])) return 1;
+  if (tmhip_apply_op(ctx, op, f[5], f[4])) return 1;
   hipLaunchKernelGGL(dot_kernel<true>, sh.grid, bs, 0, ctx->stream, (const v2d *)t, (const v2d *)s, ns, sh.n, w->partials, (const BicgState *)st);
   hipLaunchKernelGGL(sum_scalar_kernel<3>, dim3(1), dim3(1024), 0, ctx->stream, (const double *)w->partials, sh.per, sh.halves, st, w->sums, w->hist, w->hist_len);
   hipLaunchKernelGGL(update_kernel, sh.grid, bs, 0, ctx->stream, P->d, r, (const v2d *)p, (const v2d *)s, (const v2d *)t, (const v2d *)hatr, ns, sh.n,
@@ -465,18 +448,13 @@ int tmhip_bicgstab_complex(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int m
   const char *who = "bicgstab_complex";
   if (!iters) TMHIP_FAIL("%s: null argument", who);
   if (refuse_split(ctx, who)) return 1;
-  const bool known = (op >= TMHIP_OP_QTM_PLUS && op <= TMHIP_OP_MTM_MINUS) || (op >= TMHIP_OP_MTM_PLUS_SYM && op <= TMHIP_OP_D_PSI);
-  if (!known) TMHIP_FAIL("%s: operator id %d is not one of its operators (Qtm/Mtm_plus/minus_psi, Mtm_plus/minus_sym_psi, Qsw_plus/minus_psi, Msw_plus_psi, D_psi)", who, op);
-  const int kind = op == TMHIP_OP_D_PSI ? TMHIP_FIELD_FULL : TMHIP_FIELD_EO;
+  if (!P || !Q || P->kind != Q->kind) TMHIP_FAIL("%s needs two fields of one kind", who);
+  if (tmhip_op_check(ctx, who, TMHIP_S_BICG, op, P->kind)) return 1;
+  const int kind = P->kind;
   tmhip_field *pq[2] = {P, Q};
   Shape sh;
-  if (P && Q && (P->kind != kind || Q->kind != kind)) TMHIP_FAIL("%s: operator %d acts on %s fields", who, op, kind == TMHIP_FIELD_FULL ? "FULL" : "one-parity (EO)");
   if (shape_of(ctx, who, N, 2, pq, &sh)) return 1;
   if (P->d == Q->d) TMHIP_FAIL("%s: P and Q must differ", who);
-  if (op >= TMHIP_OP_QSW_PLUS && op <= TMHIP_OP_MSW_PLUS) {
-    if (!ctx->clover_set) TMHIP_FAIL("%s: clover operator without a valid clover term (tmhip_set_clover / tmhip_sw_term and tmhip_sw_invert)", who);
-    if (op == TMHIP_OP_QSW_MINUS && fabs(ctx->mu) > 0 && ctx->sw_inv_sets < 2) TMHIP_FAIL("%s: Qsw_minus_psi with mu != 0 needs the -mu set of sw_inv (sw_invert with the current mu)", who);
-  }
   if (!ctx->gauge_set) TMHIP_FAIL("%s called before tmhip_set_gauge", who);
   Work *w;
   if (work(ctx, kind, true, &w)) return 1;
@@ -492,7 +470,7 @@ int tmhip_bicgstab_complex(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int m
   BicgState h;
   memset(&h, 0, sizeof(h));
   h.eps_sq = eps_sq; h.rel_prec = rel_prec; h.max_iter = max_iter;
-  if (apply(ctx, op, r, P)) return 1;
+  if (tmhip_apply_op(ctx, op, r, P)) return 1;
   if (s_diff(ctx, sh, p, Q, r) || s_assign(ctx, sh, r, p) || s_assign(ctx, sh, hatr, p)) return 1;
   if (s_scalar_prod(ctx, sh, hatr, r, h.rho0) || s_square_norm(ctx, sh, Q, &h.squarenorm)) return 1;
   if (!ctx->opt_bicg_fused) {

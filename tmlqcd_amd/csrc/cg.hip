@@ -333,19 +333,6 @@ __global__ __launch_bounds__(CG_SUM_BS) void cg_sum_xsum_scalar_kernel(const dou
   if (lw >= 0 && lw < NW) reinterpret_cast<double *>(st)[lw] = reinterpret_cast<const double *>(&ls)[lw];
 }
 
-int tmhip_apply_op(tmhip_ctx *ctx, int op, tmhip_field *l, tmhip_field *k) {
-  switch (op) {
-    case TMHIP_OP_QTM_PM: return tmhip_Qtm_pm_psi(ctx, l, k);
-    case TMHIP_OP_QTM_PLUS: return tmhip_Qtm_plus_psi(ctx, l, k);
-    case TMHIP_OP_QTM_MINUS: return tmhip_Qtm_minus_psi(ctx, l, k);
-    case TMHIP_OP_MTM_PLUS: return tmhip_Mtm_plus_psi(ctx, l, k);
-    case TMHIP_OP_MTM_MINUS: return tmhip_Mtm_minus_psi(ctx, l, k);
-    case TMHIP_OP_QSW_PM: return tmhip_Qsw_pm_psi(ctx, l, k);
-  }
-  fprintf(stderr, "[tmlqcd_hip] cg_her: unknown operator id %d\n", op);
-  return 1;
-}
-
 // straightforward port of the reference loop: three host round trips per iteration (kept for A/B: option cg_sync=1)
 static int cg_her_sync(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec, int N, int op,
                        int *iters, double *res_hist, int hist_len) {
@@ -533,9 +520,9 @@ static int cg_enqueue_iteration(tmhip_ctx *ctx, int op, bool fp32, bool fused, C
 
 extern "C" int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec, int N,
                             int op, int *iters, double *res_hist, int hist_len) {
-  if (!P || !Q || P->kind != TMHIP_FIELD_EO || Q->kind != TMHIP_FIELD_EO) TMHIP_FAIL("cg_her needs one-parity (EO) fields");
+  if (!P || !Q || P->kind != Q->kind) TMHIP_FAIL("cg_her needs two fields of one kind");
+  if (tmhip_op_check(ctx, "cg_her", TMHIP_S_CG, op, P->kind)) return 1;
   if (N != ctx->Vh) TMHIP_FAIL("cg_her: N must be VOLUME/2");
-  if (op == TMHIP_OP_Q_PM_FULL) TMHIP_FAIL("cg_her: Q_pm_psi acts on FULL fields; cg_her takes the e/o operators only");
   if (ctx->opt_cg_sync) return cg_her_sync(ctx, P, Q, max_iter, eps_sq, rel_prec, N, op, iters, res_hist, hist_len);
   TMHIP_CHECK(hipSetDevice(ctx->device));
   if (cg_state_alloc(ctx)) return 1;
@@ -591,13 +578,12 @@ extern "C" int tmhip_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int 
  * device-resident loop of tmhip_cg_her instantiated for float2 fields with the stopping rule of :141. */
 extern "C" int tmhip_mixed_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec, int N,
                                   int op, double innereps, int max_inner_it, int *iters, int *outer_iters) {
-  if (!P || !Q || P->kind != TMHIP_FIELD_EO || Q->kind != TMHIP_FIELD_EO || P->prec || Q->prec) TMHIP_FAIL("mixed_cg_her needs fp64 one-parity fields");
+  if (!P || !Q || P->kind != Q->kind || P->prec || Q->prec) TMHIP_FAIL("mixed_cg_her needs two fp64 fields of one kind");
+  if (tmhip_op_check(ctx, "mixed_cg_her", TMHIP_S_MIXED, op, P->kind)) return 1;
   if (N != ctx->Vh) TMHIP_FAIL("mixed_cg_her: N must be VOLUME/2");
-  if (op != TMHIP_OP_QTM_PM && op != TMHIP_OP_QSW_PM) TMHIP_FAIL("mixed_cg_her: fp32 operators exist for Qtm_pm_psi and Qsw_pm_psi only");
   TMHIP_CHECK(hipSetDevice(ctx->device));
   if (tmhip_prepare_fp32(ctx)) return 1;
-  const bool clover = op == TMHIP_OP_QSW_PM;
-  if (clover && tmhip_prepare_clover32(ctx)) return 1;
+  if (tmhip_op_row_of(op)->clover && tmhip_prepare_clover32(ctx)) return 1;
   if (cg_state_alloc(ctx)) return 1;
   CgState *st = (CgState *)ctx->cg_state;
   int N_outer = max_iter / (max_inner_it > 0 ? max_inner_it : 1);
@@ -694,13 +680,12 @@ static int rg_inner_loop(tmhip_ctx *ctx, int op, bool fp32, bool fused, CgFields
  * falls back to fp64 inner loops.  Returns the reference's count iter_out + iter_in_sp + iter_in_dp, or -1. */
 extern "C" int tmhip_rg_mixed_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec, int N,
                                      int op, double delta_in, int *iters, int *iter_out_p, int *iter_sp_p, int *iter_dp_p) {
-  if (!P || !Q || P->kind != TMHIP_FIELD_EO || Q->kind != TMHIP_FIELD_EO || P->prec || Q->prec) TMHIP_FAIL("rg_mixed_cg_her needs fp64 one-parity fields");
+  if (!P || !Q || P->kind != Q->kind || P->prec || Q->prec) TMHIP_FAIL("rg_mixed_cg_her needs two fp64 fields of one kind");
+  if (tmhip_op_check(ctx, "rg_mixed_cg_her", TMHIP_S_MIXED, op, P->kind)) return 1;
   if (N != ctx->Vh) TMHIP_FAIL("rg_mixed_cg_her: N must be VOLUME/2");
-  if (op != TMHIP_OP_QTM_PM && op != TMHIP_OP_QSW_PM) TMHIP_FAIL("rg_mixed_cg_her: fp32 operators exist for Qtm_pm_psi and Qsw_pm_psi only");
   TMHIP_CHECK(hipSetDevice(ctx->device));
   if (tmhip_prepare_fp32(ctx)) return 1;
-  const bool clover = op == TMHIP_OP_QSW_PM;
-  if (clover && tmhip_prepare_clover32(ctx)) return 1;
+  if (tmhip_op_row_of(op)->clover && tmhip_prepare_clover32(ctx)) return 1;
   if (cg_state_alloc(ctx)) return 1;
   if (!ctx->sf_extra && tmhip_field_alloc(ctx, TMHIP_FIELD_EO, &ctx->sf_extra)) return 1;
   const bool split = ctx->g.nproc_t > 1 || ctx->loopback;

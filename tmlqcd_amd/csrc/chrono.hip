@@ -62,8 +62,9 @@ int tmhip_chrono_guess(tmhip_ctx *ctx, tmhip_field *trial, tmhip_field *phi, tmh
   if (!trial || trial->kind != TMHIP_FIELD_EO || trial->prec != 0) TMHIP_FAIL("chrono_guess: needs one-parity (EO) fp64 fields");
   if (n > TMHIP_CSG_MAX) TMHIP_FAIL("chrono_guess: %d vectors, at most %d are supported", n, TMHIP_CSG_MAX);
   if (N < 0 || N > ctx->Vh) TMHIP_FAIL("chrono_guess: N = %d is outside [0, VOLUME/2 = %d]", N, ctx->Vh);
-  if (n <= 0 || N == 0) return tmhip_field_zero(ctx, trial);
+  if (n <= 0 || N == 0) return tmhip_field_zero(ctx, trial);   // no operator is applied: `op` is not looked at
   if (!phi || !v) TMHIP_FAIL("chrono_guess: null argument");
+  if (tmhip_op_check(ctx, "chrono_guess", TMHIP_S_CG, op, trial->kind)) return 1;   // before step 1 rewrites the caller's older vectors
   const bool batched = ctx->opt_csg_batch && !tmhip_reduce_over_ranks(ctx) && N == ctx->Vh;
   tmhip_field *newest = v[n - 1];
   cplx s[TMHIP_CSG_MAX], G[TMHIP_CSG_MAX * TMHIP_CSG_MAX], b[TMHIP_CSG_MAX];

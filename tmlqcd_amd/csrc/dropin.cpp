@@ -119,6 +119,8 @@ struct Session {
     ensure_clover();
     return c;
   }
+  // a solve on row `op` of the operator table (op_table.h): a clover row needs the host's sw / sw_inv on the device
+  tmhip_ctx *refresh_for(int op) { return tmhip_op_row_of(op)->clover ? refresh_clover() : refresh(true); }
   tmhip_ctx *refresh_unsplit(const char *who, const char *what) {
     if (g_nproc_t > 1) {
       char m[160];
@@ -273,32 +275,36 @@ template <class F> inline void team_once(F body) {
 }
 
 int chrono_guess_generic(spinor *const trial, spinor *const phi, spinor **const v, const int *index_array, const int n, const int V, matrix_mult f);
-// the operators the device-resident solvers know by address (TMHIP_OP_*), -1 for any other function
-int op_of(matrix_mult f) {
-  if (f == &Qtm_pm_psi) return TMHIP_OP_QTM_PM;
-  if (f == &Qtm_plus_psi) return TMHIP_OP_QTM_PLUS;
-  if (f == &Qtm_minus_psi) return TMHIP_OP_QTM_MINUS;
-  if (f == &Mtm_plus_psi) return TMHIP_OP_MTM_PLUS;
-  if (f == &Mtm_minus_psi) return TMHIP_OP_MTM_MINUS;
-  if (f == &Qsw_pm_psi) return TMHIP_OP_QSW_PM;
+// The one lookup from the reference's functions to the rows of the operator table (op_table.h): the id `solver` (TMHIP_S_*) runs
+// device-resident for f on N sites, or -1 -- f is no row, N is not the site count of the row's fields, or the solver does not take
+// the row.  The FULL rows are not ours when g_c_sw > 0: there D_psi is Msw_full (d_psi_core), and Q_pm_psi is built on it.
+int dev_op_of(matrix_mult f, const int N, const int solver) {
+  static const struct { matrix_mult f; int id; } fn[] = {
+#define X(ID, NAME, KIND, SW, FP32, SOLVERS) {&NAME, TMHIP_OP_##ID},
+    TMHIP_OP_TABLE(X)
+#undef X
+  };
+  for (const auto &e : fn) {
+    if (e.f != f) continue;
+    const tmhip_op_row *r = tmhip_op_row_of(e.id);
+    const bool full = r->kind == TMHIP_FIELD_FULL;
+    if (N != (full ? VOLUME : VOLUME / 2) || !tmhip_op_taken(r, solver) || (full && &g_c_sw && g_c_sw > 0.)) return -1;
+    return e.id;
+  }
   return -1;
 }
+// the same for the doublet (TMHIP_ND_OP_*)
+int dev_nd_op_of(matrix_mult_nd f, const int N) {
+  static const struct { matrix_mult_nd f; int id; } fn[] = {
+#define X(ID, NAME, KIND, SW, FP32, SOLVERS) {&NAME, TMHIP_ND_OP_##ID},
+    TMHIP_ND_OP_TABLE(X)
+#undef X
+  };
+  for (const auto &e : fn) if (e.f == f) return N == VOLUME / 2 ? e.id : -1;
+  return -1;
+}
+int op_kind(int op) { return tmhip_op_row_of(op)->kind; }   // the kind of the fields row `op` acts on
 int cg_her_generic(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f);
-// the operators tmhip_bicgstab_complex knows by address, with the N they act on; -1 for any other pair (op_of above keeps cg_her's set)
-int bicg_op_of(matrix_mult f, const int N) {
-  if (N == VOLUME) return f == &D_psi && !(&g_c_sw && g_c_sw > 0.) ? TMHIP_OP_D_PSI : -1;   // (with g_c_sw > 0 D_psi is Msw_full: d_psi_core)
-  if (N != VOLUME / 2) return -1;
-  if (f == &Qtm_plus_psi) return TMHIP_OP_QTM_PLUS;
-  if (f == &Qtm_minus_psi) return TMHIP_OP_QTM_MINUS;
-  if (f == &Mtm_plus_psi) return TMHIP_OP_MTM_PLUS;
-  if (f == &Mtm_minus_psi) return TMHIP_OP_MTM_MINUS;
-  if (f == &Mtm_plus_sym_psi) return TMHIP_OP_MTM_PLUS_SYM;
-  if (f == &Mtm_minus_sym_psi) return TMHIP_OP_MTM_MINUS_SYM;
-  if (f == &Qsw_plus_psi) return TMHIP_OP_QSW_PLUS;
-  if (f == &Qsw_minus_psi) return TMHIP_OP_QSW_MINUS;
-  if (f == &Msw_plus_psi) return TMHIP_OP_MSW_PLUS;
-  return -1;
-}
 int bicgstab_complex_generic(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f);
 int cg_mms_tm_generic(spinor **const P, spinor *const Q, tmlqcd_solver_params *sp, double *cgmms_reached_prec);
 
@@ -888,9 +894,9 @@ void assign_to_64(spinor *const R, spinor32 *const S, const int N) {   /* linalg
  * drop-in linalg in COHERENT mode, which is correct for an arbitrary host-side f (cg_her_generic, at the end of this file). */
 int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N,
            matrix_mult f) {
-  const int op = op_of(f);
-  if (op < 0 || N != VOLUME / 2) return cg_her_generic(P, Q, max_iter, eps_sq, rel_prec, N, f);
-  tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? ses.refresh_clover() : ses.refresh(true);
+  const int op = dev_op_of(f, N, TMHIP_S_CG);
+  if (op < 0) return cg_her_generic(P, Q, max_iter, eps_sq, rel_prec, N, f);
+  tmhip_ctx *c = ses.refresh_for(op);
   tmhip_field *fq = in(c, Q, TMHIP_FIELD_EO), *fp = in(c, P, TMHIP_FIELD_EO);
   int iters = -1;
   CK(tmhip_cg_her(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, &iters, nullptr, 0));
@@ -898,13 +904,13 @@ int cg_her(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, 
   return iters;
 }
 
-/* solver/bicgstab_complex.c:49-116.  For the operators of bicg_op_of on an unsplit lattice the whole solve runs device-resident
- * (tmhip_bicgstab_complex); for any other f the reference's loop runs over the drop-in linalg in coherent mode (bicgstab_complex_generic). */
+/* solver/bicgstab_complex.c:49-116.  For the rows of the operator table that name BiCGstab, on an unsplit lattice, the whole solve
+ * runs device-resident (tmhip_bicgstab_complex); for any other f the reference's loop runs over the drop-in linalg in coherent mode (bicgstab_complex_generic). */
 int bicgstab_complex(spinor *const P, spinor *const Q, const int max_iter, double eps_sq, const int rel_prec, const int N, matrix_mult f) {
-  const int op = bicg_op_of(f, N);
+  const int op = dev_op_of(f, N, TMHIP_S_BICG);
   if (op < 0 || g_nproc_t > 1) return bicgstab_complex_generic(P, Q, max_iter, eps_sq, rel_prec, N, f);
-  tmhip_ctx *c = op >= TMHIP_OP_QSW_PLUS && op <= TMHIP_OP_MSW_PLUS ? ses.refresh_clover() : ses.refresh(true);
-  const int kind = op == TMHIP_OP_D_PSI ? TMHIP_FIELD_FULL : TMHIP_FIELD_EO;
+  tmhip_ctx *c = ses.refresh_for(op);
+  const int kind = op_kind(op);
   tmhip_field *fq = in(c, Q, kind), *fp = in(c, P, kind);
   int iters = -1;
   CK(tmhip_bicgstab_complex(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, &iters, nullptr, 0));
@@ -922,9 +928,9 @@ int chrono_guess(spinor *const trial, spinor *const phi, spinor **const v, int i
     return 0;
   }
   if (_n > _N) die("chrono_guess: more vectors than the list holds");
-  const int op = op_of(f);
-  if (op < 0 || V != VOLUME / 2) return chrono_guess_generic(trial, phi, v, index_array, _n, V, f);
-  tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? ses.refresh_clover() : ses.refresh(true);
+  const int op = dev_op_of(f, V, TMHIP_S_CG);
+  if (op < 0) return chrono_guess_generic(trial, phi, v, index_array, _n, V, f);
+  tmhip_ctx *c = ses.refresh_for(op);
   tmhip_field *fv[20];
   for (int i = 0; i < _n; i++) fv[i] = in(c, v[index_array[i]], TMHIP_FIELD_EO);
   tmhip_field *fphi = in(c, phi, TMHIP_FIELD_EO), *ft = out(c, trial, TMHIP_FIELD_EO);
@@ -954,19 +960,20 @@ static_assert(sizeof(tmlqcd_solver_params) == 144 && offsetof(tmlqcd_solver_para
 /* solver/cg_her_nd.c:57-160 with f = Qtm_pm_ndpsi or Qsw_pm_ndpsi, device-resident */
 int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *const Q_dn, const int max_iter, double eps_sq,
               const int rel_prec, const int N, matrix_mult_nd f) {
-  if ((f != &Qtm_pm_ndpsi && f != &Qsw_pm_ndpsi) || N != VOLUME / 2) die("cg_her_nd: only f = Qtm_pm_ndpsi / Qsw_pm_ndpsi on VOLUME/2 sites runs on the device");
+  const int op = dev_nd_op_of(f, N);
+  if (op < 0) die("cg_her_nd: only f = Qtm_pm_ndpsi / Qsw_pm_ndpsi on VOLUME/2 sites runs on the device");
   tmhip_ctx *c = ses.refresh_nd("cg_her_nd");
   tmhip_field *fqu = in(c, Q_up, TMHIP_FIELD_EO), *fqd = in(c, Q_dn, TMHIP_FIELD_EO);
   tmhip_field *fpu = in(c, P_up, TMHIP_FIELD_EO), *fpd = in(c, P_dn, TMHIP_FIELD_EO);
   int iters = -1;
-  CK(tmhip_cg_her_nd_op(c, fpu, fpd, fqu, fqd, max_iter, eps_sq, rel_prec, N, f == &Qsw_pm_ndpsi ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, &iters));
+  CK(tmhip_cg_her_nd_op(c, fpu, fpd, fqu, fqd, max_iter, eps_sq, rel_prec, N, op, &iters));
   done(c, P_up); done(c, P_dn);
   return iters;
 }
 /* solver/cg_mms_tm_nd.c:64-215 with M_ndpsi = Qtm_pm_ndpsi or Qsw_pm_ndpsi, device-resident */
 int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *sp) {
-  if ((sp->M_ndpsi != &Qtm_pm_ndpsi && sp->M_ndpsi != &Qsw_pm_ndpsi) || sp->sdim != VOLUME / 2)
-    die("cg_mms_tm_nd: only M_ndpsi = Qtm_pm_ndpsi / Qsw_pm_ndpsi on VOLUME/2 sites runs on the device");
+  const int op = dev_nd_op_of(sp->M_ndpsi, sp->sdim);
+  if (op < 0) die("cg_mms_tm_nd: only M_ndpsi = Qtm_pm_ndpsi / Qsw_pm_ndpsi on VOLUME/2 sites runs on the device");
   const int n = sp->no_shifts;
   if (n < 1 || n > 32) die("cg_mms_tm_nd: no_shifts must be in [1, 32]");
   tmhip_ctx *c = ses.refresh_nd("cg_mms_tm_nd");
@@ -974,8 +981,7 @@ int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spin
   tmhip_field *fu[32], *fd[32];
   for (int s = 0; s < n; s++) { fu[s] = out(c, Pup[s], TMHIP_FIELD_EO); fd[s] = out(c, Pdn[s], TMHIP_FIELD_EO); }
   int iters = -1;
-  CK(tmhip_cg_mms_tm_nd_op(c, fu, fd, fqu, fqd, sp->shifts, n, sp->max_iter, sp->squared_solver_prec, sp->rel_prec,
-                           sp->M_ndpsi == &Qsw_pm_ndpsi ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, &iters));
+  CK(tmhip_cg_mms_tm_nd_op(c, fu, fd, fqu, fqd, sp->shifts, n, sp->max_iter, sp->squared_solver_prec, sp->rel_prec, op, &iters));
   for (int s = 0; s < n; s++) { done(c, Pup[s]); done(c, Pdn[s]); }
   return iters;
 }
@@ -984,14 +990,11 @@ int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spin
 int cg_mms_tm(spinor **const P, spinor *const Q, tmlqcd_solver_params *sp, double *cgmms_reached_prec) {
   const int N = sp->sdim, n = sp->no_shifts, max_iter = sp->max_iter, rel_prec = sp->rel_prec;
   const double eps_sq = sp->squared_solver_prec;
-  const bool clover_full = &g_c_sw && g_c_sw > 0.;   /* Q_pm_psi with a clover term goes through Msw_full (d_psi_core): not on the device here */
-  int op = -1;
-  if ((sp->M_psi == &Qtm_pm_psi || sp->M_psi == &Qsw_pm_psi) && N == VOLUME / 2) op = sp->M_psi == &Qsw_pm_psi ? TMHIP_OP_QSW_PM : TMHIP_OP_QTM_PM;
-  else if (sp->M_psi == &Q_pm_psi && N == VOLUME && !clover_full) op = TMHIP_OP_Q_PM_FULL;
+  const int op = dev_op_of(sp->M_psi, N, TMHIP_S_MMS);
   int iters = -1;
   if (op >= 0 && g_nproc_t == 1 && n >= 1 && n <= 32 && max_iter >= 1) {
-    tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? ses.refresh_clover() : ses.refresh(true);
-    const int kind = op == TMHIP_OP_Q_PM_FULL ? TMHIP_FIELD_FULL : TMHIP_FIELD_EO;
+    tmhip_ctx *c = ses.refresh_for(op);
+    const int kind = op_kind(op);
     tmhip_field *fq = in(c, Q, kind), *fp[32];
     for (int s = 0; s < n; s++) fp[s] = out(c, P[s], kind);
     double reached = 0.0;
@@ -1007,11 +1010,11 @@ int cg_mms_tm(spinor **const P, spinor *const Q, tmlqcd_solver_params *sp, doubl
 
 int mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params, const int max_iter, double eps_sq,
                  const int rel_prec, const int N, matrix_mult f, matrix_mult32) {
-  if ((f != &Qtm_pm_psi && f != &Qsw_pm_psi) || N != VOLUME / 2) die("mixed_cg_her: only f = Qtm_pm_psi / Qsw_pm_psi on VOLUME/2 sites runs on the device");
-  const int op = f == &Qsw_pm_psi ? TMHIP_OP_QSW_PM : TMHIP_OP_QTM_PM;
+  const int op = dev_op_of(f, N, TMHIP_S_MIXED);
+  if (op < 0) die("mixed_cg_her: only f = Qtm_pm_psi / Qsw_pm_psi on VOLUME/2 sites runs on the device");
   const double innereps = &mixcg_innereps ? mixcg_innereps : 5.0e-5;           /* default_input_values.h:193 */
   const int max_inner = &mixcg_maxinnersolverit ? mixcg_maxinnersolverit : 5000; /* default_input_values.h:194 */
-  tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? ses.refresh_clover() : ses.refresh(true);
+  tmhip_ctx *c = ses.refresh_for(op);
   int iters = -1, outer = 0;
   apply(c, TMHIP_FIELD_EO, P, Q, nullptr, [&](Ctx, Fld fp, Fld fq, Fld) {
     CK(tmhip_mixed_cg_her(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, innereps, max_inner, &iters, &outer));
@@ -1022,9 +1025,9 @@ int mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params, const i
 /* solver/rg_mixed_cg_her.c:180-347 with (f, f32) = (Qtm_pm_psi, Qtm_pm_psi_32) or (Qsw_pm_psi, Qsw_pm_psi_32) */
 int rg_mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params solver_params, const int max_iter,
                     const double eps_sq, const int rel_prec, const int N, matrix_mult f, matrix_mult32) {
-  if ((f != &Qtm_pm_psi && f != &Qsw_pm_psi) || N != VOLUME / 2) die("rg_mixed_cg_her: only f = Qtm_pm_psi / Qsw_pm_psi on VOLUME/2 sites runs on the device");
-  const int op = f == &Qsw_pm_psi ? TMHIP_OP_QSW_PM : TMHIP_OP_QTM_PM;
-  tmhip_ctx *c = op == TMHIP_OP_QSW_PM ? ses.refresh_clover() : ses.refresh(true);
+  const int op = dev_op_of(f, N, TMHIP_S_MIXED);
+  if (op < 0) die("rg_mixed_cg_her: only f = Qtm_pm_psi / Qsw_pm_psi on VOLUME/2 sites runs on the device");
+  tmhip_ctx *c = ses.refresh_for(op);
   int iters = -1;
   apply(c, TMHIP_FIELD_EO, P, Q, nullptr, [&](Ctx, Fld fp, Fld fq, Fld) {
     CK(tmhip_rg_mixed_cg_her(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, solver_params.mcg_delta, &iters, nullptr, nullptr, nullptr));
@@ -1221,11 +1224,12 @@ void assign_mul_add_mul_add_mul_add_mul_r(spinor *const R, spinor *const S, spin
 }
 /* Ptilde_nd.c:102-203 with Qsq = Qtm_pm_ndpsi or Qsw_pm_ndpsi; the interval is phmc_cheb_evmin / phmc_cheb_evmax at call time */
 void Ptilde_ndpsi(spinor *R_s, spinor *R_c, double *dd, int n, spinor *S_s, spinor *S_c, matrix_mult_nd Qsq) {
-  if (Qsq != &Qtm_pm_ndpsi && Qsq != &Qsw_pm_ndpsi) die("Ptilde_ndpsi: only Qsq = Qtm_pm_ndpsi / Qsw_pm_ndpsi runs on the device");
+  const int op = dev_nd_op_of(Qsq, VOLUME / 2);
+  if (op < 0) die("Ptilde_ndpsi: only Qsq = Qtm_pm_ndpsi / Qsw_pm_ndpsi runs on the device");
   if (!&phmc_cheb_evmin || !&phmc_cheb_evmax) die("Ptilde_ndpsi: the host program has no phmc_cheb_evmin / phmc_cheb_evmax");
   const double evmin = phmc_cheb_evmin, evmax = phmc_cheb_evmax;
   apply2(ses.refresh_nd("Ptilde_ndpsi"), R_s, R_c, S_s, S_c, [&](Ctx c, Fld frs, Fld frc, Fld fss, Fld fsc) {
-    CK(tmhip_Ptilde_ndpsi(c, frs, frc, dd, n, fss, fsc, evmin, evmax, Qsq == &Qsw_pm_ndpsi ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM));
+    CK(tmhip_Ptilde_ndpsi(c, frs, frc, dd, n, fss, fsc, evmin, evmax, op));
   });
 }
 // the three bodies run with g_mubar / g_epsbar of the host (ndpoly_set_global_parameter has set them) and phmc_invmaxev = the monomial's EVMaxInv

@@ -5,6 +5,7 @@
 #define TMLQCD_DROPIN_INTERNAL_H
 #include "../../include/tmlqcd_dropin.h"
 #include "../../include/tmlqcd_hip.h"
+#include "op_table.h"
 
 #include <cstddef>
 

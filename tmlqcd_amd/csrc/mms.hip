@@ -180,8 +180,13 @@ static int mms_prepare(tmhip_ctx *ctx) {
   return 0;
 }
 
-// Q_pm_psi (tm_operators.c:380-388) on FULL fields: D_psi at -mu, gamma5, D_psi at +mu, gamma5; tmp is a FULL scratch field
-static int mms_q_pm_full(tmhip_ctx *ctx, tmhip_field *l, tmhip_field *k, tmhip_field *tmp) {
+// Q_pm_psi (tm_operators.c:380-388) on FULL fields: D_psi at -mu, gamma5, D_psi at +mu, gamma5.  Row TMHIP_OP_Q_PM_FULL of the operator
+// table; its FULL scratch field lives with the state of the only solver that takes the row.
+int tmhip_Q_pm_psi(tmhip_ctx *ctx, tmhip_field *l, tmhip_field *k) {
+  if (mms_prepare(ctx)) return 1;
+  TmhipMms *m = (TmhipMms *)ctx->mms;
+  if (!m->full_tmp && tmhip_field_alloc(ctx, TMHIP_FIELD_FULL, &m->full_tmp)) return 1;
+  tmhip_field *tmp = m->full_tmp;
   const double mu = ctx->mu;
   ctx->mu = -mu;
   const int e = tmhip_D_psi(ctx, l, k);
@@ -216,19 +221,15 @@ static bool mms_fusable(const tmhip_ctx *ctx) { return ctx->opt_cg_fused_dot && 
 static int mms_solve(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const double *shifts, int nsh, int max_iter, double eps_sq,
                      int rel_prec, int op, int *iters, double *reached) {
   TmhipMms *m = (TmhipMms *)ctx->mms;
-  const bool full = op == TMHIP_OP_Q_PM_FULL;
-  const int kind = full ? TMHIP_FIELD_FULL : TMHIP_FIELD_EO;
+  const tmhip_op_row *row = tmhip_op_row_of(op);
+  const int kind = row->kind;
+  const bool full = kind == TMHIP_FIELD_FULL;
   for (int j = 0; j < 3; j++)
     if (!m->w[kind][j] && tmhip_field_alloc(ctx, kind, &m->w[kind][j])) return 1;
   for (; m->nps[kind] < nsh - 1; m->nps[kind]++)
     if (tmhip_field_alloc(ctx, kind, &m->ps[kind][m->nps[kind]])) return 1;
   tmhip_field *r = m->w[kind][0], *p = m->w[kind][1], *ap = m->w[kind][2];
-  tmhip_field *tmp = nullptr;
-  if (full) {
-    if (!m->full_tmp && tmhip_field_alloc(ctx, TMHIP_FIELD_FULL, &m->full_tmp)) return 1;
-    tmp = m->full_tmp;
-  }
-  const bool clover = op == TMHIP_OP_QSW_PM;
+  const bool clover = row->clover != TMHIP_SW_NONE;
   const double mu = ctx->mu, nrm = 1. / (1. + mu * mu);
   const size_t gs = ctx->gs;
   if (clover && fabs(mu) > 0 && ctx->sw_inv_sets < 2) TMHIP_FAIL("cg_mms_tm: Qsw_pm_psi with mu != 0 needs both sets of sw_inv (sw_invert with the current mu)");
@@ -291,11 +292,7 @@ static int mms_solve(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const doub
           if (tmhip_launch_hopping_dot(ctx, TMHIP_OE, nullptr, s1, s0, p->d, 1., mu, &n2, 3, r->d, scal, nullptr, 1)) return 1;
         }
       } else {
-        if (full) {
-          if (mms_q_pm_full(ctx, ap, p, tmp)) return 1;
-        } else if (tmhip_apply_op(ctx, op, ap, p)) {
-          return 1;
-        }
+        if (tmhip_apply_op(ctx, op, ap, p)) return 1;
         hipLaunchKernelGGL(mms_dot_kernel, vg, dim3(256), 0, ctx->stream, (const MshiftState *)m->st, (const v2d *)p->d, (const v2d *)ap->d, ctx->ns, ctx->Vh, ppro);
         hipLaunchKernelGGL(mms_alpha_kernel, dim3(1), dim3(256), 0, ctx->stream, m->st, (const double *)ppro, nvec, (const double *)ppp, nvec);
         hipLaunchKernelGGL(mms_res_kernel, vg, dim3(256), 0, ctx->stream, (const MshiftState *)m->st, r->d, (const v2d *)ap->d, (const v2d *)p->d,
@@ -321,16 +318,14 @@ int tmhip_cg_mms_tm(tmhip_ctx *ctx, tmhip_field **P, tmhip_field *Q, const doubl
                     int rel_prec, int N, int op, int *iters, double *reached_prec) {
   if (nshifts < 1 || nshifts > MSHIFT_MAX_SHIFTS) TMHIP_FAIL("cg_mms_tm: nshifts = %d is outside [1, %d]", nshifts, MSHIFT_MAX_SHIFTS);
   if (!P || !Q || !shifts || !iters) TMHIP_FAIL("cg_mms_tm: null argument");
-  if (op != TMHIP_OP_QTM_PM && op != TMHIP_OP_QSW_PM && op != TMHIP_OP_Q_PM_FULL)
-    TMHIP_FAIL("cg_mms_tm: operator id %d is not Qtm_pm_psi, Qsw_pm_psi or Q_pm_psi", op);
-  const bool full = op == TMHIP_OP_Q_PM_FULL;
-  const int kind = full ? TMHIP_FIELD_FULL : TMHIP_FIELD_EO;
+  if (tmhip_op_check(ctx, "cg_mms_tm", TMHIP_S_MMS, op, Q->kind)) return 1;
+  const int kind = Q->kind;
+  const bool full = kind == TMHIP_FIELD_FULL;
   if (N != (full ? ctx->V : ctx->Vh)) TMHIP_FAIL("cg_mms_tm: N = %d does not match the operator (%s needs %d)", N, full ? "Q_pm_psi" : "an e/o operator", full ? ctx->V : ctx->Vh);
   if (ctx->g.nproc_t > 1 || ctx->loopback) TMHIP_FAIL("cg_mms_tm: unsplit lattices only (nproc_t = %d%s)", ctx->g.nproc_t, ctx->loopback ? ", loopback" : "");
   if (!ctx->gauge_set) TMHIP_FAIL("cg_mms_tm called before tmhip_set_gauge");
-  if (op == TMHIP_OP_QSW_PM && !ctx->clover_set) TMHIP_FAIL("cg_mms_tm: Qsw_pm_psi needs tmhip_set_clover");
   if (max_iter < 1) TMHIP_FAIL("cg_mms_tm: max_iter < 1");
-  if (Q->kind != kind || Q->prec) TMHIP_FAIL("cg_mms_tm: Q must be an fp64 %s field", full ? "FULL" : "one-parity (EO)");
+  if (Q->prec) TMHIP_FAIL("cg_mms_tm: Q must be an fp64 %s field", full ? "FULL" : "one-parity (EO)");
   for (int s = 0; s < nshifts; s++) {
     if (!P[s] || P[s]->kind != kind || P[s]->prec || P[s]->view) TMHIP_FAIL("cg_mms_tm: P[%d] must be an fp64 %s field", s, full ? "FULL" : "one-parity (EO)");
     if (P[s]->d == Q->d) TMHIP_FAIL("cg_mms_tm: a solution field is the source");

@@ -592,9 +592,7 @@ static int nd_check4(tmhip_ctx *ctx, const char *who, tmhip_field *a, tmhip_fiel
 // the clover doublet: unsplit lattices (the loopback rehearsal counts as split), 1+T resident, and -- need_inv -- sw_inv_nd valid
 static int ndsw_check4(tmhip_ctx *ctx, const char *who, bool need_inv, tmhip_field *a, tmhip_field *b, tmhip_field *c, tmhip_field *d) {
   if (ctx->g.nproc_t > 1 || ctx->loopback) TMHIP_FAIL("%s: the clover doublet runs on unsplit lattices only (nproc_t = %d%s)", who, ctx->g.nproc_t, ctx->loopback ? ", loopback" : "");
-  if (!ctx->sw_set) TMHIP_FAIL("%s called before tmhip_sw_term / tmhip_set_clover", who);
-  if (need_inv && !ctx->clover_nd_set) TMHIP_FAIL("%s: sw_inv_nd is not valid: call tmhip_sw_invert_nd on the current clover term", who);
-  return nd_check4(ctx, who, a, b, c, d);
+  return tmhip_ndsw_ready(ctx, who, need_inv) || nd_check4(ctx, who, a, b, c, d);
 }
 
 // ---------------------------------------------------------------- solver engine
@@ -759,8 +757,8 @@ int tmhip_H_eo_tm_ndpsi(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhi
 }
 
 static int nd_op_check4(tmhip_ctx *ctx, const char *who, int op, tmhip_field *a, tmhip_field *b, tmhip_field *c, tmhip_field *d) {
-  if (op != TMHIP_ND_OP_QTM_PM && op != TMHIP_ND_OP_QSW_PM) TMHIP_FAIL("%s: op = %d is neither TMHIP_ND_OP_QTM_PM nor TMHIP_ND_OP_QSW_PM", who, op);
-  return op == TMHIP_ND_OP_QSW_PM ? ndsw_check4(ctx, who, true, a, b, c, d) : nd_check4(ctx, who, a, b, c, d);
+  if (tmhip_nd_op_check(ctx, who, op)) return 1;
+  return tmhip_nd_op_row_of(op)->clover ? ndsw_check4(ctx, who, true, a, b, c, d) : nd_check4(ctx, who, a, b, c, d);
 }
 
 int tmhip_cg_her_nd_op(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_field *Q_up, tmhip_field *Q_dn, int max_iter, double eps_sq,

@@ -73,9 +73,7 @@ static bool poly_eo(const tmhip_ctx *ctx, const tmhip_field *f) { return f && f-
 static int poly_prepare(tmhip_ctx *ctx, const char *who, tmhip_field *a, tmhip_field *b, int op = TMHIP_ND_OP_QTM_PM) {
   if (ctx->g.nproc_t > 1 || ctx->loopback) TMHIP_FAIL("%s: unsplit lattices only (nproc_t = %d%s)", who, ctx->g.nproc_t, ctx->loopback ? ", loopback" : "");
   if (!ctx->gauge_set) TMHIP_FAIL("%s called before tmhip_set_gauge", who);
-  if (op != TMHIP_ND_OP_QTM_PM && op != TMHIP_ND_OP_QSW_PM) TMHIP_FAIL("%s: op = %d is neither TMHIP_ND_OP_QTM_PM nor TMHIP_ND_OP_QSW_PM", who, op);
-  if (op == TMHIP_ND_OP_QSW_PM && (!ctx->sw_set || !ctx->clover_nd_set))
-    TMHIP_FAIL("%s: sw_inv_nd is not valid: call tmhip_sw_term and tmhip_sw_invert_nd on the current links", who);
+  if (tmhip_nd_op_check(ctx, who, op)) return 1;
   if (!poly_eo(ctx, a) || !poly_eo(ctx, b)) TMHIP_FAIL("%s needs fp64 one-parity (EO) fields of this context's stride", who);
   if (a->d == b->d) TMHIP_FAIL("%s: the two flavours must be different fields", who);
   TMHIP_CHECK(hipSetDevice(ctx->device));
@@ -126,10 +124,6 @@ static int poly_comb4(tmhip_ctx *ctx, int nfl, tmhip_field *const *out, tmhip_fi
   return 0;
 }
 
-static int poly_qsq(tmhip_ctx *ctx, int op, tmhip_field *const *l, tmhip_field *const *k) {
-  return op == TMHIP_ND_OP_QSW_PM ? tmhip_Qsw_pm_ndpsi(ctx, l[0], l[1], k[0], k[1]) : tmhip_Qtm_pm_ndpsi(ctx, l[0], l[1], k[0], k[1]);
-}
-
 // Ptilde_nd.c:141-189 after the checks; R may be S, neither is one of the work fields
 static int ptilde_body(tmhip_ctx *ctx, tmhip_field *R_s, tmhip_field *R_c, const double *dd, int n, tmhip_field *S_s, tmhip_field *S_c, double evmin,
                        double evmax, int op) {
@@ -141,11 +135,11 @@ static int ptilde_body(tmhip_ctx *ctx, tmhip_field *R_s, tmhip_field *R_c, const
   for (int f = 0; f < 2; f++)
     if (tmhip_field_zero(ctx, d[f]) || tmhip_field_zero(ctx, e[f])) return 1;   // :144-147
   for (int j = n - 1; j >= 1; j--) {                                          // :154-175
-    if (poly_qsq(ctx, op, q, d)) return 1;
+    if (tmhip_apply_nd_op(ctx, op, q[0], q[1], d[0], d[1])) return 1;
     if (poly_comb4(ctx, 2, e, d, q, e, S, fact2, fact1, -1.0, dd[j])) return 1;   // the new d over the old dd
     for (int f = 0; f < 2; f++) { tmhip_field *t = d[f]; d[f] = e[f]; e[f] = t; }
   }
-  if (poly_qsq(ctx, op, q, d)) return 1;                                       // :180
+  if (tmhip_apply_nd_op(ctx, op, q[0], q[1], d[0], d[1])) return 1;            // :180
   return poly_comb4(ctx, 2, R, q, d, e, S, fact1 / 2, fact2 / 2, -1.0, dd[0] / 2);   // :182-189
 }
 

@@ -229,7 +229,7 @@ static int ndrat_force_body(tmhip_ctx *ctx, tmhip_field **chi_up, tmhip_field **
 // the clover monomial: refused before any launch unless the clover term and its doublet inverse are those of the current links
 static int ndcloverrat_prepare(tmhip_ctx *ctx, const char *who, int np) {
   if (rat_prepare(ctx, who, np)) return 1;
-  if (!ctx->sw_set || !ctx->clover_nd_set) TMHIP_FAIL("%s: sw_inv_nd is not valid: call tmhip_sw_term and tmhip_sw_invert_nd on the current links", who);
+  if (tmhip_ndsw_ready(ctx, who, true)) return 1;
   // the force ends in sw_all on the links tmhip_sw_term kept: a clover term uploaded with tmhip_set_clover has none
   if (!ctx->gauge_raw_valid) TMHIP_FAIL("%s: no lexicographic links on the device: the clover term must come from tmhip_sw_term, not tmhip_set_clover", who);
   return 0;
@@ -520,11 +520,10 @@ struct RatMu3Zero {
 // nd: both flavours (the _dn arguments are used), op: TMHIP_OP_QTM_PM / TMHIP_OP_QSW_PM, with nd TMHIP_ND_OP_QTM_PM / TMHIP_ND_OP_QSW_PM
 struct RatcorZ { bool nd; int op; const double *mu, *rmu; double A; int np, max_iter; double eps_sq; int rel_prec; };
 
+// the fields of these entry points are one-parity fields (rat_eo, in the argument checks that follow)
 static int ratcor_op_check(tmhip_ctx *ctx, const char *who, bool nd, int op, int np) {
-  const bool sw = nd ? op == TMHIP_ND_OP_QSW_PM : op == TMHIP_OP_QSW_PM;
-  if (!sw && op != (nd ? (int)TMHIP_ND_OP_QTM_PM : (int)TMHIP_OP_QTM_PM))
-    TMHIP_FAIL("%s: operator id %d is not %s", who, op, nd ? "Qtm_pm_ndpsi or Qsw_pm_ndpsi" : "Qtm_pm_psi or Qsw_pm_psi");
-  if (!sw) return rat_prepare(ctx, who, np);
+  if (nd ? tmhip_nd_op_check(ctx, who, op) : tmhip_op_check(ctx, who, TMHIP_S_RATCOR, op, TMHIP_FIELD_EO)) return 1;
+  if (!(nd ? tmhip_nd_op_row_of(op) : tmhip_op_row_of(op))->clover) return rat_prepare(ctx, who, np);
   return nd ? ndcloverrat_prepare(ctx, who, np) : cloverrat_prepare(ctx, who, np);
 }
 
@@ -540,10 +539,7 @@ static int ratcor_apply_Z(tmhip_ctx *ctx, const RatcorZ &z, tmhip_field *k_up, t
     return z.nd ? tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, q_up, q_dn, z.mu, np, z.max_iter, z.eps_sq, z.rel_prec, z.op, it)
                 : tmhip_cg_mms_tm(ctx, r->chi_up, q_up, z.mu, np, z.max_iter, z.eps_sq, z.rel_prec, N, z.op, it, nullptr);
   };
-  auto Qsq = [&]() {   // :209 / :236-237
-    if (!z.nd) return tmhip_apply_op(ctx, z.op, k_up, t_up);
-    return z.op == TMHIP_ND_OP_QSW_PM ? tmhip_Qsw_pm_ndpsi(ctx, k_up, k_dn, t_up, t_dn) : tmhip_Qtm_pm_ndpsi(ctx, k_up, k_dn, t_up, t_dn);
-  };
+  auto Qsq = [&]() { return z.nd ? tmhip_apply_nd_op(ctx, z.op, k_up, k_dn, t_up, t_dn) : tmhip_apply_op(ctx, z.op, k_up, t_up); };   // :209 / :236-237
   if (solve(l_up, l_dn, it0)) return 1;                                                       // :188 / :208
   if (ctx->opt_ratcor_fused) {
     if (tmhip_rat_sum_nd(ctx, k_up, z.nd ? k_dn : nullptr, l_up, z.nd ? l_dn : nullptr, r->chi_up, z.nd ? r->chi_dn : nullptr, z.rmu, np, 1.0)) return 1;

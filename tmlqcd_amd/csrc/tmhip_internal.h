@@ -12,6 +12,7 @@
 #include <cstring>
 #include <cmath>
 #include "../../include/tmlqcd_hip.h"
+#include "op_table.h"
 
 typedef double v2d __attribute__((ext_vector_type(2)));  // one complex double: .x = re, .y = im
 typedef float v2f __attribute__((ext_vector_type(2)));   // one complex float (mixed-precision CG)
@@ -426,7 +427,15 @@ __device__ __forceinline__ void tmhip_cdot_add(double &re, double &im, const v2d
 int tmhip_stage_reserve(tmhip_ctx *ctx, size_t bytes);
 int tmhip_field_alloc_prec(tmhip_ctx *ctx, int kind, int prec, tmhip_field **out);
 int tmhip_halo_exchange(tmhip_ctx *ctx);
-int tmhip_apply_op(tmhip_ctx *ctx, int op, tmhip_field *l, tmhip_field *k);
+// ---- the operator table (op_table.h, ops.hip) ----
+int tmhip_apply_op(tmhip_ctx *ctx, int op, tmhip_field *l, tmhip_field *k);   // l = operator `op` (any TMHIP_OP_*) of k
+int tmhip_apply_nd_op(tmhip_ctx *ctx, int op, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);   // the same for TMHIP_ND_OP_*
+// The first statement of every solver entry point, before anything is allocated, enqueued or written: refuses, naming `who`, an id
+// outside the table, a row `solver` (TMHIP_S_*) does not take, fields of another kind than the row's, a missing clover prerequisite.
+int tmhip_op_check(tmhip_ctx *ctx, const char *who, int solver, int op, int kind);
+int tmhip_nd_op_check(tmhip_ctx *ctx, const char *who, int op);
+int tmhip_ndsw_ready(tmhip_ctx *ctx, const char *who, bool need_inv);   // the clover doublet's prerequisite: 1+T resident and -- need_inv -- sw_inv_nd valid
+int tmhip_Q_pm_psi(tmhip_ctx *ctx, tmhip_field *l, tmhip_field *k);     // mms.hip: row TMHIP_OP_Q_PM_FULL, on FULL fields
 int tmhip_prepare_fp32(tmhip_ctx *ctx);
 int tmhip_exchange_gauge_halo(tmhip_ctx *ctx);   // md_update.hip: t = 0 / T-1 slices of the resident links -> the ring neighbours' halo slabs
 int tmhip_resort_gauge(tmhip_ctx *ctx);   // md_update.hip: stencil gauge copy from the device-resident lexicographic links

@@ -10,12 +10,15 @@ import numpy as np
 
 EO, OE = 0, 1
 FIELD_EO, FIELD_FULL = 0, 1
-OPS = {"Qtm_pm_psi": 0, "Qtm_plus_psi": 1, "Qtm_minus_psi": 2, "Mtm_plus_psi": 3, "Mtm_minus_psi": 4, "Qsw_pm_psi": 5}
-MMS_OPS = {"Qtm_pm_psi": 0, "Qsw_pm_psi": 5, "Q_pm_psi": 6}   # cg_mms_tm's operators (Q_pm_psi: FULL fields, TMHIP_OP_Q_PM_FULL)
-# bicgstab_complex's operators (D_psi: FULL fields, N = VOLUME; the others EO fields, N = VOLUME/2)
-BICG_OPS = {"Qtm_plus_psi": 1, "Qtm_minus_psi": 2, "Mtm_plus_psi": 3, "Mtm_minus_psi": 4, "Mtm_plus_sym_psi": 7, "Mtm_minus_sym_psi": 8,
-            "Qsw_plus_psi": 9, "Qsw_minus_psi": 10, "Msw_plus_psi": 11, "D_psi": 12}
-ND_OPS = {"Qtm_pm_ndpsi": 0, "Qsw_pm_ndpsi": 1}         # the doublet solvers' operators (TMHIP_ND_OP_*)
+# The operator ids of include/tmlqcd_hip.h by the reference's function: TMHIP_OP_* and TMHIP_ND_OP_* (tests/test_op_table.py holds
+# both maps against the header).  Which solver takes which row is the library's business (csrc/op_table.h): it refuses the others.
+ALL_OPS = {"Qtm_pm_psi": 0, "Qtm_plus_psi": 1, "Qtm_minus_psi": 2, "Mtm_plus_psi": 3, "Mtm_minus_psi": 4, "Qsw_pm_psi": 5, "Q_pm_psi": 6,
+           "Mtm_plus_sym_psi": 7, "Mtm_minus_sym_psi": 8, "Qsw_plus_psi": 9, "Qsw_minus_psi": 10, "Msw_plus_psi": 11, "D_psi": 12}
+ND_OPS = {"Qtm_pm_ndpsi": 0, "Qsw_pm_ndpsi": 1}
+# the names each wrapper below accepts (Q_pm_psi and D_psi: FULL fields, N = VOLUME; the others EO fields, N = VOLUME/2)
+OPS, MMS_OPS, BICG_OPS = ({n: ALL_OPS[n] for n in names.split()} for names in (
+    "Qtm_pm_psi Qtm_plus_psi Qtm_minus_psi Mtm_plus_psi Mtm_minus_psi Qsw_pm_psi", "Qtm_pm_psi Qsw_pm_psi Q_pm_psi",
+    "Qtm_plus_psi Qtm_minus_psi Mtm_plus_psi Mtm_minus_psi Mtm_plus_sym_psi Mtm_minus_sym_psi Qsw_plus_psi Qsw_minus_psi Msw_plus_psi D_psi"))
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 

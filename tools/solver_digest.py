@@ -8,7 +8,9 @@ Only the Python API is used, so the same file runs against any build of the libr
 bytes.  The list: cg_her over both operators, cg_fused_dot 0 / 1 / 2, cg_self 0 / 1, cg_sync 1, loopback 1 / 2 / 3, cg_batch
 1 / 4 / 7, max_iter reached before and exactly at convergence; mixed_cg_her and rg_mixed_cg_her over both operators and
 cg_fused_dot 0 / 2; cg_her_nd from a zero and a non-zero start; cg_mms_tm_nd and cg_mms_tm with 1 / 5 / 32 shifts (long enough
-to drop shifts), nd_fused 0 / 1, all three operators of cg_mms_tm in its fused and unfused forms, rel_prec -1 / 0 / 2.
+to drop shifts), nd_fused 0 / 1, all three operators of cg_mms_tm in its fused and unfused forms, rel_prec -1 / 0 / 2;
+bicgstab_complex over an e/o, a clover and the FULL operator with bicg_fused 0 / 1; chrono_guess on three vectors with csg_batch
+0 / 1; apply_Z and apply_Z_nd over both of their operators with ratcor_fused 0 / 1; Ptilde_ndpsi over both.
 """
 import argparse
 import hashlib
@@ -183,6 +185,81 @@ def mms_cases():
         lat.close()
 
 
+def bicg_cases():
+    lat = lattice((8, 8, 8, 8))
+    for op in ("Mtm_plus_sym_psi", "Qsw_plus_psi", "D_psi"):
+        full = op == "D_psi"
+        n = lat.V if full else lat.Vh
+        q, x = lat.field(random_spinor(2, n), kind=int(full)), lat.field(kind=int(full))
+        for fused in (1, 0):
+            options(lat, bicg_fused=fused)
+            name = "bicgstab_complex %s bicg_fused=%d" % (op, fused)
+
+            def solve():
+                x.zero()
+                it, hist = lat.bicgstab_complex(x, q, 1500, 1e-18, 1, n, op=op)
+                emit(name, [x], it=it, err=float(hist[-1]))
+            attempt(name, solve)
+    options(lat, bicg_fused=1)
+    lat.close()
+
+
+def chrono_cases():
+    lat = lattice((8, 8, 8, 8))
+    phi = lat.field(random_spinor(2, lat.Vh))
+    for op in OPS:
+        for batch in (1, 0):
+            options(lat, csg_batch=batch)
+            vs, trial = [lat.field() for _ in range(3)], lat.field()
+            for k, v in enumerate(vs):
+                lat.chrono_add_solution(v, lat.field(random_spinor(10 + k, lat.Vh)))
+            name = "chrono_guess %s n=3 csg_batch=%d" % (op[:3], batch)
+
+            def guess():
+                G, bn = lat.chrono_guess(trial, phi, vs, op=op)
+                emit(name, [trial] + vs, G=hashlib.sha256(G.tobytes()).hexdigest()[:16], b=hashlib.sha256(bn.tobytes()).hexdigest()[:16])
+            attempt(name, guess)
+    options(lat, csg_batch=1)
+    lat.close()
+
+
+def ratcor_poly_cases():
+    mu, rmu, A = [0.1, 0.3, 0.9], [0.2, 0.5, 0.1], 1.05
+    coefs = [1.0, -0.6, 0.35, -0.2, 0.1, -0.05, 0.02, -0.01]
+    lat = lattice((8, 8, 8, 8))
+    lat.set_mu(0.0)                      # the correction monomials' clover operator wants the inverse of sw_invert(EE, 0.)
+    lat.sw_invert(0, 0.0)
+    lat.set_nd(0.1, 0.05, 0.8)
+    lat.sw_invert_nd(0.1 * 0.1 - 0.05 * 0.05)
+    l = [lat.field(random_spinor(2, lat.Vh)), lat.field(random_spinor(3, lat.Vh))]
+    k = [lat.field(), lat.field()]
+    for fused in (1, 0):
+        options(lat, ratcor_fused=fused)
+        for op in OPS:
+            name = "apply_Z %s ratcor_fused=%d" % (op[:3], fused)
+
+            def single():
+                delta, it = lat.apply_Z(k[0], l[0], mu, rmu, A, 1500, 1e-18, 1, op=op)
+                emit(name, k[:1], it=it, delta=delta)
+            attempt(name, single)
+        for op in ("Qtm_pm_ndpsi", "Qsw_pm_ndpsi"):
+            name = "apply_Z_nd %s ratcor_fused=%d" % (op[:3], fused)
+
+            def doublet():
+                delta, it = lat.apply_Z_nd(k, l, mu, rmu, A, 1500, 1e-18, 1, op=op)
+                emit(name, k, it=it, delta=delta)
+            attempt(name, doublet)
+    options(lat, ratcor_fused=1)
+    for op in ("Qtm_pm_ndpsi", "Qsw_pm_ndpsi"):
+        name = "Ptilde_ndpsi %s" % op[:3]
+
+        def ptilde():
+            lat.Ptilde_ndpsi(k[0], k[1], coefs, l[0], l[1], 0.01, 1.0, op=op)
+            emit(name, k)
+        attempt(name, ptilde)
+    lat.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
@@ -191,6 +268,9 @@ def main():
     mixed_cases()
     nd_cases()
     mms_cases()
+    bicg_cases()
+    chrono_cases()
+    ratcor_poly_cases()
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")
