@@ -530,6 +530,22 @@ extern paramsGaugeInfo GaugeInfo;                                               
 /* reads gauge_precision_read_flag and g_disable_IO_checks at call time (both optional: weak references, defaults 64 / checks on) */
 int read_gauge_field(char *filename, su3 **const gf);                            /* io/gauge.h, io/gauge_read.c:28 */
 int write_gauge_field(char *filename, const int prec, paramsXlfInfo const *xlfInfo);   /* io/gauge_write.c:22 */
+/* ---- propagators and sources: read_spinor replaces the function of that name in io/spinor_read.o, which stays in libio.a with the
+ *      symbol localized (the object also defines PropInfo and SourceInfo) -- */
+/* io/spinor.h, io/spinor_read.c:27: return values, messages and prints of the reference; r == NULL: s is a lexicographic field.  Reads
+ * g_disable_src_IO_checks, g_debug_level and g_cart_id at call time (all optional: weak references, defaults 0, 1, 0).  The fields
+ * follow the residency mode like any other output. */
+int read_spinor(spinor *const s, spinor *const r, char *filename, const int position);
+/* write_spinor(writer, s, r, flavours, prec) of io/spinor_write.c:23 on a file name instead of a c-lime WRITER: per flavour the
+ * "scidac-binary-data" header, the record packed on the device and the "scidac-checksum" message are appended to (append != 0) or
+ * start (append == 0) the file; r == NULL: lexicographic fields; at most 8 flavours.  tmlqcd_hip_write_lime_message writes one of
+ * the message records around them with the caller's text.  Both return 0 or -1. */
+int tmlqcd_hip_write_spinor(char *filename, const int append, spinor **const s, spinor **const r, const int flavours, const int prec);
+int tmlqcd_hip_write_lime_message(char *filename, const int append, const char *type, const char *text, const int mb, const int me);
+/* source_spinor_field (start.c:707) and source_spinor_field_point_from_file (start.c:743) on the device mirrors of P and Q; not under
+ * their reference names: start.o holds the random number generator and stays on the link line */
+void tmlqcd_hip_source_spinor_field(spinor *const P, spinor *const Q, int is, int ic);
+void tmlqcd_hip_source_spinor_field_point_from_file(spinor *const P, spinor *const Q, int is, int ic, int source_indx);
 /* benchmark.c:291-300 on device-resident mirrors; returns seconds for `iters` x {H(0,f1,f0); H(1,f2,f1)} */
 double tmlqcd_hip_benchmark_loop(spinor *f0, spinor *f1, spinor *f2, int iters);
 

@@ -77,6 +77,9 @@ int tmhip_field_download_range(tmhip_ctx *ctx, tmhip_field *f, void *pinned_spin
 int tmhip_pinned_alloc(unsigned long bytes, void **out);
 int tmhip_pinned_free(void *p);
 int tmhip_field_zero(tmhip_ctx *ctx, tmhip_field *f);
+/* the planes of an fp64 one-parity field as they lie in HBM, d[12][*stride] complex doubles with the padding entries
+ * [VOLUME/2, *stride): host -> device (to_device != 0) or device -> host; host == NULL only reports the stride (diagnostics, tests) */
+int tmhip_field_raw(tmhip_ctx *ctx, tmhip_field *f, void *host, int to_device, int *stride);
 /* FULL field <-> its two parities (linalg/convert_eo_to_lexic.c) -- views, no copy */
 tmhip_field *tmhip_field_even(tmhip_field *full);
 tmhip_field *tmhip_field_odd(tmhip_field *full);
@@ -690,6 +693,48 @@ int tmhip_gauge_pack_ildg(tmhip_ctx *ctx, void *file_bytes, int prec, unsigned *
 int tmhip_read_gauge_field(tmhip_ctx *ctx, const char *filename, int prec_expected, int io_checks, void *host_gauge, tmhip_gauge_info *info);
 int tmhip_write_gauge_field(tmhip_ctx *ctx, const char *filename, int prec, const char *xlf_info, unsigned *sums);
 
+/* ---- propagators and sources (io/spinor_read.c, io/spinor_write.c, io/spinor_read_binary.c, io/spinor_write_binary.c, start.c).  The
+ *      "scidac-binary-data" record travels to / from the device as it lies in the file; parity selection, the x <-> z transposition
+ *      between the e/o fields and the file's site order, byte swap, 32 <-> 64 bit conversion and the SciDAC checksum happen in HBM
+ *      (spinor_io.hip). -- */
+/* io/spinor_write_binary.c:145-224 (write_binary_spinor_data) and io/spinor_read_binary.c (read_binary_spinor_data) with
+ * io/dml.c:49-60: this rank's contiguous part of the record (host pointer; T LZ LY LX sites, x fastest; per site the 24 reals of
+ * `spinor`, su3.h:60-63, big-endian; prec 64 | 32 with the (float) cast / exact widening of io/utils.h) from / into two fp64 EO
+ * fields: file site (t, x, y, z) is entry g_lexic2eosub[g_ipt[t][x][y][z]] of `even` if (t_global + x + y + z) % 2 == 0, else of
+ * `odd`.  sums[2] = SciDAC checksum A, B of this rank's sites with rank = proc_t T LZ LY LX + site number (XOR over the ranks of a
+ * T split = the file's, io/dml.c:63-66).  Entries [VOLUME/2, stride) of the planes are not written.  The `_l` forms of the
+ * reference (write_binary_spinor_data_l / read_binary_spinor_data_l: one lexicographic field) are these same calls on a FULL field
+ * passed as tmhip_field_even(full), tmhip_field_odd(full). */
+int tmhip_spinor_pack(tmhip_ctx *ctx, tmhip_field *even, tmhip_field *odd, void *file_bytes, int prec, unsigned *sums);
+int tmhip_spinor_unpack(tmhip_ctx *ctx, tmhip_field *even, tmhip_field *odd, const void *file_bytes, int prec, unsigned *sums);
+typedef struct {
+  int prec;                             /* 64 | 32, from the length of the record (spinor_read.c:83-95) */
+  int prop_type;                        /* parse_propagator_type after the switch of spinor_read.c:40-55: 0, 1 or 10 */
+  int position;                         /* the "scidac-binary-data" record that was read (2 position + 1 for Source_Sink_Pairs) */
+  int checksum_read;                    /* a "scidac-checksum" record followed and parsed (always 0 with io_checks = 0) */
+  unsigned suma, sumb;                  /* calculated over the record */
+  unsigned suma_stored, sumb_stored;    /* as stored in the file */
+} tmhip_spinor_info;
+/* io/spinor_read.c:27-150 read_spinor(s, r, filename, position) with io/utils_parse_propagator_type.c:22-91, unsplit lattices only
+ * (fails with a message on a T-split context).  Returns 0, or with the reference's messages on stderr: -2 / -3 propagator / source
+ * types that are not supported, -5 no such "scidac-binary-data" record, -6 a record of the wrong length, -1 no "scidac-checksum"
+ * record behind the data (io_checks = g_disable_src_IO_checks != 1), -7 the data could not be read; 1 for errors the reference does
+ * not return from (no such file, no device memory).  Calculated and stored checksum are NOT compared, as in the reference, which
+ * only prints them: both are in `info` (may be NULL).  Unlike the reference, -1 is found before the data are touched: a refused
+ * file leaves the fields as they were. */
+int tmhip_read_spinor(tmhip_ctx *ctx, tmhip_field *even, tmhip_field *odd, const char *filename, int position, int io_checks, tmhip_spinor_info *info);
+/* io/spinor_write.c:23-47 write_spinor(writer, s, r, flavours, prec): per flavour a "scidac-binary-data" header (MB 1, ME 0), the record
+ * packed on the device, and the "scidac-checksum" message (0, 1; io/utils_write_checksum.c:30-44).  append = 0 creates the file,
+ * 1 adds to it.  sums (may be NULL): 2 words per flavour.  Unsplit lattices only. */
+int tmhip_write_spinor(tmhip_ctx *ctx, const char *filename, int append, tmhip_field *const *even, tmhip_field *const *odd, int flavours, int prec, unsigned *sums);
+/* write_header + write_message + close_writer_record (io/utils.h) for the records around the data ("propagator-type", "inversion-info",
+ * "etmc-propagator-format", "source-type", "etmc-source-format"): the text is the caller's, as with "xlf-info" on the gauge side */
+int tmhip_write_lime_message(const char *filename, int append, const char *type, const char *text, int mb, int me);
+/* start.c:707-741 source_spinor_field(P, Q, is, ic) (global_site 0) and start.c:743-830 source_spinor_field_point_from_file(P, Q, is, ic,
+ * source_indx): both fields zero, component (is, ic) = 1.0 at the site whose GLOBAL index is global_site = ((t LX + x) LY + y) LZ + z --
+ * z fastest --, on the rank and in the field (even: P, odd: Q) that own it */
+int tmhip_source_point(tmhip_ctx *ctx, tmhip_field *even, tmhip_field *odd, int is, int ic, long long global_site);
+
 /* ---- multi-GPU halo exchange (replaces xchange_field / xchange_halffield,
  *      xchange/xchange_field.c:269-470, xchange/xchange_halffield.c:176-263) -- */
 #define TMHIP_UNIQUE_ID_BYTES 128
@@ -744,6 +789,10 @@ int tmhip_multi_hopping_matrix(int n, tmhip_ctx **ctxs, int ieo, tmhip_field **l
 /* The benchmark.c:291-300 loop on device-resident fields: iters x {H(0,f1,f0); H(1,f2,f1)},
  * timed with HIP events on the context's stream.  ms_total = elapsed milliseconds. */
 int tmhip_bench_hopping(tmhip_ctx *ctx, tmhip_field *f0, tmhip_field *f1, tmhip_field *f2, int iters, double *ms_total);
+/* `reps` launches of the spinor record's pack (pack != 0) or unpack kernel alone, timed with HIP events: no host copy, no checksum
+ * fetch.  The record is the one a first pack of (even, odd) leaves in the staging buffer; an unpack rewrites the fields with their
+ * own values (at 32 bit: rounded). */
+int tmhip_bench_spinor_io(tmhip_ctx *ctx, tmhip_field *even, tmhip_field *odd, int prec, int pack, int reps, double *ms_total);
 /* generic event slots (0..15) recorded on the context's compute stream */
 int tmhip_event_record(tmhip_ctx *ctx, int slot);
 int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double *ms);

@@ -465,6 +465,20 @@ int tmhip_field_download(tmhip_ctx *ctx, tmhip_field *f, void *host, int nsites)
   return tmhip_check_async_error(ctx);
 }
 
+/* The planes of an fp64 one-parity field as they lie in HBM, d[12][stride] complex doubles, padding entries [VOLUME/2, stride)
+ * included: host -> device (to_device != 0) or device -> host; host == NULL only reports the stride.  For diagnostics and tests
+ * (what a kernel left in the padding cannot be seen through tmhip_field_download). */
+int tmhip_field_raw(tmhip_ctx *ctx, tmhip_field *f, void *host, int to_device, int *stride) {
+  if (!f || f->kind != TMHIP_FIELD_EO || f->prec != 0) TMHIP_FAIL("tmhip_field_raw: needs an fp64 one-parity field");
+  if (stride) *stride = f->ns;
+  if (!host) return 0;
+  const size_t bytes = (size_t)12 * f->ns * sizeof(v2d);
+  if (to_device) TMHIP_CHECK(hipMemcpyAsync(f->d, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  else TMHIP_CHECK(hipMemcpyAsync(host, f->d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 /* page-locked host memory for callers that must keep the runtime away from their own pages (the drop-in's lazy mode: user arrays
  * whose protection changes must never be registered with the driver) */
 int tmhip_pinned_alloc(unsigned long bytes, void **out) {

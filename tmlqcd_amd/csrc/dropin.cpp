@@ -39,6 +39,9 @@ void update_backward_gauge(su3 **const gf) __attribute__((weak));
 // ILDG I/O (io/gauge_read.c, io/gauge_write.c): the reader's precision switch and the IO-check switch are owned by the input parser
 extern int gauge_precision_read_flag __attribute__((weak));       /* read_input.l; default 64 */
 extern int g_disable_IO_checks __attribute__((weak));             /* global.h:74 */
+extern int g_disable_src_IO_checks __attribute__((weak));         /* global.h:74; read_spinor; default 0 */
+extern int g_debug_level __attribute__((weak));                   /* global.h:70; read_spinor's prints; default 1 (default_input_values.h:115) */
+extern int g_cart_id __attribute__((weak));                       /* global.h:206; default 0 */
 extern int T_global __attribute__((weak));                        /* global.h:82 */
 extern int L __attribute__((weak));                               /* global.h:82 */
 // Q_pm_psi_prec: the preconditioner and its globals
@@ -1611,6 +1614,81 @@ int write_gauge_field(char *filename, const int prec, paramsXlfInfo const *xlfIn
   }
   unsigned cs[2];
   return tmhip_write_gauge_field(c, filename, prec, msg[0] ? msg : nullptr, cs) ? -1 : 0;
+}
+
+// ------------------------------------------------------------------ propagators and sources
+/* The e/o pair (s, r) or -- r == NULL -- the lexicographic field s as the two one-parity device fields the core calls take */
+static void spinor_pair(tmhip_ctx *c, spinor *s, spinor *r, bool reading, tmhip_field **fe, tmhip_field **fo) {
+  if (r) {
+    *fe = reading ? in(c, s, TMHIP_FIELD_EO) : out(c, s, TMHIP_FIELD_EO);
+    *fo = reading ? in(c, r, TMHIP_FIELD_EO) : out(c, r, TMHIP_FIELD_EO);
+  } else {
+    tmhip_field *f = reading ? in(c, s, TMHIP_FIELD_FULL) : out(c, s, TMHIP_FIELD_FULL);
+    *fe = tmhip_field_even(f); *fo = tmhip_field_odd(f);
+  }
+}
+
+/* io/spinor_read.c:27-150 read_spinor(s, r, filename, position): the LIME records are walked on the host, the record goes through
+ * page-locked memory to the device and is unpacked and check-summed there; (s, r) follow the residency mode like any other output.
+ * r == NULL: s is a lexicographic field of VOLUME sites (read_binary_spinor_data_l).  Return values, messages and prints are the
+ * reference's; a file that is refused leaves s and r as they were. */
+int read_spinor(spinor *const s, spinor *const r, char *filename, const int position) {
+  if (g_nproc_t > 1) die("read_spinor: single-rank reader (T-split ranks: tmhip_spinor_unpack for their part of the record)");
+  tmhip_ctx *c = ctx();
+  ses.calls++;
+  tmhip_field *fe, *fo;
+  spinor_pair(c, s, r, false, &fe, &fo);
+  tmhip_spinor_info info;
+  const int checks = !(&g_disable_src_IO_checks && g_disable_src_IO_checks == 1);
+  const bool talk = (&g_cart_id ? g_cart_id : 0) == 0 && (&g_debug_level ? g_debug_level : 1) >= 0;
+  const int rc = tmhip_read_spinor(c, fe, fo, filename, position, checks, &info);
+  if (rc > 0) die("tmhip_read_spinor");
+  if (talk && info.prec) printf("# %s precision read (%d bits).\n", info.prec == 64 ? "Double" : "Single", info.prec);   /* spinor_read.c:97-99: before the data */
+  if (rc < 0) return rc;
+  done(c, s);
+  if (r) done(c, r);
+  if (talk) {
+    if (checks) {
+      printf("# Scidac checksums for DiracFermion field %s position %d:\n", filename, info.position);
+      printf("#   Calculated            : A = %#010x B = %#010x.\n", info.suma, info.sumb);
+      printf("#   Read from LIME headers: A = %#010x B = %#010x.\n", info.suma_stored, info.sumb_stored);
+    }
+  }
+  return 0;
+}
+
+/* What write_spinor (io/spinor_write.c:23-47) puts on a writer, on a file name: the reference's function takes a c-lime WRITER and
+ * cannot be replaced under its own name.  A host array whose device mirror is current is packed where it lies; any other is
+ * uploaded first.  r == NULL: s[i] are lexicographic fields.  Returns 0, or -1 after a message. */
+int tmlqcd_hip_write_spinor(char *filename, const int append, spinor **const s, spinor **const r, const int flavours, const int prec) {
+  if (g_nproc_t > 1) die("tmlqcd_hip_write_spinor: single-rank writer (T-split ranks: tmhip_spinor_pack for their part of the record)");
+  if (flavours < 1 || flavours > 8) die("tmlqcd_hip_write_spinor: 1 to 8 flavours");
+  tmhip_ctx *c = ctx();
+  ses.calls++;
+  tmhip_field *fe[8], *fo[8];
+  for (int i = 0; i < flavours; i++) spinor_pair(c, s[i], r ? r[i] : nullptr, true, &fe[i], &fo[i]);
+  return tmhip_write_spinor(c, filename, append, fe, fo, flavours, prec, nullptr) ? -1 : 0;
+}
+int tmlqcd_hip_write_lime_message(char *filename, const int append, const char *type, const char *text, const int mb, const int me) {
+  return tmhip_write_lime_message(filename, append, type, text, mb, me) ? -1 : 0;
+}
+
+/* start.c:707-741 and start.c:743-830 on the device mirrors of P and Q (start.o keeps the random number generator and stays on the
+ * link line, so these carry names of their own) */
+void tmlqcd_hip_source_spinor_field_point_from_file(spinor *const P, spinor *const Q, int is, int ic, int source_indx) {
+  tmhip_ctx *c = ctx();
+  ses.calls++;
+  const long long Vg = (long long)VOLUME * (g_nproc_t < 1 ? 1 : g_nproc_t);
+  if (source_indx < 0 || source_indx >= Vg) {     /* start.c:755-759 */
+    printf("Error in the input parameter file, SourceLocation must be in [0,VOLUME-1]! Exiting...!\n");
+    exit(1);
+  }
+  tmhip_field *fp = out(c, P, TMHIP_FIELD_EO), *fq = out(c, Q, TMHIP_FIELD_EO);
+  CK(tmhip_source_point(c, fp, fq, is, ic, source_indx));
+  done(c, P); done(c, Q);
+}
+void tmlqcd_hip_source_spinor_field(spinor *const P, spinor *const Q, int is, int ic) {
+  tmlqcd_hip_source_spinor_field_point_from_file(P, Q, is, ic, 0);
 }
 
 // ------------------------------------------------------------------ benchmark helper

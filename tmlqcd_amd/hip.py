@@ -39,6 +39,12 @@ class GaugeInfo(C.Structure):
                 ("xlf_info", C.c_char * 1024), ("ildg_data_lfn", C.c_char * 512)]
 
 
+class SpinorInfo(C.Structure):
+    """tmhip_spinor_info (include/tmlqcd_hip.h): what read_spinor found -- precision, propagator type, the record read, both checksums."""
+    _fields_ = [("prec", C.c_int), ("prop_type", C.c_int), ("position", C.c_int), ("checksum_read", C.c_int),
+                ("suma", C.c_uint), ("sumb", C.c_uint), ("suma_stored", C.c_uint), ("sumb_stored", C.c_uint)]
+
+
 class _Geom(C.Structure):
     _fields_ = [("T", C.c_int), ("LX", C.c_int), ("LY", C.c_int), ("LZ", C.c_int),
                 ("nproc_t", C.c_int), ("proc_t", C.c_int)]
@@ -67,6 +73,7 @@ def load_library():
         "tmhip_field_upload": [vp, vp, vp, i],
         "tmhip_field_download": [vp, vp, vp, i],
         "tmhip_field_zero": [vp, vp],
+        "tmhip_field_raw": [vp, vp, vp, i, C.POINTER(i)],
         "tmhip_hopping_matrix": [vp, i, vp, vp],
         "tmhip_hopping_matrix_nocom": [vp, i, vp, vp],
         "tmhip_tm_times_hopping_matrix": [vp, i, vp, vp, d, d],
@@ -123,6 +130,12 @@ def load_library():
         "tmhip_gauge_unpack_ildg": [vp, vp, i, C.POINTER(C.c_uint)], "tmhip_gauge_pack_ildg": [vp, vp, i, C.POINTER(C.c_uint)],
         "tmhip_read_gauge_field": [vp, C.c_char_p, i, i, vp, C.POINTER(GaugeInfo)],
         "tmhip_write_gauge_field": [vp, C.c_char_p, i, C.c_char_p, C.POINTER(C.c_uint)],
+        "tmhip_spinor_pack": [vp, vp, vp, vp, i, C.POINTER(C.c_uint)], "tmhip_spinor_unpack": [vp, vp, vp, vp, i, C.POINTER(C.c_uint)],
+        "tmhip_read_spinor": [vp, vp, vp, C.c_char_p, i, i, C.POINTER(SpinorInfo)],
+        "tmhip_write_spinor": [vp, C.c_char_p, i, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(C.c_uint)],
+        "tmhip_write_lime_message": [C.c_char_p, i, C.c_char_p, C.c_char_p, i, i],
+        "tmhip_source_point": [vp, vp, vp, i, i, C.c_longlong],
+        "tmhip_bench_spinor_io": [vp, vp, vp, i, i, i, pd],
         "tmhip_gauge_su3_deviation": [vp, pd],
         "tmhip_gauge_pack_stats": [vp, C.POINTER(C.c_longlong)], "tmhip_gauge_pack_build_ms": [vp, pd],
         "tmhip_gauge_pack_launches": [vp, C.POINTER(C.c_longlong)],
@@ -280,6 +293,13 @@ def csg_solve(G, b):
     return b
 
 
+def write_lime_message(filename, record_type, text, mb, me, append=True):
+    """One message record of a LIME file (tmhip_write_lime_message): the "propagator-type", "inversion-info", ... records around the
+    data of a propagator file; the text is the caller's."""
+    _ck(load_library().tmhip_write_lime_message(str(filename).encode(), 1 if append else 0, record_type.encode(), text.encode(), mb, me),
+        "tmhip_write_lime_message")
+
+
 class Field:
     """A device-resident spinor field (opaque handle); prec 32 = the reference's spinor32."""
 
@@ -324,6 +344,20 @@ class Field:
     def zero(self):
         _ck(self.lat.lib.tmhip_field_zero(self.lat.h, self.h), "tmhip_field_zero")
         return self
+
+    def raw(self, planes=None):
+        """The planes of an fp64 one-parity field as they lie in HBM, float64 [12][stride][2] with the padding entries [Vh, stride):
+        returned, or -- `planes` given -- written to the device."""
+        ns = C.c_int()
+        _ck(self.lat.lib.tmhip_field_raw(self.lat.h, self.h, None, 0, C.byref(ns)), "tmhip_field_raw")
+        if planes is not None:
+            if planes.shape != (12, ns.value, 2):
+                raise TmHipError("raw(planes): needs a float64 [12][%d][2] array" % ns.value)
+            _ck(self.lat.lib.tmhip_field_raw(self.lat.h, self.h, _hp(planes), 1, None), "tmhip_field_raw")
+            return self
+        out = np.empty((12, ns.value, 2))
+        _ck(self.lat.lib.tmhip_field_raw(self.lat.h, self.h, _hp(out), 0, None), "tmhip_field_raw")
+        return out
 
     def even(self):
         return Field(self.lat, FIELD_EO, C.c_void_p(self.lat.lib.tmhip_field_even(self.h)), owner=False)
@@ -716,6 +750,61 @@ class Lattice:
         sums = (C.c_uint * 2)()
         _ck(self.lib.tmhip_write_gauge_field(self.h, str(filename).encode(), prec, xlf_info.encode() if xlf_info else None, sums), "tmhip_write_gauge_field")
         return int(sums[0]), int(sums[1])
+
+    # ---- propagators and sources (io/spinor_read.c, io/spinor_write.c, start.c; spinor_io.hip)
+    def spinor_pack(self, even, odd, prec, out=None):
+        """Two fp64 EO fields (or the two views of a FULL field) as the bytes of this rank's part of a "scidac-binary-data" record;
+        returns (uint8 array, (suma, sumb)).  `out`: a contiguous uint8 buffer of the record's size to fill."""
+        n = self.V * (192 if prec == 64 else 96)
+        if out is None:
+            out = np.zeros(n, dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.size != n or not out.flags["C_CONTIGUOUS"]:
+            raise TmHipError("spinor_pack: out must be a contiguous uint8 array of %d bytes" % n)
+        sums = (C.c_uint * 2)()
+        _ck(self.lib.tmhip_spinor_pack(self.h, even.h, odd.h, out.ctypes.data_as(C.c_void_p), prec, sums), "tmhip_spinor_pack")
+        return out, (int(sums[0]), int(sums[1]))
+
+    def spinor_unpack(self, even, odd, file_bytes, prec):
+        """This rank's part of a "scidac-binary-data" record (bytes / uint8 array) -> the two fields; returns (suma, sumb)."""
+        buf = np.frombuffer(file_bytes, dtype=np.uint8) if not isinstance(file_bytes, np.ndarray) else file_bytes
+        want = self.V * (192 if prec == 64 else 96)
+        if buf.size != want:
+            raise TmHipError("spinor_unpack: %d bytes, expected %d" % (buf.size, want))
+        buf = np.ascontiguousarray(buf)
+        sums = (C.c_uint * 2)()
+        _ck(self.lib.tmhip_spinor_unpack(self.h, even.h, odd.h, buf.ctypes.data_as(C.c_void_p), prec, sums), "tmhip_spinor_unpack")
+        return int(sums[0]), int(sums[1])
+
+    def read_spinor(self, even, odd, filename, position=0, io_checks=True):
+        """read_spinor(s, r, filename, position) (io/spinor_read.c:27): returns (status 0 | -1 | -2 | -3 | -5 | -6 | -7, SpinorInfo)."""
+        info = SpinorInfo()
+        rc = self.lib.tmhip_read_spinor(self.h, even.h, odd.h, str(filename).encode(), position, 1 if io_checks else 0, C.byref(info))
+        if rc > 0:
+            raise TmHipError("tmhip_read_spinor failed (rc=%d)" % rc)
+        return rc, info
+
+    def write_spinor(self, filename, even, odd, prec=64, append=False):
+        """write_spinor(writer, s, r, flavours, prec) (io/spinor_write.c:23): `even`, `odd` a field each or equally long lists of
+        them (one entry per flavour); returns the list of (suma, sumb), one per flavour."""
+        ev = list(even) if isinstance(even, (list, tuple)) else [even]
+        od = list(odd) if isinstance(odd, (list, tuple)) else [odd]
+        if len(ev) != len(od) or not ev:
+            raise TmHipError("write_spinor: as many even as odd fields, at least one")
+        n = len(ev)
+        sums = (C.c_uint * (2 * n))()
+        _ck(self.lib.tmhip_write_spinor(self.h, str(filename).encode(), 1 if append else 0, (C.c_void_p * n)(*[f.h.value for f in ev]),
+                                        (C.c_void_p * n)(*[f.h.value for f in od]), n, prec, sums), "tmhip_write_spinor")
+        return [(int(sums[2 * k]), int(sums[2 * k + 1])) for k in range(n)]
+
+    def bench_spinor_io(self, even, odd, prec, pack, reps):
+        """Milliseconds of `reps` launches of the pack / unpack kernel alone (HIP events)."""
+        ms = C.c_double()
+        _ck(self.lib.tmhip_bench_spinor_io(self.h, even.h, odd.h, prec, 1 if pack else 0, reps, C.byref(ms)), "tmhip_bench_spinor_io")
+        return ms.value
+
+    def source_point(self, even, odd, is_, ic, global_site=0):
+        """source_spinor_field (start.c:707, site 0) / source_spinor_field_point_from_file (start.c:743) on the device."""
+        _ck(self.lib.tmhip_source_point(self.h, even.h, odd.h, is_, ic, global_site), "tmhip_source_point")
 
     def sw_invert(self, ieo, mu):
         """operator/clover_invert.c:170 on the device (needs sw_term or set_clover first)."""

@@ -80,6 +80,8 @@ RULES = [
     (r"^(void )?bicghip::(dot_kernel<(true|false)>|sub_kernel|update_kernel|dir_kernel)", "fused BiCGstab", 8),
     # the four-term combination of the polynomial monomial (poly.hip), both flavours of a doublet per launch: a stream like the ones above
     (r"^(void )?polyhip::comb4_kernel", "four-term combination", 8),
+    # propagator / source records (spinor_io.hip): byte work through an LDS tile, a handful of registers; "no scratch" is the floor
+    (r"^void spinor_io_kernel<[24], (true|false)>", "spinor record pack / unpack", 1),
 ]
 
 
