@@ -873,9 +873,9 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  * updated links leave SU(3) by 1e-7 after two steps with |step P| = 2.5 and by 1e-13 after some hundred ordinary ones.
  * The measurement is one launch and one synchronisation per such call; with the default 18-real read nothing is added.
  * "gauge_pack" -1 (automatic, default) | 0 | 1 changes what is read but never a result: the staged 256-thread fp64 stencil with a
- * twisted-mass epilogue on an unsplit lattice reads a packed twin of the gauge copy -- two rows of every link, the fp32 residual of the
- * third row against its rebuild conj(row_a x row_b), and one byte that says which cyclic rotation of the rows was stored: 121 bytes
- * instead of 144.  The twin is built on the context's stream by the first such launch after the links changed (one kernel, a 12-byte copy
+ * twisted-mass epilogue on an unsplit lattice reads a packed twin of the gauge copy -- two rows of every link and a 16-byte tail: the distance of the
+ * third row from its rebuild conj(row_a x row_b) as six 21-bit offsets in ulps, and two bits that say which cyclic rotation of the rows
+ * was stored: 112 bytes instead of 144.  The twin is built on the context's stream by the first such launch after the links changed (one kernel, a 12-byte copy
  * and one synchronisation per change of the links) and every link is verified there bit for bit with the stencil's own rebuild
  * function; a field in which some link has no exact rotation is read in full, silently.  0: never; 1: as automatic.  "gauge_recon" 12 takes
  * precedence.  "gauge_pack_rot" -1 (default: the first rotation that verifies) | 0 | 1 | 2 (try that rotation first; for tests). */

@@ -126,8 +126,8 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
                                         const unsigned char *lds = nullptr, int jl = 0, const TmhipGaugePack &pk = TmhipGaugePack{}) {
   (void)j2; (void)pk;
   V2T pa[3], pb[3];
-  V2T ra[3], rb[3], rc[3]; v4f r4 = {}; v2f r2 = {}; int rot = 0;   // GAUX 15: the two stored rows, the rebuilt one, its residual, the selector
-  (void)ra; (void)rb; (void)rc; (void)r4; (void)r2; (void)rot;
+  V2T ra[3], rb[3], rc[3]; v4u tl = {};   // GAUX 15: the two stored rows, the rebuilt one, the tail (its offsets and the rotation)
+  (void)ra; (void)rb; (void)rc; (void)tl;
   static_assert(GAUX != 15 || !HALO, "the packed link read has no boundary form");
   if (HALO) {
     V2T h[6];
@@ -149,7 +149,7 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
       ld6<false>(s, in, (size_t)ns, j, 0); ld6<false>(s + 6, in, (size_t)ns, j, 1);
     }
     if constexpr (GAUX == 15) {
-      // Packed link read: the link's eleven loads are requested right behind the spinor's, and the spinor is projected (48 -> 24
+      // Packed link read: the link's seven loads are requested right behind the spinor's, and the spinor is projected (48 -> 24
       // registers) while they are in flight; the rebuild and the selects below then have the room they need.  Left to itself
       // the compiler asks for the link first and rebuilds it with the whole neighbour spinor outstanding: 176 registers for EPI_TM_SUB_G5
       // when the instance is compiled with __launch_bounds__(256, 1) (tools/micro/regprobe.hip), scratch under the bound of three waves.
@@ -162,12 +162,8 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
         ra[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)e * ugs + ui) * 16u)));
         rb[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)(3 + e) * ugs + ui) * 16u)));
       }
-      const v4f *p4 = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(pk.res4 + (size_t)D * gs) + (size_t)(ui * 16u));
-      const v2f *p2 = reinterpret_cast<const v2f *>(reinterpret_cast<const char *>(pk.res2 + (size_t)D * gs) + (size_t)(ui * 8u));
-      const unsigned char *ps = pk.sel + (size_t)D * gs + (size_t)ui;
-      r4 = NT ? __builtin_nontemporal_load(p4) : *p4;
-      r2 = NT ? __builtin_nontemporal_load(p2) : *p2;
-      rot = NT ? __builtin_nontemporal_load(ps) : *ps;
+      const v4u *pt = reinterpret_cast<const v4u *>(reinterpret_cast<const char *>(pk.tail + (size_t)D * gs) + (size_t)(ui * 16u));
+      tl = NT ? __builtin_nontemporal_load(pt) : *pt;
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -209,11 +205,18 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
   }
 #else
   if constexpr (GAUX == 15) {
-    // packed read ("gauge_pack"): two rows, the fp32 residual of the third and the selector byte -- 121 bytes; the third row is
-    // rebuilt by the function that verified it bit for bit when the copy was built (gauge_pack_kernel, md_update.hip), and the rows
-    // go back to their places by selects on the selector: every load is uniform across the wave, the result is the stored link
-    const float rs[6] = {r4.x, r4.y, r4.z, r4.w, r2.x, r2.y};
-    tmhip_su3_row_rebuild(ra, rb, rs, rc);
+    // packed read ("gauge_pack"): two rows and the 16-byte tail -- 112 bytes; the third row is rebuilt and moved by the tail's
+    // offsets (integer additions on the bit patterns) by the functions that verified it bit for bit when the copy was built
+    // (gauge_pack_codec.h, gauge_pack_kernel in md_update.hip), and the rows go back to their places by selects on the tail's
+    // rotation: every load is uniform across the wave, the result is the stored link
+    tmhip_su3_row_rebuild(ra, rb, rc);
+    const uint32_t t[4] = {tl.x, tl.y, tl.z, tl.w};
+    const double w6[6] = {rc[0].x, rc[0].y, rc[1].x, rc[1].y, rc[2].x, rc[2].y};
+    double c6[6];
+    tmhip_gpack_decode(w6, t, c6);
+#pragma unroll
+    for (int e = 0; e < 3; e++) rc[e] = V2T{c6[2 * e], c6[2 * e + 1]};
+    const int rot = tmhip_gpack_rot(t);
 #pragma unroll
     for (int e = 0; e < 3; e++) {
       u[e] = rot == 0 ? ra[e] : (rot == 1 ? rc[e] : rb[e]);
@@ -1028,7 +1031,7 @@ static void launch_variant(const HopArgs &a, hipStream_t st, const HopLaunch &o)
         if (o.recon == 12) { launch_one<EPI, TSKIP, true, 256, 3, 12, 64>(a, st, o); return; }
 #ifndef HOP_GAUGE_PACKED
         if constexpr (!TSKIP) {
-          if (o.pack) { launch_one<EPI, 0, true, 256, 3, 15, 64>(a, st, o); if (o.pack_count) ++*o.pack_count; return; }   // bit-exact 121-byte link read ("gauge_pack")
+          if (o.pack) { launch_one<EPI, 0, true, 256, 3, 15, 64>(a, st, o); if (o.pack_count) ++*o.pack_count; return; }   // bit-exact 112-byte link read ("gauge_pack")
         }
 #endif
       }
@@ -1144,7 +1147,7 @@ static int pack_setup(tmhip_ctx *ctx, HopArgs &a, HopLaunch &o, int ieo, int epi
   if (tmhip_gauge_pack_prepare(ctx, &usable)) return 1;
   if (!usable) return 0;
   const size_t off = (size_t)(ieo ? 1 : 0) * 8 * ctx->gs;
-  a.pack.rows = ctx->gpack.rows + off * 6; a.pack.res4 = ctx->gpack.res4 + off; a.pack.res2 = ctx->gpack.res2 + off; a.pack.sel = ctx->gpack.sel + off;
+  a.pack.rows = ctx->gpack.rows + off * 6; a.pack.tail = ctx->gpack.tail + off;
   o.pack = 1; o.pack_count = &ctx->gpack_launches;
 #else
   (void)ctx; (void)a; (void)o; (void)ieo; (void)epi; (void)split;

@@ -313,12 +313,12 @@ int tmhip_resort_gauge(tmhip_ctx *ctx) {
 
 // ---- the packed twin of the gauge copy (TmhipGaugePack, tmhip_internal.h) ----
 // One thread per link slot of ctx->gauge (blockIdx.y = parity * 8 + direction).  The rotations r = first, first + 1, first + 2 (mod 3) are
-// tried in turn: rows r and r + 1 are kept, the residual of row r + 2 against its rebuild from them is taken in double and rounded
-// to fp32, the row is rebuilt WITH that residual by the function the stencil uses and compared with the stored row as 64-bit
-// integers.  The first rotation that reproduces all six reals is stored; a link without one is counted in count[2] and the field
-// is then not read packed at all.  count[0..1]: links on rotation 1 / 2 (one atomic per wave that has any).
-__global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__ g, v2d *__restrict__ rows, v4f *__restrict__ res4, v2f *__restrict__ res2,
-                                                         unsigned char *__restrict__ sel, int gs, int Vh, int first, unsigned int *count) {
+// tried in turn: rows r and r + 1 are kept, row r + 2 is rebuilt from them, the distance of the stored row from the rebuild is encoded
+// (gauge_pack_codec.h: six 21-bit offsets in ulps), decoded again by the function the stencil uses and compared with the stored row
+// as 64-bit integers.  The first rotation that reproduces all six reals is stored; a link without one is counted in count[2] and the
+// field is then not read packed at all.  count[0..1]: links on rotation 1 / 2 (one atomic per wave that has any).
+__global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__ g, v2d *__restrict__ rows, v4u *__restrict__ tail, int gs, int Vh, int first,
+                                                         unsigned int *count) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   int chosen = 0;   // 0..2: rotation, 3: none, -1: no link
   if (i >= Vh) chosen = -1;
@@ -328,35 +328,32 @@ __global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__
     v2d u[9];
 #pragma unroll
     for (int e = 0; e < 9; e++) u[e] = gp[(size_t)e * gs];
-    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     v2d ka[3], kb[3];
-    float kr[6];
-    int kept = 0;
+    uint32_t kt[4];
     chosen = 3;
     for (int n = 0; n < 3 && chosen == 3; n++) {
       const int r = (first + n) % 3;
-      v2d a[3], b[3], c[3], w[3], t[3];
-      float rs[6];
+      v2d a[3], b[3], c[3], w[3];
 #pragma unroll
       for (int e = 0; e < 3; e++) {   // selects, not indexed registers
         a[e] = r == 0 ? u[e] : (r == 1 ? u[3 + e] : u[6 + e]);
         b[e] = r == 0 ? u[3 + e] : (r == 1 ? u[6 + e] : u[e]);
         c[e] = r == 0 ? u[6 + e] : (r == 1 ? u[e] : u[3 + e]);
       }
-      tmhip_su3_row_rebuild(a, b, zero, w);
+      tmhip_su3_row_rebuild(a, b, w);
+      const double c6[6] = {c[0].x, c[0].y, c[1].x, c[1].y, c[2].x, c[2].y}, w6[6] = {w[0].x, w[0].y, w[1].x, w[1].y, w[2].x, w[2].y};
+      double t6[6];
+      uint32_t t[4];
+      bool same = tmhip_gpack_encode(c6, w6, r, t);
+      tmhip_gpack_decode(w6, t, t6);
+      same = same && tmhip_gpack_rot(t) == r;
 #pragma unroll
-      for (int e = 0; e < 3; e++) { rs[2 * e] = (float)(c[e].x - w[e].x); rs[2 * e + 1] = (float)(c[e].y - w[e].y); }
-      tmhip_su3_row_rebuild(a, b, rs, t);
-      bool same = true;
-#pragma unroll
-      for (int e = 0; e < 3; e++)
-        same = same && __double_as_longlong(t[e].x) == __double_as_longlong(c[e].x) && __double_as_longlong(t[e].y) == __double_as_longlong(c[e].y);
+      for (int e = 0; e < 6; e++) same = same && tmhip_gpack_bits(t6[e]) == tmhip_gpack_bits(c6[e]);
       if (same || n == 2) {   // (a link without an exact rotation still gets defined planes)
 #pragma unroll
         for (int e = 0; e < 3; e++) { ka[e] = a[e]; kb[e] = b[e]; }
 #pragma unroll
-        for (int e = 0; e < 6; e++) kr[e] = rs[e];
-        kept = r;
+        for (int e = 0; e < 4; e++) kt[e] = t[e];
         if (same) chosen = r;
       }
     }
@@ -365,9 +362,7 @@ __global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__
       rows[((size_t)blockIdx.y * 6 + e) * gs + i] = ka[e];
       rows[((size_t)blockIdx.y * 6 + 3 + e) * gs + i] = kb[e];
     }
-    res4[slot] = v4f{kr[0], kr[1], kr[2], kr[3]};
-    res2[slot] = v2f{kr[4], kr[5]};
-    sel[slot] = (unsigned char)kept;
+    tail[slot] = v4u{kt[0], kt[1], kt[2], kt[3]};
   }
 #pragma unroll
   for (int v = 1; v <= 3; v++) {
@@ -389,7 +384,7 @@ int tmhip_gauge_pack_prepare(tmhip_ctx *ctx, bool *usable) {
         ctx->gpack_ev_made = true;
       }
       // (out of memory is no error: the field is simply not read packed, and the allocation is not tried again)
-      if (hipMalloc(&ctx->gpack_mem, n * 121 + 64) != hipSuccess) {
+      if (hipMalloc(&ctx->gpack_mem, n * 112 + 64) != hipSuccess) {
         (void)hipGetLastError();
         ctx->gpack_mem = nullptr; ctx->gpack_unavailable = true;
         for (int k = 0; k < 4; k++) ctx->gpack_stats[k] = 0;
@@ -397,16 +392,14 @@ int tmhip_gauge_pack_prepare(tmhip_ctx *ctx, bool *usable) {
       }
       unsigned char *m = (unsigned char *)ctx->gpack_mem;
       ctx->gpack.rows = (const v2d *)m;
-      ctx->gpack.res4 = (const v4f *)(m + n * 96);
-      ctx->gpack.res2 = (const v2f *)(m + n * 112);
-      ctx->gpack.sel = m + n * 120;
-      ctx->gpack_count = (unsigned int *)(m + (n * 121 + 15) / 16 * 16);
+      ctx->gpack.tail = (const v4u *)(m + n * 96);
+      ctx->gpack_count = (unsigned int *)(m + n * 112);
     }
     TMHIP_CHECK(hipMemsetAsync(ctx->gpack_count, 0, 3 * sizeof(unsigned int), ctx->stream));
     TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[0], ctx->stream));
     const int first = ctx->opt_gauge_pack_rot < 0 ? 0 : ctx->opt_gauge_pack_rot;
     hipLaunchKernelGGL(gauge_pack_kernel, dim3((ctx->Vh + 255) / 256, 16), dim3(256), 0, ctx->stream, (const v2d *)ctx->gauge, (v2d *)ctx->gpack.rows,
-                       (v4f *)ctx->gpack.res4, (v2f *)ctx->gpack.res2, (unsigned char *)ctx->gpack.sel, ctx->gs, ctx->Vh, first, ctx->gpack_count);
+                       (v4u *)ctx->gpack.tail, ctx->gs, ctx->Vh, first, ctx->gpack_count);
     TMHIP_CHECK(hipGetLastError());
     TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[1], ctx->stream));
     unsigned int h[3] = {0, 0, 0};

@@ -13,6 +13,7 @@
 #include <cmath>
 #include "../../include/tmlqcd_hip.h"
 #include "op_table.h"
+#include "gauge_pack_codec.h"
 
 typedef double v2d __attribute__((ext_vector_type(2)));  // one complex double: .x = re, .y = im
 typedef float v2f __attribute__((ext_vector_type(2)));   // one complex float (mixed-precision CG)
@@ -83,36 +84,15 @@ struct TmhipDirect {
   unsigned long long sum_seq;   // reductions done so far (the same number on every rank)
 };
 
-// Packed links of the fp64 stencil: two rows of a link (six v2d planes), the fp32 residual of the third (a v4f and a v2f plane) and
-// one byte that says which cyclic rotation of the rows was stored: 96 + 24 + 1 = 121 bytes instead of 144.  Selector r: rows r and
-// r + 1 (mod 3) are kept, row r + 2 is tmhip_su3_row_rebuild of them.
+// Packed links of the fp64 stencil: two rows of a link (six v2d planes) and one 16-byte tail -- six 21-bit offsets, in ulps, of the
+// stored third row from its rebuild out of the other two, and two bits that say which cyclic rotation of the rows was stored:
+// 96 + 16 = 112 bytes instead of 144.  Rotation r: rows r and r + 1 (mod 3) are kept, row r + 2 is tmhip_su3_row_rebuild of them
+// plus the offsets.  The bit layout, the rebuild and the encode / decode pair live in gauge_pack_codec.h.
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 struct TmhipGaugePack {
   const v2d *rows;            // [8][6][gs]: kept row a (elements 0..2), kept row b (elements 0..2)
-  const v4f *res4;            // [8][gs]: residual of the rebuilt row, elements 0 and 1 (re, im, re, im)
-  const v2f *res2;            // [8][gs]: ... element 2
-  const unsigned char *sel;   // [8][gs]
+  const v4u *tail;            // [8][gs]
 };
-// The third row of an SU(3) link from the other two, c = conj(a x b) + residual: ONE sequence of operations for the kernel that builds
-// the packed copy (and verifies every link bit for bit) and for the stencil that reads it.  Explicit fma() calls, no contraction, the
-// residual added last in an addition of its own: both callers round exactly alike.
-__device__ __forceinline__ void tmhip_su3_row_rebuild(const v2d (&a)[3], const v2d (&b)[3], const float (&res)[6], v2d (&c)[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const int i = (k + 1) % 3, j = (k + 2) % 3;   // (a x b)_k = a_i b_j - a_j b_i
-    double re = a[i].x * b[j].x;
-    re = fma(-a[i].y, b[j].y, re);
-    re = fma(-a[j].x, b[i].x, re);
-    re = fma(a[j].y, b[i].y, re);
-    double im = a[i].x * b[j].y;
-    im = fma(a[i].y, b[j].x, im);
-    im = fma(-a[j].x, b[i].y, im);
-    im = fma(-a[j].y, b[i].x, im);
-    const double rr = (double)res[2 * k], ri = (double)res[2 * k + 1];
-    c[k].x = re + rr;
-    c[k].y = -im + ri;
-  }
-}
 
 struct tmhip_ctx {
   tmhip_geom g;
@@ -217,8 +197,8 @@ struct tmhip_ctx {
   void *flow;                         // gradient flow in progress (flow.hip): two link buffers and Z, from tmhip_flow_begin to tmhip_flow_end
   void *meas;                         // online measurements (meas.hip): partial sums and the pinned results of a call, allocated on first use
   double gauge_recon_dev;   // max |U_row2 - conj(row0 x row1)| over all links of the resident gauge field (-1: not measured)
-  // packed twin of the gauge copy (121 bytes per link, bit-exact: DESIGN.md section 6, "packed gauge read"), built on first use like gauge32
-  void *gpack_mem;          // one allocation behind the four plane sets of gpack
+  // packed twin of the gauge copy (112 bytes per link, bit-exact: DESIGN.md section 6, "packed gauge read"), built on first use like gauge32
+  void *gpack_mem;          // one allocation behind the two plane sets of gpack
   TmhipGaugePack gpack;     // device planes, [2 parities][8 directions][..][gs] each (null until the first build)
   int gpack_state;          // 0 stale, 1 built and every link has an exact rotation (the stencil may read it), 2 built, some link has none
   bool gpack_unavailable;   // the allocation failed once: the field is read in full from then on, no further attempt
