@@ -434,7 +434,7 @@ int tmlqcd_hip_ndrat_acc(spinor *const pf, spinor *const pf2, const double *mu, 
                          const double eps_sq, const int rel_prec, double *energy1);
 /* ---- the polynomial monomial NDPOLY (monomial/ndpoly_monomial.c, Ptilde_nd.h, linalg/assign_mul_add_mul_add_mul_add_mul_r.h) ----
  * fp64, unsplit lattices, the branch g_epsbar != 0 || phmc_exact_poly == 0.  Not built: type NDCLOVER (cloverndpoly), the phmc_exact_poly == 1
- * branches, the eigenvalue measurement (phmc_compute_ev stays the caller's), fp32 twins, T-split ranks.
+ * branches, fp32 twins, T-split ranks (phmc_compute_ev of ndpoly_monomial.c:176: tmlqcd_hip_phmc_compute_ev, below).
  * assign_mul_add_mul_add_mul_add_mul_r: N = VOLUME/2 (or 0).  Ptilde_ndpsi: Qsq = &Qtm_pm_ndpsi or &Qsw_pm_ndpsi, any other ends the program
  * with a message; phmc_cheb_evmin / phmc_cheb_evmax are read at call time (weak references: a host program without them cannot call it).
  * The three bodies take what the reference's bodies read from the monomial; the caller keeps ndpoly_set_global_parameter (g_mubar, g_epsbar)
@@ -453,6 +453,36 @@ int tmlqcd_hip_ndpoly_heatbath(spinor *const pf, spinor *const pf2, const _Compl
 int tmlqcd_hip_ndpoly_acc(spinor *const pf, spinor *const pf2, const _Complex double *MDPolyRoots, const int MDPolyDegree, const double MDPolyLocNormConst,
                           const double EVMaxInv, const double *MDPolyCoefs, const double *PtildeCoefs, const int PtildeDegree, const double EVMin,
                           const double PrecisionHfinal, double *energy1);
+/* ---- the eigenvalue measurement (solver/eigenvalues_bi.h, phmc.c:205-253, solver/eigenvalues.c:162-229) ----
+ * Thick-restart Lanczos on the device (tmhip_eigenvalues / tmhip_eigenvalues_nd of tmlqcd_hip.h) where the reference runs jdher /
+ * jdher_bi on LAPACK with host vectors; the basis never leaves the device.  Unsplit lattices, fp64.  The residency rules are those of
+ * the solvers; the doublet reads g_mubar, g_epsbar and phmc_invmaxev at the call.
+ *   eigenvalues_bi     under its reference name.  Qsq is recognised BY ADDRESS as &Qtm_pm_ndbipsi or &Qsw_pm_ndbipsi -- the reference's
+ *                      functions, declared weak here and never called (there are no bispinor data on the device) --, any other pointer
+ *                      ends the program with a message.  maxmin 0 lowest, 1 highest (JD_MINIMAL / JD_MAXIMAL).  Returns the first
+ *                      eigenvalue and sets *nev to the number converged (eigenvalues_bi.c:148-151); max_iterations bounds the restarts:
+ *                      the run takes at most max_iterations Lanczos cycles (option "eig_restarts" of tmlqcd_hip.h around the call).
+ *                      For &Qsw_pm_ndbipsi, and for clover != 0 below, the device's clover term must belong to the current links
+ *                      (tmlqcd_hip_sw_term, or the host's sw_term followed by tmlqcd_hip_update_clover) and sw_invert_nd(mubar^2 -
+ *                      epsbar^2) must have run on it, as for every symbol of the clover doublet above; otherwise the program ends
+ *                      with the core's message.
+ *   tmlqcd_hip_phmc_compute_ev   the body of phmc.c:205-253 for the monomial `name` with its EVMin: the lowest, then the highest
+ *                      eigenvalue of Qtm_pm_ndpsi (clover = 0) or Qsw_pm_ndpsi (clover != 0) to `prec` (eigenvalue_precision), the two
+ *                      warnings on stderr, and the line "%.8d %1.5e %1.5e %1.5e %1.5e\n" appended to monomial-<id>.data.  *ev_min, *ev_max
+ *                      (may be NULL) receive the two values.  Returns 0.
+ *   tmlqcd_hip_eigenvalues   the single-flavour case, in place of the jdher calls of eigenvalues.c:162-229: Qtm_pm_psi on VOLUME/2 sites
+ *                      when even_odd_flag is set, Q_pm_psi on VOLUME sites otherwise.  evals[0 .. *nev) and, when evecs is not NULL, the
+ *                      unit eigenvectors evecs[i * VOLUMEPLUSRAND/2 ...] (even_odd_flag) or evecs[i * VOLUMEPLUSRAND ...] in the host layout;
+ *                      *nev = the number converged; returns evals[0].  The files and the globals eigenvectors / eigenvls / inv_eigenvls
+ *                      stay the caller's.
+ * Not built: interior eigenvalues and index_jd, the deflation globals, eigenvalues_Jacobi / jdher_su3vect, T-split ranks. */
+typedef struct { spinor sp_up, sp_dn; } bispinor;                                      /* su3.h:70-73 */
+typedef void (*matrix_mult_bi)(bispinor *const, bispinor *const);                     /* solver/matrix_mult_typedef.h:34 */
+/* (Qtm_pm_ndbipsi and Qsw_pm_ndbipsi of operator/tm_operators_nd.h stay the host program's: the library refers to them weakly) */
+double eigenvalues_bi(int *nev, const int max_iterations, const double prec, const int maxmin, matrix_mult_bi Qsq);
+int tmlqcd_hip_phmc_compute_ev(const int trajectory_counter, const int id, const char *name, const double EVMin, const int clover,
+                               const double prec, double *ev_min, double *ev_max);
+double tmlqcd_hip_eigenvalues(int *nev, const int max_iterations, const double prec, const int maxmin, spinor *evecs, double *evals);
 /* type NDCLOVERRAT: the same three bodies on the clover doublet (Qsw_pm_ndpsi, Qsw_tau1_sub_const_ndpsi, H_eo_sw_ndpsi).  The derivative also
  * does the clover part of ndrat_monomial.c:80-86, :162-184 on the device: swm / swp zeroed, four sw_spinor_eo per shift, sw_deriv_nd(EE)
  * when trlog is set, sw_all(kappa, c_sw).  The caller runs tmlqcd_hip_sw_term and sw_invert_nd(mubar^2 - epsbar^2) first (:89-91).  The
@@ -492,7 +522,7 @@ int tmlqcd_hip_rat_acc(spinor *const pf, const double *mu, const double *rmu, co
  * them; the globals are left alone.  Clover types: the caller runs tmlqcd_hip_sw_term and tmlqcd_hip_sw_invert(EE, 0.), respectively
  * sw_invert_nd(mubar^2 - epsbar^2), first, as the reference's bodies do; otherwise the call ends the program with a message.
  * The reference's loops can apply Z a seventh time and then read past coefs[6]; these bodies end the program with a message naming delta and
- * accprec when the sixth application leaves delta >= accprec.  Unsplit lattices only.  Not built: check_C_psi / check_C_ndpsi, phmc_compute_ev. */
+ * accprec when the sixth application leaves delta >= accprec.  Unsplit lattices only.  Not built: check_C_psi / check_C_ndpsi (phmc_compute_ev: tmlqcd_hip_phmc_compute_ev). */
 int tmlqcd_hip_ratcor_heatbath(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter,
                                const double accprec, const int rel_prec, double *energy0, int *napp);
 int tmlqcd_hip_ratcor_acc(spinor *const pf, const double *mu, const double *rmu, const double A, const int np, const int max_iter, const double accprec,

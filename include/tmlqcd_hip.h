@@ -222,6 +222,64 @@ int tmhip_chrono_add_solution(tmhip_ctx *ctx, tmhip_field *slot, tmhip_field *tr
 /* step 3 alone, on the host: G (2 n n doubles, row-major, overwritten with its factors) y = b, y returned in b (2 n doubles); 1 <= n <= TMHIP_CSG_MAX */
 int tmhip_csg_solve(int n, double *G, double *b);
 
+/* ---- eigenvalue measurement (solver/eigenvalues.c, solver/eigenvalues_bi.c, phmc.c:205-253) -----------------
+ * The nev lowest (which = 0) or highest (which = 1) eigenpairs of a Hermitian positive operator by thick-restart Lanczos (Wu and
+ * Simon) with full reorthogonalisation (classical Gram-Schmidt, twice), where the reference runs Jacobi-Davidson on LAPACK with host
+ * vectors.  fp64, unsplit lattices.  The basis of a cycle has m = "eig_basis" vectors (tmhip_set_option; nev + 2 <= m <=
+ * TMHIP_EIG_MAX_BASIS), a restart keeps nev + (m - nev) / 2 Ritz vectors (at most m - 2) and the residual vector.  The small
+ * symmetric eigenproblem is solved on the host (tmhip_eig_small: cyclic Jacobi, csrc/eig_small.h).
+ *   tmhip_eigenvalues     op: the rows of the operator table marked TMHIP_S_EIG -- Qtm_pm_psi, Qsw_pm_psi (valid clover term) on EO
+ *                         fields with N = VOLUME/2, Q_pm_psi on FULL fields with N = VOLUME
+ *   tmhip_eigenvalues_nd  op: TMHIP_ND_OP_* (the doublet rows); a vector is the pair (up, dn)
+ * evals[0 .. nev): ascending for which = 0, descending for which = 1; each is the Rayleigh quotient <v, A v> of its Ritz vector with
+ * the operator itself, resid[i] = |A v_i - evals[i] v_i| with |v_i| = 1, computed, not estimated.  *converged = how many of the nev
+ * pairs have resid <= prec (an absolute bound, as tol of jdher); the run ends when all have.  max_apps (>= nev + 1) caps the
+ * operator applications, those of the residuals included; reaching it is no error: the call returns 0 with *converged < nev and the
+ * best estimates with their residuals (a pair the cap left no vector for comes back with resid = infinity).  *apps = applications done.
+ * evec (evec_up, evec_dn), NULL or nev fields of the operator's kind: on exit evec[i] is the unit eigenvector of evals[i].  ON ENTRY
+ * evec[0] is the start vector if its norm is not zero; otherwise (and with evec = NULL) a fixed pseudo-random vector starts the run.
+ * One start vector finds ONE eigenvector per distinct eigenvalue: exact multiplicities (the doublet at epsbar = 0) are not promised,
+ * a degenerate eigenvalue is reported once and the next distinct one follows.
+ * Option "eig_cheb" = d > 0 (default 4): the lowest end runs on B = T_d((hi + lo - 2 A) / (hi - lo)), whose largest eigenvalues are the wanted
+ * ones; eigenvalues and residuals are still those of A.  tmhip_eig_set_interval gives (lo, hi), 0 < lo < hi with every wanted
+ * eigenvalue below lo and the spectrum below hi; (0, 0), the default, takes them from one unfiltered cycle: hi = 1.1 (largest Ritz
+ * value + its residual bound), lo = the largest Ritz value the restart rule would keep.  The highest end always runs unfiltered.
+ * Option "eig_fused" 1 (default): tmhip_eig_dots / _eig_project / _basis_rotate, the coefficients never leave the device: a step is nine
+ * launches beside the operator (dots, project, dots, project, each with its one-block final pass, and the scaling to unit norm as a
+ * pass of its own) with one host synchronisation, and none inside the filter; 0: the same algorithm on tmhip_multi_scalar_prod (calls
+ * of up to TMHIP_CSG_MAX = 20 fields, six per launch inside), tmhip_multi_assign_diff_mul per vector, tmhip_square_norm, tmhip_mul_r and,
+ * for the rotation, tmhip_lincomb into work vectors, with their host round trips (the baseline of tools/eig_speed.py, the cross-check
+ * of the tests; its rotation holds up to m - 2 more vectors while it runs).  Neither form changes bits from call to call.
+ * Not built, so not measured against what is: the scaling folded into the second projection, and a rotation that walks its outputs in
+ * column groups (the rotation keeps all k accumulators of a thread in registers: 8 / 6 / 3 / 1 waves per SIMD for k <= 8 / 16 / 32 / 64).
+ * Work memory: m + 3 vectors (m + 1 basis, 2 work), allocated on first use, kept for the next call and freed with the context -- a
+ * vector being one EO field, one FULL field or two EO fields -- plus 2 * 65 block sums per block of a launch.
+ * Refused with a message, nothing written: an operator outside the rows above (tmhip_op_check / tmhip_nd_op_check), a clover row
+ * without its clover term, an N or fields that do not match the operator, nev + 2 > "eig_basis", a T-split context or its loopback
+ * rehearsal.
+ * Not built: T-split ranks, fp32 and mixed precision, block Lanczos, interior eigenvalues. */
+#define TMHIP_EIG_MAX_BASIS 64
+int tmhip_eigenvalues(tmhip_ctx *ctx, int op, int N, int nev, int which /* 0 lowest, 1 highest */, double prec, int max_apps,
+                      tmhip_field *const *evec /* nev fields or NULL */, double *evals, double *resid, int *converged, int *apps);
+int tmhip_eigenvalues_nd(tmhip_ctx *ctx, int op, int nev, int which, double prec, int max_apps, tmhip_field *const *evec_up,
+                         tmhip_field *const *evec_dn /* both nev fields, or both NULL */, double *evals, double *resid, int *converged, int *apps);
+int tmhip_eig_set_interval(tmhip_ctx *ctx, double lo, double hi);   /* 0, 0 = automatic */
+/* The pieces, public so that they can be tested.  A vector is v_up[i] alone (v_dn = NULL, w_dn = NULL: EO fields with 1 <= N <= VOLUME/2
+ * sites, or FULL fields with N = VOLUME) or the pair (v_up[i], v_dn[i]) of EO fields; all of one kind.
+ *   eig_dots      out[2i], out[2i+1] = Re, Im <v_i, w>, i < nv <= 65, in ONE launch that reads w once and every v_i once; an EO value
+ *                 carries the bits of tmhip_scalar_prod of the same pair (a pair of flavours: of the up value + the down value)
+ *   eig_project   w -= sum_i h_i v_i (h: nv complex coefficients), added up in ascending i; *sqnorm = |w|^2 of the result from the
+ *                 same pass.  w may not be one of the v_i.
+ *   basis_rotate  V[:, 0:k] = V[:, 0:n] Y in place, Y real n x k row-major, 1 <= k <= n <= TMHIP_EIG_MAX_BASIS; vectors k .. n-1
+ *                 are left as they are
+ *   eig_small     host only: A (n x n symmetric, row-major, n <= TMHIP_EIG_MAX_BASIS) -> its eigenvectors by column, w ascending */
+int tmhip_eig_dots(tmhip_ctx *ctx, int nv, tmhip_field *const *v_up, tmhip_field *const *v_dn, tmhip_field *w_up, tmhip_field *w_dn, int N,
+                   double *out /* 2 nv */);
+int tmhip_eig_project(tmhip_ctx *ctx, int nv, tmhip_field *const *v_up, tmhip_field *const *v_dn, tmhip_field *w_up, tmhip_field *w_dn,
+                      const double *h /* 2 nv */, int N, double *sqnorm);
+int tmhip_basis_rotate(tmhip_ctx *ctx, int n, int k, tmhip_field *const *v_up, tmhip_field *const *v_dn, const double *Y /* n * k */, int N);
+int tmhip_eig_small(int n, double *A /* n*n, in: symmetric, out: eigenvectors by column */, double *w);
+
 /* ---- non-degenerate twisted-mass doublet (operator/tm_operators_nd.c) ------------------------
  * A doublet is a pair of EO fields (strange = up, charm = dn).  Unsplit lattices only: a context with nproc_t > 1 refuses every
  * entry point below with a message.  Wilson twisted mass, fp64 (no clover term, no fp32 twins). */
@@ -412,7 +470,7 @@ int tmhip_cloverrat_acc(tmhip_ctx *ctx, tmhip_field *pf, const double *mu, const
  * Clover types: the clover term is the caller's, as for tmhip_cloverrat_* / tmhip_ndcloverrat_*: tmhip_sw_term and tmhip_sw_invert(EE, 0.)
  * (ratcor_monomial.c:75-76,137-138), respectively tmhip_sw_term and tmhip_sw_invert_nd(mubar^2 - epsbar^2) (ndratcor_monomial.c:77-78,146-147),
  * on the current links before the call; a missing or foreign clover term is refused exactly as those functions refuse it.
- * Not built: check_C_psi / check_C_ndpsi, fp32 fields, T-split lattices, phmc_compute_ev. */
+ * Not built: check_C_psi / check_C_ndpsi, fp32 fields, T-split lattices (phmc_compute_ev: tmhip_eigenvalues_nd). */
 int tmhip_rat_sum(tmhip_ctx *ctx, tmhip_field *out, tmhip_field *in, tmhip_field *const *chi, const double *rmu, int np, double c);
 int tmhip_rat_sum_nd(tmhip_ctx *ctx, tmhip_field *out_up, tmhip_field *out_dn, tmhip_field *in_up, tmhip_field *in_dn, tmhip_field *const *chi_up,
                      tmhip_field *const *chi_dn, const double *rmu, int np, double c);
@@ -438,7 +496,7 @@ int tmhip_ndratcor_acc(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, c
  * Qtm_dagger_ndpsi / Qtm_pm_ndpsi inside the bodies from tmhip_set_nd: the three bodies refuse, before any launch, an invmaxev that is not
  * the one of tmhip_set_nd.
  * Not built: type NDCLOVER (cloverndpoly), the phmc_exact_poly == 1 branches (P_ndpsi, Qtau1_P_ndpsi, Qtm_pm_sub_const_nrm_psi, Ptm_pm_psi),
- * Qtm_pm_ndbipsi, the eigenvalue measurement, fp32 twins, T-split ranks; degree_of_polynomial_nd / degree_of_Ptilde and the Chebyshev
+ * Qtm_pm_ndbipsi, fp32 twins, T-split ranks (the eigenvalue measurement is tmhip_eigenvalues_nd); degree_of_polynomial_nd / degree_of_Ptilde and the Chebyshev
  * coefficient routines are host scalar code and stay the reference's. */
 /* assign_mul_add_mul_add_mul_add_mul_r(R,S,U,V,c1,c2,c3,c4,VOLUME/2): R = c1 R + c2 S + c3 U + c4 V in that order; the fields may alias */
 int tmhip_assign_mul_add_mul_add_mul_add_mul_r(tmhip_ctx *ctx, tmhip_field *R, tmhip_field *S, tmhip_field *U, tmhip_field *V, double c1, double c2,
@@ -462,7 +520,7 @@ int tmhip_Ptilde_ndpsi(tmhip_ctx *ctx, tmhip_field *R_s, tmhip_field *R_c, const
  * with a smaller "poly_batch" starts from nothing), n < 3, a T-split context or its loopback rehearsal, fp32 / FULL fields or fields of
  * another stride, no gauge field, an invmaxev other than that of tmhip_set_nd. */
 int tmhip_ndpoly_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *roots, int n, double Cpol, double invmaxev);
-/* ndpoly_heatbath   :179-209, 255-256 without the RANLUX lines and phmc_compute_ev (the caller's, as for tmhip_ndrat_heatbath): pf holds
+/* ndpoly_heatbath   :179-209, 255-256 without the RANLUX lines and phmc_compute_ev (the caller's, as for tmhip_ndrat_heatbath; tmhip_eigenvalues_nd measures it): pf holds
  * the Gaussian field on entry and Ptilde B^dagger Q eta on exit, *energy0 = |eta|^2; the chain ping-pongs between two doublets */
 int tmhip_ndpoly_heatbath(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_dn, const double *roots, int n, double Cpol, double invmaxev,
                           const double *ptilde_coefs, int ptilde_n, double evmin, double evmax, double *energy0);
@@ -850,6 +908,10 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                before its MPI_Allreduce) or the sum over the ranks of a T split (1: its return value; needs the communicator, like parallel = 1)
  *   "csg_batch" 1 (default) | 0: tmhip_chrono_guess on the batched kernels (tmhip_multi_scalar_prod, tmhip_multi_assign_diff_mul, tmhip_lincomb)
  *                or as a sequence of the complex singles
+ *   "eig_basis" m (default 24; 3 .. TMHIP_EIG_MAX_BASIS), "eig_cheb" d (default 4; 0 = no filter), "eig_fused" 1 (default) | 0 -- the fastest
+ *                measured forms at 32^4, profiles/r19_eig_speed.log: the
+ *                eigenvalue measurement, tmhip_eigenvalues / tmhip_eigenvalues_nd (described there); "eig_restarts" n (default 0 = no
+ *                bound): a run ends after n Lanczos cycles as it ends at max_apps (the max_iterations of the drop-in's eigenvalues_bi)
  *   "cg_sync" 1: host-side scalars as in the reference loop;  "cg_batch" n: iterations enqueued between two polls of `done`
  *   "gauge_cache" -1 (automatic) / 0 / 1: the 64-thread stencil launches of small unsplit lattices, and the stencil launches of a T-split rank,
  *                  load the links with (0) or without (1) the streaming hint; automatic = without while the gauge copy is <= 200 MB (it then
@@ -880,6 +942,8 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  * function; a field in which some link has no exact rotation is read in full, silently.  0: never; 1: as automatic.  "gauge_recon" 12 takes
  * precedence.  "gauge_pack_rot" -1 (default: the first rotation that verifies) | 0 | 1 | 2 (try that rotation first; for tests). */
 int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value);
+/* the value an option has now, for a caller that changes one around a call and puts it back: "eig_basis", "eig_cheb", "eig_fused", "eig_restarts" */
+int tmhip_get_option(tmhip_ctx *ctx, const char *name, int *value);
 /* The packed twin of the gauge copy ("gauge_pack"), built now if it is stale: out = {1 if the stencil may read it else 0, links stored on
  * rotation 0, 1, 2, links without an exact rotation}.  tmhip_gauge_pack_build_ms: device time of the last build. */
 int tmhip_gauge_pack_stats(tmhip_ctx *ctx, long long out[5]);

@@ -30,6 +30,7 @@ extern double phmc_invmaxev __attribute__((weak));                 /* phmc.h:31 
 extern double phmc_cheb_evmin __attribute__((weak));               /* phmc.h:29: the interval of the Chebyshev sums (Ptilde_ndpsi) */
 extern double phmc_cheb_evmax __attribute__((weak));
 extern int phmc_exact_poly __attribute__((weak));                  /* phmc.c: 1 selects the branches of ndpoly_monomial.c that are not built */
+extern int even_odd_flag __attribute__((weak));                    /* read_input.h: tmlqcd_hip_eigenvalues picks Qtm_pm_psi (set, the default) or Q_pm_psi */
 extern double mixcg_innereps __attribute__((weak));               /* read_input.h:112 (only needed by mixed_cg_her) */
 extern int mixcg_maxinnersolverit __attribute__((weak));          /* read_input.h:113 */
 extern int g_sloppy_precision __attribute__((weak));              /* global.h:95 */
@@ -49,6 +50,9 @@ extern void *g_precWS __attribute__((weak));                       /* global.h:2
 extern double g_prec_sequence_d_dagger_d[3] __attribute__((weak)); /* solver/dirac_operator_eigenvectors.h:67 */
 void spinorPrecondition(spinor *spinor_out, const spinor *spinor_in, void *ws, int tt, int ll, const TM_COMPLEX alpha,
                         unsigned int dagger, unsigned int autofft) __attribute__((weak));
+// the two bispinor operators eigenvalues_bi is called with: the reference's functions, known here by their addresses only, never called
+void Qtm_pm_ndbipsi(bispinor *const bisp_l, bispinor *const bisp_k) __attribute__((weak));   /* operator/tm_operators_nd.h */
+void Qsw_pm_ndbipsi(bispinor *const bisp_l, bispinor *const bisp_k) __attribute__((weak));
 extern paramsGaugeInfo GaugeInfo;   /* defined with read_gauge_field below */
 }
 
@@ -1277,6 +1281,81 @@ int tmlqcd_hip_ndpoly_acc(spinor *const pf, spinor *const pf2, const _Complex do
   CK(tmhip_ndpoly_acc(c, fu, fd, (const double *)MDPolyRoots, MDPolyDegree, sqrt(MDPolyLocNormConst), EVMaxInv, MDPolyCoefs, PtildeCoefs, PtildeDegree, EVMin,
                       1.0, PrecisionHfinal, energy1, &corrections, nullptr));
   return corrections;
+}
+
+// ------------------------------------------------------------------ eigenvalue measurement (eig.hip)
+// max_iterations bounds the restarts: the run takes at most that many Lanczos cycles (option "eig_restarts", put back to "no bound" after
+// the call); the operator applications themselves are not capped
+static const int EIG_NO_APP_CAP = 2000000000;
+extern "C++" {
+template <class F> inline void with_restarts(tmhip_ctx *c, const int max_iterations, F body) {
+  CK(tmhip_set_option(c, "eig_restarts", max_iterations < 1 ? 1 : max_iterations));
+  body();
+  CK(tmhip_set_option(c, "eig_restarts", 0));
+}
+}
+/* solver/eigenvalues_bi.c:59-152 with Qsq = Qtm_pm_ndbipsi or Qsw_pm_ndbipsi, which are known here by their addresses only */
+double eigenvalues_bi(int *nev, const int max_iterations, const double prec, const int maxmin, matrix_mult_bi Qsq) {
+  int op = -1;
+  if (Qsq && Qsq == &Qtm_pm_ndbipsi) op = TMHIP_ND_OP_QTM_PM;
+  else if (Qsq && Qsq == &Qsw_pm_ndbipsi) op = TMHIP_ND_OP_QSW_PM;
+  if (op < 0) die("eigenvalues_bi: only Qsq = Qtm_pm_ndbipsi / Qsw_pm_ndbipsi runs on the device");
+  if (!nev || *nev < 1 || *nev > 62) die("eigenvalues_bi: the number of eigenvalues must be in [1, 62]");
+  tmhip_ctx *c = ses.refresh_nd("eigenvalues_bi");
+  double evals[64], resid[64];
+  int converged = 0, apps = 0;
+  with_restarts(c, max_iterations, [&] {
+    CK(tmhip_eigenvalues_nd(c, op, *nev, maxmin ? 1 : 0, prec < 1.e-14 ? 1.e-14 : prec, EIG_NO_APP_CAP, nullptr, nullptr, evals, resid, &converged, &apps));
+  });
+  *nev = converged;
+  return evals[0];
+}
+/* phmc.c:205-253 */
+int tmlqcd_hip_phmc_compute_ev(const int trajectory_counter, const int id, const char *name, const double EVMin, const int clover, const double prec,
+                               double *ev_min, double *ev_max) {
+  tmhip_ctx *c = ses.refresh_nd("tmlqcd_hip_phmc_compute_ev");
+  const int op = clover ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM;
+  double ev[2] = {0., 0.}, resid = 0.;
+  for (int maxmin = 0; maxmin < 2; maxmin++) {
+    int converged = 0, apps = 0;
+    with_restarts(c, 1000, [&] {   /* max_iter_ev = 1000, :218 */
+      CK(tmhip_eigenvalues_nd(c, op, 1, maxmin, prec < 1.e-14 ? 1.e-14 : prec, EIG_NO_APP_CAP, nullptr, nullptr, &ev[maxmin], &resid, &converged, &apps));
+    });
+  }
+  const char *mname = name ? name : "";
+  if (ev[1] > 1.) fprintf(stderr, "\nWarning: largest eigenvalue for monomial %s larger than upper bound!\n\n", mname);
+  if (ev[0] < EVMin) fprintf(stderr, "\nWarning: smallest eigenvalue for monomial %s smaller than lower bound!\n\n", mname);
+  char filename[100];
+  snprintf(filename, sizeof(filename), "monomial-%.2d.data", id);
+  FILE *countfile = fopen(filename, "a");
+  if (!countfile) die("tmlqcd_hip_phmc_compute_ev: cannot open the monomial's data file for appending");
+  fprintf(countfile, "%.8d %1.5e %1.5e %1.5e %1.5e\n", trajectory_counter, ev[0], ev[1], EVMin, 1.);
+  fclose(countfile);
+  if (ev_min) *ev_min = ev[0];
+  if (ev_max) *ev_max = ev[1];
+  return 0;
+}
+/* the jdher calls of solver/eigenvalues.c:162-229 */
+double tmlqcd_hip_eigenvalues(int *nev, const int max_iterations, const double prec, const int maxmin, spinor *evecs, double *evals) {
+  const bool eo = &even_odd_flag ? even_odd_flag != 0 : true;
+  const int N = eo ? VOLUME / 2 : VOLUME;
+  const int op = dev_op_of(eo ? &Qtm_pm_psi : &Q_pm_psi, N, TMHIP_S_EIG);
+  if (op < 0) die("tmlqcd_hip_eigenvalues: Q_pm_psi with a clover term (g_c_sw > 0) does not run on the device");
+  if (!nev || !evals || *nev < 1 || *nev > 62) die("tmlqcd_hip_eigenvalues: the number of eigenvalues must be in [1, 62]");
+  if (g_nproc_t > 1) die("tmlqcd_hip_eigenvalues: the eigenvalue measurement runs on unsplit lattices only");
+  tmhip_ctx *c = ses.refresh_for(op);
+  const int kind = op_kind(op), n = *nev;
+  const size_t stride = eo ? (size_t)VOLUMEPLUSRAND / 2 : (size_t)VOLUMEPLUSRAND;
+  tmhip_field *fv[64];
+  if (evecs) for (int i = 0; i < n; i++) fv[i] = in(c, evecs + i * stride, kind);   // evecs[0], when it is not zero, is the start vector
+  double resid[64];
+  int converged = 0, apps = 0;
+  with_restarts(c, max_iterations, [&] {
+    CK(tmhip_eigenvalues(c, op, N, n, maxmin ? 1 : 0, prec < 1.e-14 ? 1.e-14 : prec, EIG_NO_APP_CAP, evecs ? fv : nullptr, evals, resid, &converged, &apps));
+  });
+  if (evecs) for (int i = 0; i < n; i++) done(c, evecs + i * stride);
+  *nev = converged;
+  return evals[0];
 }
 
 // ------------------------------------------------------------------ rational monomials (rational.hip)

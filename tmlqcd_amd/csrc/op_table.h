@@ -15,20 +15,21 @@ enum { TMHIP_S_CG = 1      /* cg_her (both forms), chrono_guess */,
        TMHIP_S_RATCOR = 4  /* apply_Z, ratcor_* */,
        TMHIP_S_BICG = 8    /* bicgstab_complex */,
        TMHIP_S_ND = 16     /* the doublet solvers, Ptilde_ndpsi, apply_Z_nd, ndratcor_* */,
-       TMHIP_S_MIXED = 32  /* mixed_cg_her, rg_mixed_cg_her: asked through the fp32 column */ };
+       TMHIP_S_MIXED = 32  /* mixed_cg_her, rg_mixed_cg_her: asked through the fp32 column */,
+       TMHIP_S_EIG = 64    /* eigenvalues: the Hermitian positive single-flavour rows (the doublet call takes the TMHIP_S_ND rows) */ };
 // the clover column: what the context must hold.  TERM: sw and sw_inv valid (doublet rows: sw and sw_inv_nd); TERM_MINUS_MU: with
 // mu != 0 additionally the -mu set of sw_inv
 enum { TMHIP_SW_NONE = 0, TMHIP_SW_TERM = 1, TMHIP_SW_TERM_MINUS_MU = 2 };
 
 //  id suffix       reference function   fields  clover          fp32  solvers
 #define TMHIP_OP_TABLE(X)                                                                                 \
-  X(QTM_PM,         Qtm_pm_psi,          EO,     NONE,           1,    TMHIP_S_CG | TMHIP_S_MMS | TMHIP_S_RATCOR) \
+  X(QTM_PM,         Qtm_pm_psi,          EO,     NONE,           1,    TMHIP_S_CG | TMHIP_S_MMS | TMHIP_S_RATCOR | TMHIP_S_EIG) \
   X(QTM_PLUS,       Qtm_plus_psi,        EO,     NONE,           0,    TMHIP_S_CG | TMHIP_S_BICG)         \
   X(QTM_MINUS,      Qtm_minus_psi,       EO,     NONE,           0,    TMHIP_S_CG | TMHIP_S_BICG)         \
   X(MTM_PLUS,       Mtm_plus_psi,        EO,     NONE,           0,    TMHIP_S_CG | TMHIP_S_BICG)         \
   X(MTM_MINUS,      Mtm_minus_psi,       EO,     NONE,           0,    TMHIP_S_CG | TMHIP_S_BICG)         \
-  X(QSW_PM,         Qsw_pm_psi,          EO,     TERM,           1,    TMHIP_S_CG | TMHIP_S_MMS | TMHIP_S_RATCOR) \
-  X(Q_PM_FULL,      Q_pm_psi,            FULL,   NONE,           0,    TMHIP_S_MMS)                       \
+  X(QSW_PM,         Qsw_pm_psi,          EO,     TERM,           1,    TMHIP_S_CG | TMHIP_S_MMS | TMHIP_S_RATCOR | TMHIP_S_EIG) \
+  X(Q_PM_FULL,      Q_pm_psi,            FULL,   NONE,           0,    TMHIP_S_MMS | TMHIP_S_EIG)         \
   X(MTM_PLUS_SYM,   Mtm_plus_sym_psi,    EO,     NONE,           0,    TMHIP_S_BICG)                      \
   X(MTM_MINUS_SYM,  Mtm_minus_sym_psi,   EO,     NONE,           0,    TMHIP_S_BICG)                      \
   X(QSW_PLUS,       Qsw_plus_psi,        EO,     TERM,           0,    TMHIP_S_BICG)                      \

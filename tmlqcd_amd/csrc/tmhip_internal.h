@@ -215,6 +215,11 @@ struct tmhip_ctx {
   int opt_csg_batch;        // 1 (default): tmhip_chrono_guess on the batched kernels; 0: a sequence of the complex singles
   void *bicg;               // BiCGstab (bicgstab.hip): six work fields per field kind, the device state and the block sums, allocated on first use
   int opt_bicg_fused;       // 1 (default): tmhip_bicgstab_complex on the fused kernels with its scalars on the device; 0: the reference's statement sequence on the singles
+  void *eig;                // the eigensolver (eig.hip): basis and work vectors, block sums, the filter interval; allocated on first use
+  int opt_eig_basis;        // m: basis vectors of a thick-restart Lanczos cycle, nev + 2 <= m <= TMHIP_EIG_MAX_BASIS
+  int opt_eig_cheb;         // degree of the Chebyshev filter of the lowest end (0: none)
+  int opt_eig_restarts;     // > 0: a run ends after that many Lanczos cycles (the drop-in's max_iterations); 0 (default): only max_apps bounds it
+  int opt_eig_fused;        // 1 (default): eig_dots / eig_project / basis_rotate, coefficients on the device; 0: the same algorithm on the singles of linalg.hip
 };
 
 // N is a site count of a one-parity field: 0 is a legal empty loop in the reference (linalg/*.c), anything outside [0, V/2] would
@@ -427,6 +432,7 @@ void tmhip_mms_destroy(tmhip_ctx *ctx);  // mms.hip: work fields and state of th
 void tmhip_flow_destroy(tmhip_ctx *ctx); // flow.hip: the buffers of a gradient flow in progress
 void tmhip_meas_destroy(tmhip_ctx *ctx); // meas.hip: the reduction buffers of the online measurements
 void tmhip_bicg_destroy(tmhip_ctx *ctx); // bicgstab.hip: work fields and state of BiCGstab
+void tmhip_eig_destroy(tmhip_ctx *ctx);  // eig.hip: basis, work vectors and buffers of the eigensolver
 // launch geometry shared by linalg.hip and cg.hip
 #define LA_BS 256
 #define LA_UNROLL 4

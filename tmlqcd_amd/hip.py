@@ -254,6 +254,14 @@ def load_library():
         "tmhip_ndpoly_derivative": [vp, vp, vp, pd, i, d, d],
         "tmhip_ndpoly_heatbath": [vp, vp, vp, pd, i, d, d, pd, i, d, d, pd],
         "tmhip_ndpoly_acc": [vp, vp, vp, pd, i, d, d, pd, pd, i, d, d, d, pd, C.POINTER(i), pd],
+        "tmhip_eigenvalues": [vp, i, i, i, i, d, i, C.POINTER(vp), pd, pd, C.POINTER(i), C.POINTER(i)],
+        "tmhip_eigenvalues_nd": [vp, i, i, i, d, i, C.POINTER(vp), C.POINTER(vp), pd, pd, C.POINTER(i), C.POINTER(i)],
+        "tmhip_eig_set_interval": [vp, d, d],
+        "tmhip_eig_dots": [vp, i, C.POINTER(vp), C.POINTER(vp), vp, vp, i, pd],
+        "tmhip_eig_project": [vp, i, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, pd],
+        "tmhip_basis_rotate": [vp, i, i, C.POINTER(vp), C.POINTER(vp), pd, i],
+        "tmhip_eig_small": [i, pd, pd],
+        "tmhip_get_option": [vp, C.c_char_p, C.POINTER(i)],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -291,6 +299,17 @@ def csg_solve(G, b):
     pd = C.POINTER(C.c_double)
     _ck(load_library().tmhip_csg_solve(len(b), G.view(np.float64).ctypes.data_as(pd), b.view(np.float64).ctypes.data_as(pd)), "csg_solve")
     return b
+
+
+def eig_small(A):
+    """The small symmetric eigenproblem of the eigensolver alone (tmhip_eig_small; host code, no device needed): (w ascending, Y with
+    the eigenvectors by column) of the real symmetric matrix A, n <= 64."""
+    Y = np.array(A, dtype=np.float64, order="C")
+    n = Y.shape[0]
+    w = np.zeros(n)
+    pd = C.POINTER(C.c_double)
+    _ck(load_library().tmhip_eig_small(n, Y.ctypes.data_as(pd), w.ctypes.data_as(pd)), "eig_small")
+    return w, Y
 
 
 def write_lime_message(filename, record_type, text, mb, me, append=True):
@@ -419,6 +438,12 @@ class Lattice:
 
     def set_option(self, name, value):
         _ck(self.lib.tmhip_set_option(self.h, name.encode(), int(value)), "tmhip_set_option")
+
+    def get_option(self, name):
+        """the value an option has now (the eigensolver's options: "eig_basis", "eig_cheb", "eig_fused", "eig_restarts")"""
+        out = C.c_int()
+        _ck(self.lib.tmhip_get_option(self.h, name.encode(), C.byref(out)), "tmhip_get_option")
+        return out.value
 
     def gauge_su3_deviation(self):
         """max |row2 - conj(row0 x row1)| over the resident links (what the gauge_recon=12 guard looks at)."""
@@ -1105,6 +1130,105 @@ class Lattice:
                                             hist.ctypes.data_as(C.POINTER(C.c_double)), hist.size), "bicgstab_complex")
         n = it.value + 1 if it.value > 0 else hist.size
         return it.value, hist[:n]
+
+    # --- eigenvalue measurement (solver/eigenvalues.c, eigenvalues_bi.c; eig.hip) ---
+    @staticmethod
+    def _flavours(vs):
+        """a list of fields or of (up, dn) pairs -> (up handles, dn handles or None)"""
+        if len(vs) and isinstance(vs[0], (tuple, list)):
+            return Lattice._handles([v[0] for v in vs]), Lattice._handles([v[1] for v in vs])
+        return Lattice._handles(vs), None
+
+    def eig_dots(self, vs, w, N=None):
+        """[<v_i, w>] as a complex128 array from one launch; vs: fields, or (up, dn) pairs with w = (w_up, w_dn)"""
+        up, dn = self._flavours(vs)
+        wu, wd = (w[0].h, w[1].h) if dn is not None else (w.h, None)
+        out = np.zeros(len(vs), dtype=np.complex128)
+        _ck(self.lib.tmhip_eig_dots(self.h, len(vs), up, dn, wu, wd, self.Vh if N is None else N,
+                                    out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))), "eig_dots")
+        return out
+
+    def eig_project(self, vs, w, h, N=None):
+        """w -= sum_i h_i v_i, ascending i; returns |w|^2 of the result"""
+        up, dn = self._flavours(vs)
+        wu, wd = (w[0].h, w[1].h) if dn is not None else (w.h, None)
+        if len(h) != len(vs):
+            raise TmHipError("eig_project: one coefficient per vector")
+        keep, pc = self._pairs(h)
+        out = C.c_double()
+        _ck(self.lib.tmhip_eig_project(self.h, len(vs), up, dn, wu, wd, pc, self.Vh if N is None else N, C.byref(out)), "eig_project")
+        return out.value
+
+    def basis_rotate(self, vs, Y, N=None):
+        """V[:, 0:k] = V[:, 0:n] Y in place; Y real [n][k]"""
+        up, dn = self._flavours(vs)
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[0] != len(vs):
+            raise TmHipError("basis_rotate: Y must be [n = %d][k]" % len(vs))
+        _ck(self.lib.tmhip_basis_rotate(self.h, Y.shape[0], Y.shape[1], up, dn, Y.ctypes.data_as(C.POINTER(C.c_double)),
+                                        self.Vh if N is None else N), "basis_rotate")
+
+    def eig_set_interval(self, lo=0.0, hi=0.0):
+        """the interval of the Chebyshev filter ("eig_cheb"); 0, 0 = from one unfiltered cycle"""
+        _ck(self.lib.tmhip_eig_set_interval(self.h, lo, hi), "eig_set_interval")
+
+    def _eig(self, nd, op, N, nev, which, prec, max_apps, vectors, start, cheb):
+        w = {"lowest": 0, "highest": 1}.get(which, which)
+        kind = FIELD_FULL if (not nd and op == "Q_pm_psi") else FIELD_EO
+        fields = None
+        old_cheb = None
+        if cheb is not None:                 # for this call only: the context's option is back when it returns
+            old_cheb = self.get_option("eig_cheb")
+            self.set_option("eig_cheb", cheb)
+        try:
+            return self._eig_call(nd, op, N, nev, w, kind, prec, max_apps, vectors, start)
+        finally:
+            if old_cheb is not None:
+                self.set_option("eig_cheb", old_cheb)
+
+    def _eig_call(self, nd, op, N, nev, w, kind, prec, max_apps, vectors, start):
+        fields = None
+        if vectors or start is not None:
+            fields = [((self.field(), self.field()) if nd else self.field(kind=kind)) for _ in range(nev)]
+            for f in fields:
+                for g in (f if nd else (f,)):
+                    g.zero()
+            if start is not None:
+                for g, s in zip(fields[0] if nd else (fields[0],), start if nd else (start,)):
+                    g.upload(s)
+        up, dn = self._flavours(fields) if fields else (None, None)
+        ev, rs = np.zeros(nev), np.zeros(nev)
+        conv, apps = C.c_int(), C.c_int()
+        pd = C.POINTER(C.c_double)
+        if nd:
+            rc = self.lib.tmhip_eigenvalues_nd(self.h, ND_OPS[op], nev, w, prec, max_apps, up, dn, ev.ctypes.data_as(pd), rs.ctypes.data_as(pd),
+                                               C.byref(conv), C.byref(apps))
+        else:
+            rc = self.lib.tmhip_eigenvalues(self.h, ALL_OPS[op], (self.V if kind == FIELD_FULL else self.Vh) if N is None else N, nev, w, prec,
+                                            max_apps, up, ev.ctypes.data_as(pd), rs.ctypes.data_as(pd), C.byref(conv), C.byref(apps))
+        if rc != 0 and fields:
+            for f in fields:
+                for g in (f if nd else (f,)):
+                    g.free()
+        _ck(rc, "eigenvalues_nd" if nd else "eigenvalues")
+        out = {"evals": ev, "resid": rs, "converged": conv.value, "apps": apps.value}
+        if vectors:
+            out["vectors"] = fields
+        elif fields:
+            for f in fields:
+                for g in (f if nd else (f,)):
+                    g.free()
+        return out
+
+    def eigenvalues(self, nev, which="lowest", prec=1e-7, max_apps=5000, op="Qtm_pm_psi", N=None, vectors=False, start=None, cheb=None):
+        """The nev lowest / highest eigenpairs of a Hermitian positive single-flavour operator (Qtm_pm_psi, Qsw_pm_psi, Q_pm_psi on FULL
+        fields) -> {"evals", "resid", "converged", "apps"[, "vectors": nev device fields, the caller's to free]}.  start: a host
+        spinor array as the start vector; cheb: the degree of the filter of the lowest end for THIS call (the option "eig_cheb" otherwise)."""
+        return self._eig(False, op, N, nev, which, prec, max_apps, vectors, start, cheb)
+
+    def eigenvalues_nd(self, nev, which="lowest", prec=1e-7, max_apps=5000, op="Qtm_pm_ndpsi", vectors=False, start=None, cheb=None):
+        """The same for the doublet operators; vectors and start are (up, dn) pairs."""
+        return self._eig(True, op, None, nev, which, prec, max_apps, vectors, start, cheb)
 
     # --- non-degenerate doublet (operator/tm_operators_nd.c; strange = up = first field of a pair) ---
     def set_nd(self, mubar, epsbar, invmaxev=1.0):

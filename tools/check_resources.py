@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/bicgstab.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/poly.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/bicgstab.ru.txt lib/eig.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/poly.ru.txt
 """
 import re
 import subprocess
@@ -78,6 +78,15 @@ RULES = [
     # iteration -- K4 walks six fields with three accumulators --: streams like the ones above, no scratch, eight waves per SIMD
     (r"^void cplx3_kernel<[01]>", "three-field complex singles", 8),
     (r"^(void )?bicghip::(dot_kernel<(true|false)>|sub_kernel|update_kernel|dir_kernel)", "fused BiCGstab", 8),
+    # the eigensolver (eig.hip): its dots, projection, scaling and Chebyshev step are streams like the ones above -- four elements of w
+    # in registers whatever the number of basis vectors -- no scratch, eight waves per SIMD.  The rotation keeps K complex accumulators
+    # per thread, K = 8 / 16 / 32 / 64 by the number of columns: no scratch; the floor of each instance is what the build reports for
+    # this, the only form that was built (a column-group form for large k was not, so 64 columns at one wave per SIMD is unrivalled, not best)
+    (r"^(void )?eighip::(eig_dots_kernel|eig_project_kernel|eig_scale_kernel|eig_cheb_kernel)", "eigensolver streams", 8),
+    (r"^void eighip::basis_rotate_kernel<8>", "basis rotation, 8 columns", 8),
+    (r"^void eighip::basis_rotate_kernel<16>", "basis rotation, 16 columns", 6),
+    (r"^void eighip::basis_rotate_kernel<32>", "basis rotation, 32 columns", 3),
+    (r"^void eighip::basis_rotate_kernel<64>", "basis rotation, 64 columns", 1),
     # the four-term combination of the polynomial monomial (poly.hip), both flavours of a doublet per launch: a stream like the ones above
     (r"^(void )?polyhip::comb4_kernel", "four-term combination", 8),
     # propagator / source records (spinor_io.hip): byte work through an LDS tile, a handful of registers; "no scratch" is the floor
