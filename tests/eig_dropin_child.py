@@ -9,9 +9,7 @@ maximum exceeds 1) and tmlqcd_hip_eigenvalues with host vectors, and prints one 
 the CPU oracle's operators they are held against, the lines of monomial-03.data and the residuals of the returned vectors
 through the oracle's Qtm_pm_psi.  Markers on stderr separate the two phmc_compute_ev calls for the parent."""
 import ctypes as C
-import json
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -20,6 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import nd_restate as nd  # noqa: E402
+from tests import hostprog  # noqa: E402
 from tests.util import random_gauge  # noqa: E402
 
 VP, dbl, INT = C.c_void_p, C.c_double, C.c_int
@@ -49,35 +48,12 @@ def _dense(A, dim):
 
 
 def main(mode):
-    tmp = tempfile.mkdtemp()
-    host, extra = os.path.join(tmp, "libhost.so"), os.path.join(tmp, "libeigglobals.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", host, os.path.join(ROOT, "tests", "host_stub", "globals.c"), "-lm"])
-    src = os.path.join(tmp, "eig.c")
-    open(src, "w").write(GLOBALS)
-    subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-o", extra, src])
-    os.chdir(tmp)                                     # monomial-03.data lands here
-    stub = C.CDLL(host, mode=C.RTLD_GLOBAL)
-    eg = C.CDLL(extra, mode=C.RTLD_GLOBAL)
-    d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-    stub.stub_init.restype = VP
-    stub.stub_init.argtypes = [INT] * 4
-    stub.stub_boundary.argtypes = [dbl] * 5
-    stub.stub_set_mu.argtypes = [dbl]
-    stub.stub_calloc.restype = VP
-    stub.stub_calloc.argtypes = [C.c_size_t]
-    eg.eig_set.argtypes = [dbl] * 3
-    pi, pd_ = C.POINTER(INT), C.POINTER(dbl)
-    d.tmlqcd_hip_set_residency.argtypes = [INT]
-    d.tmlqcd_hip_sync_to_host.argtypes = [VP]
-    d.eigenvalues_bi.restype = dbl
-    d.eigenvalues_bi.argtypes = [pi, INT, dbl, INT, VP]
-    d.tmlqcd_hip_phmc_compute_ev.argtypes = [INT, INT, C.c_char_p, dbl, INT, dbl, pd_, pd_]
-    d.tmlqcd_hip_eigenvalues.restype = dbl
-    d.tmlqcd_hip_eigenvalues.argtypes = [pi, INT, dbl, INT, VP, pd_]
+    stub, eg, d = hostprog.load(extra_c=GLOBALS, extra_prototypes={"eig_set": (None, [dbl] * 3)})
+    pd_ = C.POINTER(dbl)
 
     if mode == "other_pointer":
         T, LX, LY, LZ = SHAPE
-        g = stub.stub_init(T, LX, LY, LZ)
+        stub.stub_init(T, LX, LY, LZ)
         nev = INT(1)
         d.eigenvalues_bi(C.byref(nev), 10, PREC, 0, C.cast(eg.some_other_operator, VP))
         print("eigenvalues_bi returned for a pointer it does not know")
@@ -90,11 +66,9 @@ def main(mode):
     orc = Oracle(T, LX, LY, LZ, kappa=KAPPA, mu=MU, theta=THETA, threads=1)
     gauge = random_gauge(97, orc.VPR)
     orc.set_gauge(gauge)
-    g = stub.stub_init(T, LX, LY, LZ)
-    C.memmove(g, gauge.ctypes.data, gauge.nbytes)
-    stub.stub_boundary(KAPPA, *THETA)
+    hostprog.init_lattice(stub, T, LX, LY, LZ, gauge, KAPPA, THETA)
     stub.stub_set_mu(MU)
-    d.tmlqcd_hip_set_residency({"coherent": 0, "resident": 1, "lazy": 2}[mode])
+    d.tmlqcd_hip_set_residency(hostprog.MODES[mode])   # (no way back at the end: tmlqcd_hip_finalize() ends this program)
 
     # the dense spectra: the doublet at invmaxev = 1 (its eigenvalues scale with invmaxev^2) and Qtm_pm_psi
     H = nd.hop_over(orc.Hopping_Matrix, N)
@@ -156,9 +130,13 @@ def main(mode):
         norms.append(float(np.linalg.norm(v)))
     out.update({"one_first": first, "one_evals": list(evals), "one_nev": nev.value, "one_resid": res, "one_norms": norms})
     d.tmlqcd_hip_finalize()
-    print(json.dumps(out))
-    sys.stdout.flush()
+    hostprog.emit(out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    with tempfile.TemporaryDirectory() as tmp_dir:
+        os.chdir(tmp_dir)                             # monomial-03.data lands here
+        try:
+            main(sys.argv[1])
+        finally:
+            os.chdir(ROOT)

@@ -11,26 +11,18 @@ and prints the results as one JSON line.  Mode "unopenable" finds a directory un
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tests import flow_restate as fr  # noqa: E402
+from tests import hostprog  # noqa: E402
+from tests.hostprog import FSO, HF  # noqa: E402
 
-VP, dbl, INT = C.c_void_p, C.c_double, C.c_int
+VP, dbl = C.c_void_p, C.c_double
 GOLD = os.path.join(ROOT, "tests", "golden")
-
-
-class FSO(C.Structure):       # meas/field_strength_types.h
-    _fields_ = [("E", dbl), ("Q", dbl)]
-
-
-class HF(C.Structure):        # hamiltonian_field.h:26-32
-    _fields_ = [("gaugefield", VP), ("momenta", VP), ("derivative", VP), ("update_gauge_copy", INT), ("traj_counter", INT)]
 
 
 def main(mode):
@@ -38,28 +30,8 @@ def main(mode):
     dims = (4, 4, 4, 4)
     V = 256
     gauge = np.ascontiguousarray(np.load(os.path.join(GOLD, "ref_fields_4x4.npz"))["gauge"][:V])
-    tmp = tempfile.mkdtemp()
-    host = os.path.join(tmp, "libhost.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", host, os.path.join(ROOT, "tests", "host_stub", "globals.c"), "-lm"])
-    stub = C.CDLL(host, mode=C.RTLD_GLOBAL)
-    d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-    stub.stub_init.restype = VP
-    stub.stub_init.argtypes = [INT] * 4
-    stub.stub_boundary.argtypes = [dbl] * 5
-    stub.stub_set_mu.argtypes = [dbl]
-    d.measure_clover_field_strength_observables.restype = None
-    d.measure_clover_field_strength_observables.argtypes = [VP, C.POINTER(FSO)]
-    d.tmlqcd_hip_gradient_flow_measurement.restype = None
-    d.tmlqcd_hip_gradient_flow_measurement.argtypes = [INT, dbl, dbl]
-    d.tmlqcd_hip_set_residency.argtypes = [INT]
-    d.tmlqcd_hip_update_gauge.restype = None
-    d.tmlqcd_hip_update_gauge.argtypes = [dbl, C.POINTER(HF)]
-    d.tmlqcd_hip_sync_gauge_to_host.argtypes = [C.POINTER(HF)]
-    d.tmlqcd_hip_calls.restype = C.c_ulong
-
-    gptr = stub.stub_init(*dims)
-    C.memmove(gptr, gauge.ctypes.data, gauge.nbytes)
-    stub.stub_boundary(0.125, 0., 0., 0., 0.)
+    stub, _, d = hostprog.load()
+    gptr = hostprog.init_lattice(stub, *dims, gauge, 0.125)
     stub.stub_set_mu(0.01)
     grows = (VP * V)(*[gptr + 4 * 144 * i for i in range(V)])
     gf = C.cast(grows, VP)
@@ -99,8 +71,7 @@ def main(mode):
         out["moved_want_E"], out["moved_want_Q"] = fr.field_strength(moved, dims)
         out["moved_sum_abs_q"] = fr.sum_abs_q(moved, dims)
     d.tmlqcd_hip_finalize()
-    print(json.dumps(out))
-    sys.stdout.flush()
+    hostprog.emit(out)
 
 
 if __name__ == "__main__":

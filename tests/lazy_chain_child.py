@@ -2,36 +2,23 @@
 handler is installed BEFORE the library's.  Prints one line, "OK ..." or the reason it is not."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
 from tests.util import TOL, random_gauge, random_spinor, rel_err  # noqa: E402
 
 VP = C.c_void_p
-d0 = os.path.join(ROOT, "tests", "host_stub")
-so, src = os.path.join(d0, "libtmhost.so"), os.path.join(d0, "globals.c")
-if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", so, src, "-lm"])
-stub = C.CDLL(so, mode=C.RTLD_GLOBAL)
-import tmlqcd_amd  # noqa: E402
-tmlqcd_amd.load_library()
-d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-stub.stub_init.restype = VP; stub.stub_init.argtypes = [C.c_int] * 4
-stub.stub_boundary.argtypes = [C.c_double] * 5
-stub.stub_set_mu.argtypes = [C.c_double]
-d.Hopping_Matrix.argtypes = [C.c_int, VP, VP]
-d.tmlqcd_hip_set_residency.argtypes = [C.c_int]
+stub, _, d = hostprog.load(core_first=True)
 
 T = L = 8
 V = T * L ** 3
 N = V // 2
 g = random_gauge(5, V)
-C.memmove(stub.stub_init(T, L, L, L), g.ctypes.data_as(VP), g.nbytes)
-stub.stub_boundary(0.13, 0.0, 0.0, 0.0, 0.0)
+hostprog.init_lattice(stub, T, L, L, L, g, 0.13)
 stub.stub_set_mu(0.01)
 assert stub.stub_install_segv_probe() == 0                    # the program's handler first ...
 assert stub.stub_touch_guard() == 1                           # ... and it works on its own

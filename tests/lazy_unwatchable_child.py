@@ -5,7 +5,6 @@ call, and the results are the coherent mode's.  With TMLQCD_HIP_LAZY_FORCE_WATCH
 of them must end the process with a message -- not hang it, which is what a fault taken inside malloc did in round 3."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import threading
 
@@ -13,34 +12,21 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
 from tests.util import random_gauge, random_spinor  # noqa: E402
 
 where = sys.argv[1]
 VP = C.c_void_p
-d0 = os.path.join(ROOT, "tests", "host_stub")
-so, src = os.path.join(d0, "libtmhost.so"), os.path.join(d0, "globals.c")
-if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", so, src, "-lm"])
-stub = C.CDLL(so, mode=C.RTLD_GLOBAL)
-import tmlqcd_amd  # noqa: E402
-tmlqcd_amd.load_library()
-d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-stub.stub_init.restype = VP; stub.stub_init.argtypes = [C.c_int] * 4
-stub.stub_boundary.argtypes = [C.c_double] * 5
-stub.stub_set_mu.argtypes = [C.c_double]
-d.Hopping_Matrix.argtypes = [C.c_int, VP, VP]
-d.tmlqcd_hip_set_residency.argtypes = [C.c_int]
+stub, _, d = hostprog.load(core_first=True)
 libc = C.CDLL(None, use_errno=True)
-libc.malloc.restype = VP; libc.malloc.argtypes = [C.c_size_t]
-libc.mmap.restype = VP; libc.mmap.argtypes = [VP, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long]
-libc.mallopt.argtypes = [C.c_int, C.c_int]
+hostprog.set_prototypes(libc, {"malloc": (VP, [C.c_size_t]), "mmap": (VP, [VP, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long]),
+                               "mallopt": (C.c_int, [C.c_int, C.c_int])})
 
 T = L = 8
 V = T * L ** 3
 N = V // 2
 g = random_gauge(5, V)
-C.memmove(stub.stub_init(T, L, L, L), g.ctypes.data_as(VP), g.nbytes)
-stub.stub_boundary(0.13, 0.0, 0.0, 0.0, 0.0)
+hostprog.init_lattice(stub, T, L, L, L, g, 0.13)
 stub.stub_set_mu(0.01)
 nb = 3 * N * 192 + 64
 if where == "shared":

@@ -11,18 +11,16 @@ and prints the results as one JSON line; the files are left in the working direc
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
+from tests.hostprog import PD, VP  # noqa: E402
 from tests.util import random_spinor  # noqa: E402
 
-VP, dbl, INT = C.c_void_p, C.c_double, C.c_int
-PD = C.POINTER(dbl)
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
@@ -32,31 +30,8 @@ def main(mode):
     V = 256
     gauge = np.ascontiguousarray(np.load(os.path.join(GOLD, "ref_fields_4x4.npz"))["gauge"][:V])
     even, odd = random_spinor(s["prop_seeds"][0], V // 2), random_spinor(s["prop_seeds"][1], V // 2)
-    tmp = tempfile.mkdtemp()
-    host = os.path.join(tmp, "libhost.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", host, os.path.join(ROOT, "tests", "host_stub", "globals.c"), "-lm"])
-    stub = C.CDLL(host, mode=C.RTLD_GLOBAL)
-    d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-    stub.stub_init.restype = VP
-    stub.stub_init.argtypes = [INT] * 4
-    stub.stub_boundary.argtypes = [dbl] * 5
-    stub.stub_set_mu.argtypes = [dbl]
-    d.tmlqcd_hip_slice_correlators.restype = None
-    d.tmlqcd_hip_slice_correlators.argtypes = [VP, VP, INT, PD, PD, PD]
-    d.measure_oriented_plaquettes.restype = None
-    d.measure_oriented_plaquettes.argtypes = [VP, PD]
-    d.oriented_plaquettes_measurement.restype = None
-    d.oriented_plaquettes_measurement.argtypes = [INT, INT, INT]
-    d.tmlqcd_hip_polyakov_loop.restype = None
-    d.tmlqcd_hip_polyakov_loop.argtypes = [PD, INT]
-    d.tmlqcd_hip_polyakov_loop_dir.restype = INT
-    d.tmlqcd_hip_polyakov_loop_dir.argtypes = [INT, INT]
-    d.tmlqcd_hip_set_residency.argtypes = [INT]
-    d.tmlqcd_hip_calls.restype = C.c_ulong
-
-    gptr = stub.stub_init(*dims)
-    C.memmove(gptr, gauge.ctypes.data, gauge.nbytes)
-    stub.stub_boundary(s["kappa"], 0., 0., 0., 0.)
+    stub, _, d = hostprog.load()
+    gptr = hostprog.init_lattice(stub, *dims, gauge, s["kappa"])
     stub.stub_set_mu(s["mu"])
     grows = (VP * V)(*[gptr + 4 * 144 * i for i in range(V)])
     gf = C.cast(grows, VP)
@@ -97,8 +72,7 @@ def main(mode):
         out["polyakov"].append(pl.tolist())
     out["calls_served"] = int(d.tmlqcd_hip_calls() - n0)
     d.tmlqcd_hip_finalize()
-    print(json.dumps(out))
-    sys.stdout.flush()
+    hostprog.emit(out)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,6 @@ field): it calls the REFERENCE-NAMED symbols of libtmlqcd_dropin.so -- Hopping_M
 parallel = 1, cg_her with a function pointer -- after tmlqcd_hip_comm_init_shm.  WORLD = 1: the unsplit host program."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import faulthandler
@@ -16,36 +15,18 @@ faulthandler.dump_traceback_later(int(os.environ.get("MP_WORKER_TIMEOUT", "240")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
 from tmlqcd_amd import synthetic as syn  # noqa: E402
 
 rank, world, job, outdir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
 VP = C.c_void_p
-d0 = os.path.join(ROOT, "tests", "host_stub")
-so, src = os.path.join(d0, "libtmhost.so"), os.path.join(d0, "globals.c")
-if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", so + ".%d" % os.getpid(), src, "-lm"])
-    os.replace(so + ".%d" % os.getpid(), so)          # (several ranks may get here at once)
-stub = C.CDLL(so, mode=C.RTLD_GLOBAL)
-import tmlqcd_amd  # noqa: E402
-tmlqcd_amd.load_library()
-d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-stub.stub_init_rank.restype = VP; stub.stub_init_rank.argtypes = [C.c_int] * 6
-stub.stub_boundary.argtypes = [C.c_double] * 5
-stub.stub_set_mu.argtypes = [C.c_double]
-d.Hopping_Matrix.argtypes = [C.c_int, VP, VP]
-d.Qtm_pm_psi.argtypes = [VP, VP]
-d.square_norm.restype = C.c_double; d.square_norm.argtypes = [VP, C.c_int, C.c_int]
-d.scalar_prod_r.restype = C.c_double; d.scalar_prod_r.argtypes = [VP, VP, C.c_int, C.c_int]
-d.cg_her.restype = C.c_int; d.cg_her.argtypes = [VP, VP, C.c_int, C.c_double, C.c_int, C.c_int, VP]
-d.tmlqcd_hip_comm_init_shm.argtypes = [C.c_char_p]
-d.tmlqcd_hip_set_residency.argtypes = [C.c_int]
+stub, _, d = hostprog.load(core_first=True)
 
 Tg, L = 8, 8
 T = Tg // world
 N = T * L ** 3 // 2
 g = syn.gauge_field(41, T, L, L, L, world, rank)                       # [VOLUMEPLUSRAND][4] su3, halo slices filled as xchange_gauge would
-C.memmove(stub.stub_init_rank(T, L, L, L, world, rank), g.ctypes.data_as(VP), g.nbytes)
-stub.stub_boundary(0.13, 1.0, 0.0, 0.0, 0.0)
+hostprog.init_lattice(stub, T, L, L, L, g, 0.13, (1.0, 0.0, 0.0, 0.0), rank=(world, rank))
 stub.stub_set_mu(0.02)
 if world > 1:
     d.tmlqcd_hip_comm_init_shm(job.encode())

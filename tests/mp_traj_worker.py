@@ -6,7 +6,6 @@ group; then a second snapshot, another update and tmlqcd_hip_reject_links.  What
 import ctypes as C
 import faulthandler
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,35 +15,13 @@ faulthandler.dump_traceback_later(int(os.environ.get("MP_WORKER_TIMEOUT", "240")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
 from tests import traj_restate as tj  # noqa: E402
+from tests.hostprog import HF  # noqa: E402
 
 rank, world, job, outdir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
 VP, dbl = C.c_void_p, C.c_double
-d0 = os.path.join(ROOT, "tests", "host_stub")
-so, src = os.path.join(d0, "libtmhost.so"), os.path.join(d0, "globals.c")
-if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", so + ".%d" % os.getpid(), src, "-lm"])
-    os.replace(so + ".%d" % os.getpid(), so)          # (several ranks may get here at once)
-stub = C.CDLL(so, mode=C.RTLD_GLOBAL)
-import tmlqcd_amd  # noqa: E402
-tmlqcd_amd.load_library()
-d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-
-
-class HF(C.Structure):        # hamiltonian_field.h:26-32
-    _fields_ = [("gaugefield", VP), ("momenta", VP), ("derivative", VP), ("update_gauge_copy", C.c_int), ("traj_counter", C.c_int)]
-
-
-P = C.POINTER(HF)
-stub.stub_init_rank.restype = VP; stub.stub_init_rank.argtypes = [C.c_int] * 6
-stub.stub_boundary.argtypes = [dbl] * 5
-stub.stub_set_mu.argtypes = [dbl]
-for name, res, args in (("tmlqcd_hip_gauge_snapshot", None, [P]), ("tmlqcd_hip_moment_energy", dbl, [P]), ("tmlqcd_hip_gauge_snapshot_diff", dbl, [P]),
-                        ("tmlqcd_hip_accept_links", None, [P, C.c_int]), ("tmlqcd_hip_reject_links", None, [P]),
-                        ("tmlqcd_hip_force_norms", None, [P, C.POINTER(dbl), C.POINTER(dbl)]), ("tmlqcd_hip_update_gauge", None, [dbl, P]),
-                        ("tmlqcd_hip_gauge_derivative", None, [P, dbl, dbl, dbl, C.c_int, dbl]), ("tmlqcd_hip_comm_init_shm", None, [C.c_char_p])):
-    f = getattr(d, name)
-    f.restype, f.argtypes = res, args
+stub, _, d = hostprog.load(core_first=True)
 
 DIMS = (8, 4, 4, 4)
 Tg, L = DIMS[0], DIMS[1]
@@ -54,9 +31,7 @@ sl = lambda a, r: a[(r % world) * V:(r % world + 1) * V]
 noisy = tj.noisy_gauge(DIMS)                                         # off the group: the accept has something to do
 g = np.ascontiguousarray(np.concatenate([sl(noisy, rank), sl(noisy, rank + 1)[:XYZ], sl(noisy, rank - 1)[V - XYZ:]])) if world > 1 else noisy
 VPR = g.shape[0]
-gptr = stub.stub_init_rank(T, L, L, L, world, rank)
-C.memmove(gptr, g.ctypes.data_as(VP), g.nbytes)
-stub.stub_boundary(0.13, 1.0, 0.0, 0.0, 0.0)
+gptr = hostprog.init_lattice(stub, T, L, L, L, g, 0.13, (1.0, 0.0, 0.0, 0.0), rank=(world, rank))
 stub.stub_set_mu(0.02)
 if world > 1:
     d.tmlqcd_hip_comm_init_shm(job.encode())

@@ -8,19 +8,18 @@ with host arrays, assign_mul_add_mul_add_mul_add_mul_r, Ptilde_ndpsi with Qsq = 
 runs the same calls through the core library and prints the largest absolute differences as one JSON line (they must be 0).
 Mode "exact_poly" sets phmc_exact_poly = 1 and calls tmlqcd_hip_ndpoly_acc, which must not return."""
 import ctypes as C
-import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
+from tests.hostprog import HF  # noqa: E402
 from tests.util import random_gauge, random_spinor  # noqa: E402
 
-VP, dbl, INT = C.c_void_p, C.c_double, C.c_int
+VP, dbl = C.c_void_p, C.c_double
 GLOBALS = """
 double g_mubar = 0.0, g_epsbar = 0.0, phmc_invmaxev = 1.0, phmc_cheb_evmin = 0.0, phmc_cheb_evmax = 1.0;
 int phmc_exact_poly = 0;
@@ -32,55 +31,19 @@ KAPPA = 0.125
 N_POLY = 5
 
 
-class HF(C.Structure):        # hamiltonian_field.h:26-32
-    _fields_ = [("gaugefield", VP), ("momenta", VP), ("derivative", VP), ("update_gauge_copy", INT), ("traj_counter", INT)]
-
-
 def main(mode):
-    tmp = tempfile.mkdtemp()
-    host, extra = os.path.join(tmp, "libhost.so"), os.path.join(tmp, "libpolyglobals.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", host, os.path.join(ROOT, "tests", "host_stub", "globals.c"), "-lm"])
-    src = os.path.join(tmp, "poly.c")
-    open(src, "w").write(GLOBALS)
-    subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-o", extra, src])
-    stub = C.CDLL(host, mode=C.RTLD_GLOBAL)
-    pg = C.CDLL(extra, mode=C.RTLD_GLOBAL)
-    d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-    stub.stub_init.restype = VP
-    stub.stub_init.argtypes = [INT] * 4
-    stub.stub_boundary.argtypes = [dbl] * 5
-    stub.stub_set_mu.argtypes = [dbl]
-    stub.stub_calloc.restype = VP
-    stub.stub_calloc.argtypes = [C.c_size_t]
-    pg.poly_set.argtypes = [dbl] * 5
-    pg.poly_set_exact.argtypes = [INT]
+    stub, pg, d = hostprog.load(extra_c=GLOBALS, extra_prototypes={"poly_set": (None, [dbl] * 5), "poly_set_exact": (None, [C.c_int])})
     pd_ = C.POINTER(dbl)
-    d.tmlqcd_hip_set_residency.argtypes = [INT]
-    d.assign_mul_add_mul_add_mul_add_mul_r.restype = None
-    d.assign_mul_add_mul_add_mul_add_mul_r.argtypes = [VP] * 4 + [dbl] * 4 + [INT]
-    d.Ptilde_ndpsi.restype = None
-    d.Ptilde_ndpsi.argtypes = [VP, VP, pd_, INT, VP, VP, VP]
-    d.tmlqcd_hip_ndpoly_derivative.argtypes = [C.POINTER(HF), VP, VP, pd_, INT, dbl, dbl]
-    d.tmlqcd_hip_ndpoly_heatbath.argtypes = [VP, VP, pd_, INT, dbl, dbl, pd_, INT, dbl, pd_]
-    d.tmlqcd_hip_ndpoly_acc.argtypes = [VP, VP, pd_, INT, dbl, dbl, pd_, pd_, INT, dbl, dbl, pd_]
-
     T = L = 4
     V = T * L ** 3
     N = V // 2
     gauge = random_gauge(97, V)
-    g = stub.stub_init(T, L, L, L)
-    C.memmove(g, gauge.ctypes.data, gauge.nbytes)
-    stub.stub_boundary(KAPPA, 0.0, 0.0, 0.0, 0.0)
+    hostprog.init_lattice(stub, T, L, L, L, gauge, KAPPA)
     stub.stub_set_mu(0.0)
     pg.poly_set(MUBAR, EPSBAR, INVMAXEV, EVMIN, 1.0)
-    d.tmlqcd_hip_set_residency(0)
-
-    def arr(init=None):   # page-aligned host arrays, as a host program's own fields
-        p = stub.stub_calloc(N * 24 * 8)
-        a = np.frombuffer((dbl * (N * 24)).from_address(p), dtype=np.float64).reshape(N, 4, 3, 2)
-        if init is not None:
-            a[:] = init
-        return a, p
+    d.tmlqcd_hip_set_residency(0)                     # coherent only, and tmlqcd_hip_finalize() ends this program
+    fields = hostprog.HostFields(stub, d, "coherent")
+    arr = lambda init=None: fields.arr(N, init)
 
     th = np.pi * (np.arange(N_POLY - 1) + 0.5) / (N_POLY - 1)
     roots = np.concatenate([0.8 * np.exp(1j * th), 0.8 * np.exp(-1j * th[::-1])])   # z[2n-3-k] = conj(z[k]), as in the reference's root files
@@ -143,8 +106,7 @@ def main(mode):
     errs["ndpoly_acc_energy1"] = abs(e1.value - e1c)
     lat.close()
     d.tmlqcd_hip_finalize()
-    print(json.dumps({"errs": errs, "corrections": steps, "corrections_core": steps_c}))
-    sys.stdout.flush()
+    hostprog.emit({"errs": errs, "corrections": steps, "corrections_core": steps_c})
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Child process of tests/test_gpu_ratcor_dropin.py.
 
-A host program in miniature, as tests/ndsw_dropin_child.py: the stub globals of tests/host_stub/globals.c (with its sw / sw_inv arrays)
+A host program in miniature (tests/hostprog.py): the stub globals of tests/host_stub/globals.c (with its sw / sw_inv arrays)
 plus the doublet's globals are loaded first, then libtmlqcd_dropin.so.  Calls the eight symbols tmlqcd_hip_{ratcor, cloverratcor,
 ndratcor, ndcloverratcor}_{heatbath, acc} on host arrays in the residency mode given on the command line, with g_mu != 0 (the
 single-flavour bodies run at twisted mass 0 and leave g_mu alone), the clover types after tmlqcd_hip_sw_term and tmlqcd_hip_sw_invert(EE,
@@ -10,57 +10,22 @@ ref_ratcor_scalars_4x4.json) as one JSON line: relative for energies and fields,
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests.nd_dropin_child import ND_GLOBALS  # noqa: E402
+from tests import hostprog  # noqa: E402
+from tests.hostprog import rel_max  # noqa: E402
 
-VP, dbl, cint = C.c_void_p, C.c_double, C.c_int
+dbl, cint = C.c_double, C.c_int
 G_MU = 0.17
 ORDER = ("ratcor", "ndratcor", "cloverratcor", "ndcloverratcor")         # the single-flavour clover type before sw_invert_nd overwrites sw_inv
 
 
 def main(mode):
-    tmp = tempfile.mkdtemp()
-    host, nd = os.path.join(tmp, "libhost.so"), os.path.join(tmp, "libndglobals.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", host, os.path.join(ROOT, "tests", "host_stub", "globals.c"), "-lm"])
-    src = os.path.join(tmp, "nd.c")
-    open(src, "w").write(ND_GLOBALS)
-    subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-o", nd, src])
-    stub = C.CDLL(host, mode=C.RTLD_GLOBAL)
-    ndg = C.CDLL(nd, mode=C.RTLD_GLOBAL)
-    d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-    stub.stub_init.restype = VP
-    stub.stub_init.argtypes = [cint] * 4
-    stub.stub_boundary.argtypes = [dbl] * 5
-    stub.stub_set_mu.argtypes = [dbl]
-    stub.stub_get_mu.restype = dbl
-    stub.stub_calloc.restype = VP
-    stub.stub_calloc.argtypes = [C.c_size_t]
-    stub.stub_init_clover.restype = VP
-    stub.stub_init_clover.argtypes = [cint]
-    ndg.nd_set.argtypes = [dbl] * 3
-    pd_, pi_ = C.POINTER(dbl), C.POINTER(cint)
-    d.tmlqcd_hip_sw_term.argtypes = [dbl, dbl]
-    d.tmlqcd_hip_sw_invert.argtypes = [cint, dbl]
-    d.sw_invert_nd.argtypes = [dbl]
-    d.tmlqcd_hip_sw_invert_failures.restype = cint
-    d.tmlqcd_hip_set_residency.argtypes = [cint]
-    d.tmlqcd_hip_sync_to_host.argtypes = [VP]
-    for t in ("ratcor", "cloverratcor"):
-        for b in ("heatbath", "acc"):
-            f = getattr(d, "tmlqcd_hip_%s_%s" % (t, b))
-            f.restype, f.argtypes = cint, [VP, pd_, pd_, dbl, cint, cint, dbl, cint, pd_, pi_]
-    for t in ("ndratcor", "ndcloverratcor"):
-        for b in ("heatbath", "acc"):
-            f = getattr(d, "tmlqcd_hip_%s_%s" % (t, b))
-            f.restype, f.argtypes = cint, [VP, VP, pd_, pd_, dbl, cint, cint, dbl, cint, pd_, pi_]
-
+    stub, ndg, d = hostprog.load(extra_c=hostprog.ND_GLOBALS)
     gold = os.path.join(ROOT, "tests", "golden")
     arrs = np.load(os.path.join(gold, "ref_ratcor_4x4.npz"))
     base = np.load(os.path.join(gold, "ref_nd_4x4.npz"))
@@ -68,60 +33,43 @@ def main(mode):
     T = L = 4
     V = T * L ** 3
     N = V // 2
-    g = stub.stub_init(T, L, L, L)
-    gauge = np.ascontiguousarray(base["gauge"])
-    C.memmove(g, gauge.ctypes.data, gauge.nbytes)
-    stub.stub_boundary(s["kappa"], 0.0, 0.0, 0.0, 0.0)
+    hostprog.init_lattice(stub, T, L, L, L, base["gauge"], s["kappa"])
     stub.stub_set_mu(G_MU)
     ndg.nd_set(s["mubar"], s["epsbar"], s["invmaxev"])
     stub.stub_init_clover(1)                                            # the host program's sw / sw_inv (init_sw_fields)
-    d.tmlqcd_hip_set_residency({"coherent": 0, "resident": 1}[mode])
-
-    def arr(init):
-        p = stub.stub_calloc(N * 24 * 8)
-        a = np.frombuffer((dbl * (N * 24)).from_address(p), dtype=np.float64).reshape(N, 4, 3, 2)
-        a[:] = init
-        return a, p
-
-    def host_copy(a):
-        if mode == "resident":
-            d.tmlqcd_hip_sync_to_host(a[1])
-        return a[0].copy()
-
     errs = {}
-    clover_made = False
-    for name in ORDER:
-        t = s["types"][name]
-        c = t["fit"]
-        if t["sw"] and not clover_made:
-            d.tmlqcd_hip_sw_term(s["kappa"], s["c_sw"])
-            d.tmlqcd_hip_sw_invert(0, 0.0)
-            errs["sw_invert_failures"] = float(d.tmlqcd_hip_sw_invert_failures())
-            clover_made = True
-        if t["sw"] and t["nd"]:
-            d.sw_invert_nd(s["mubar"] ** 2 - s["epsbar"] ** 2)
-            errs["sw_invert_nd_failures"] = float(d.tmlqcd_hip_sw_invert_failures())
-        n = c["np"]
-        mu, rmu = (dbl * n)(*c["mu"]), (dbl * n)(*c["rmu"])
-        pf = [arr(base[k]) for k in (("k_s", "k_c") if t["nd"] else ("k_s",))]
-        sfx = ("_up", "_dn")[:len(pf)]
-        e, napp = dbl(), cint()
-        rest = (mu, rmu, c["A"], n, c["max_iter"], c["accprec"], c["rel_prec"], C.byref(e), C.byref(napp))
-        it = getattr(d, "tmlqcd_hip_%s_heatbath" % name)(*[p[1] for p in pf], *rest)
-        hb = c["heatbath"]
-        errs[name + "_heatbath_iters"] = abs(it - hb["iters"])
-        errs[name + "_heatbath_napp"] = abs(napp.value - hb["napp"])
-        errs[name + "_energy0"] = abs(e.value - hb["energy0"]) / hb["energy0"]
-        errs[name + "_pf"] = max(float(np.abs(host_copy(p) - arrs[name + "_pf" + x]).max() / np.abs(arrs[name + "_pf" + x]).max()) for p, x in zip(pf, sfx))
-        it = getattr(d, "tmlqcd_hip_%s_acc" % name)(*[p[1] for p in pf], *rest)
-        ac = c["acc"]
-        errs[name + "_acc_iters"] = abs(it - ac["iters"])
-        errs[name + "_acc_napp"] = abs(napp.value - ac["napp"])
-        errs[name + "_energy1"] = abs(e.value - ac["energy1"]) / abs(ac["energy1"])
-    errs["g_mu_moved"] = abs(stub.stub_get_mu() - G_MU)
-    d.tmlqcd_hip_set_residency(0)
-    print(json.dumps(errs))
-    sys.stdout.flush()
+    with hostprog.HostFields(stub, d, mode, modes=("coherent", "resident")) as hf:
+        clover_made = False
+        for name in ORDER:
+            t = s["types"][name]
+            c = t["fit"]
+            if t["sw"] and not clover_made:
+                d.tmlqcd_hip_sw_term(s["kappa"], s["c_sw"])
+                d.tmlqcd_hip_sw_invert(0, 0.0)
+                errs["sw_invert_failures"] = float(d.tmlqcd_hip_sw_invert_failures())
+                clover_made = True
+            if t["sw"] and t["nd"]:
+                d.sw_invert_nd(s["mubar"] ** 2 - s["epsbar"] ** 2)
+                errs["sw_invert_nd_failures"] = float(d.tmlqcd_hip_sw_invert_failures())
+            n = c["np"]
+            mu, rmu = (dbl * n)(*c["mu"]), (dbl * n)(*c["rmu"])
+            pf = [hf.arr(N, base[k]) for k in (("k_s", "k_c") if t["nd"] else ("k_s",))]
+            sfx = ("_up", "_dn")[:len(pf)]
+            e, napp = dbl(), cint()
+            rest = (mu, rmu, c["A"], n, c["max_iter"], c["accprec"], c["rel_prec"], C.byref(e), C.byref(napp))
+            it = getattr(d, "tmlqcd_hip_%s_heatbath" % name)(*[p[1] for p in pf], *rest)
+            hb = c["heatbath"]
+            errs[name + "_heatbath_iters"] = abs(it - hb["iters"])
+            errs[name + "_heatbath_napp"] = abs(napp.value - hb["napp"])
+            errs[name + "_energy0"] = abs(e.value - hb["energy0"]) / hb["energy0"]
+            errs[name + "_pf"] = max(rel_max(hf.copy(p), arrs[name + "_pf" + x]) for p, x in zip(pf, sfx))
+            it = getattr(d, "tmlqcd_hip_%s_acc" % name)(*[p[1] for p in pf], *rest)
+            ac = c["acc"]
+            errs[name + "_acc_iters"] = abs(it - ac["iters"])
+            errs[name + "_acc_napp"] = abs(napp.value - ac["napp"])
+            errs[name + "_energy1"] = abs(e.value - ac["energy1"]) / abs(ac["energy1"])
+        errs["g_mu_moved"] = abs(stub.stub_get_mu() - G_MU)
+    hostprog.emit(errs)
 
 
 if __name__ == "__main__":

@@ -7,9 +7,7 @@ name and with host arrays:
 into fresh arrays, then the lexicographic forms (r == NULL) and tmlqcd_hip_source_spinor_field_point_from_file, and prints what it
 found as one JSON line."""
 import ctypes as C
-import json
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -17,58 +15,24 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
 from tests import spinor_io_restate as sr  # noqa: E402
 from tmlqcd_amd import synthetic as syn  # noqa: E402
 
-VP, dbl, INT = C.c_void_p, C.c_double, C.c_int
+VP = C.c_void_p
 DIMS = (4, 4, 4, 6)
 SENTINEL = -7.25
 
 
-def main(mode):
-    tmp = tempfile.mkdtemp()
-    host = os.path.join(tmp, "libhost.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", host, os.path.join(ROOT, "tests", "host_stub", "globals.c"), "-lm"])
-    stub = C.CDLL(host, mode=C.RTLD_GLOBAL)
-    d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-    stub.stub_init.restype = VP
-    stub.stub_init.argtypes = [INT] * 4
-    stub.stub_boundary.argtypes = [dbl] * 5
-    stub.stub_set_mu.argtypes = [dbl]
-    stub.stub_calloc.restype = VP
-    stub.stub_calloc.argtypes = [C.c_size_t]
-    d.tmlqcd_hip_set_residency.argtypes = [INT]
-    d.tmlqcd_hip_sync_to_host.argtypes = [VP]
-    d.tmlqcd_hip_source_spinor_field.restype = None
-    d.tmlqcd_hip_source_spinor_field.argtypes = [VP, VP, INT, INT]
-    d.tmlqcd_hip_source_spinor_field_point_from_file.restype = None
-    d.tmlqcd_hip_source_spinor_field_point_from_file.argtypes = [VP, VP, INT, INT, INT]
-    d.cg_her.restype = INT
-    d.cg_her.argtypes = [VP, VP, INT, dbl, INT, INT, VP]
-    d.Qtm_pm_psi.restype = None
-    d.Qtm_pm_psi.argtypes = [VP, VP]
-    d.read_spinor.restype = INT
-    d.read_spinor.argtypes = [VP, VP, C.c_char_p, INT]
-    d.tmlqcd_hip_write_spinor.restype = INT
-    d.tmlqcd_hip_write_spinor.argtypes = [C.c_char_p, INT, C.POINTER(VP), C.POINTER(VP), INT, INT]
-    d.tmlqcd_hip_write_lime_message.restype = INT
-    d.tmlqcd_hip_write_lime_message.argtypes = [C.c_char_p, INT, C.c_char_p, C.c_char_p, INT, INT]
-    d.tmlqcd_hip_transfer_counts.argtypes = [C.POINTER(C.c_ulong)]
-
+def main(mode, tmp):
+    stub, _, d = hostprog.load()
     V = sr.volume(DIMS)
     N = V // 2
-    gauge = np.ascontiguousarray(syn.gauge_field(31, *DIMS)[:V])
-    g = stub.stub_init(*DIMS)
-    C.memmove(g, gauge.ctypes.data, gauge.nbytes)
-    stub.stub_boundary(0.125, 0., 0., 0., 0.)
+    hostprog.init_lattice(stub, *DIMS, syn.gauge_field(31, *DIMS)[:V], 0.125)
     stub.stub_set_mu(0.05)
-    d.tmlqcd_hip_set_residency({"coherent": 0, "resident": 1}[mode])
-
-    def arr(fill=0.0):
-        p = stub.stub_calloc(V * 24 * 8)
-        a = np.frombuffer((dbl * (V * 24)).from_address(p), dtype=np.float64).reshape(V, 4, 3, 2)
-        a[:] = fill
-        return a, p
+    hf = hostprog.HostFields(stub, d, mode, modes=("coherent", "resident"))
+    d.tmlqcd_hip_set_residency(hostprog.MODES[mode])   # (no way back at the end: tmlqcd_hip_finalize() ends this program)
+    arr = lambda fill=0.0: hf.arr(V, fill)
 
     def counts():
         n = (C.c_ulong * 4)()
@@ -137,8 +101,9 @@ def main(mode):
         d.tmlqcd_hip_sync_to_host(back[1])
     out["lex_read_ok"] = bool(np.array_equal(back[0], lex[0]))
     d.tmlqcd_hip_finalize()
-    print(json.dumps(out))
+    hostprog.emit(out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    with tempfile.TemporaryDirectory() as tmp_dir:      # prop.lime and lex.lime
+        main(sys.argv[1], tmp_dir)

@@ -1,23 +1,16 @@
 """GPU: bicgstab_complex and its two linalg symbols through the drop-in, in a process of their own (tests/bicg_dropin_child.py): host
 arrays, coherent and lazy residency, the device-resident path for the operators the library knows and the host loop for a foreign f."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from tests.hostprog import run_child
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("mode", ["coherent", "lazy"])
 def test_dropin_symbols(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bicg_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_child("bicg_dropin_child.py", mode)
     print(out)
     for k, v in out["linalg"].items():
         assert v is True or v <= 8, (k, v)                     # eps times the sum of the magnitudes of an element's terms, as tests/test_gpu_bicg.py

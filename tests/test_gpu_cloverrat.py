@@ -2,22 +2,17 @@
 the CPU oracle (tests/cloverrat_restate.py: Qsw_plus_psi, Hopping_Matrix + clover_inv, deriv_Sb, sw_spinor_eo, sw_deriv, sw_all from
 oracle/tm_oracle.c), on 4^4 and a ragged shape; the refusals; one molecular-dynamics trajectory with everything resident; the drop-in
 symbols on host arrays.  Mirrors tests/test_gpu_ndcloverrat.py."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import cloverrat_restate as cr
 from tests import ndsw_restate as sw
+from tests.hostprog import run_child
 from tests.util import TOL, random_gauge, random_spinor, rel_err
 from tmlqcd_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KAPPA, C_SW, THETA = sw.KAPPA, sw.C_SW, sw.THETA
 SHAPES = sw.FORCE_SHAPES
 MU3, RMU3 = [0.21, 0.6, 1.7], [0.05, 0.4, 1.3]
@@ -284,10 +279,7 @@ def test_trajectory_conserves_its_hamiltonian_to_second_order_and_is_reversible(
 # ---------------------------------------------------------------- drop-in
 @pytest.mark.parametrize("mode", ["coherent", "resident"])
 def test_dropin_symbols(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "cloverrat_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    errs = json.loads(r.stdout.strip().splitlines()[-1])
+    errs = run_child("cloverrat_dropin_child.py", mode)
     print(errs)
     assert {"cloverrat_derivative", "cloverrat_derivative_iters", "cloverrat_acc", "cloverrat_heatbath", "cloverrat_heatbath_energy"} <= set(errs)
     for k, v in errs.items():

@@ -7,8 +7,6 @@ Tolerances: TOL relative to the sum of |terms| for a scalar product, TOL relativ
 cond(G) * TOL for whatever has passed the small solve -- cond(G) from the fixture, or from the restatement where there is none."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import pytest
 from oracle.nd_restate import cplx, real
 from oracle.oraclebind import Oracle
 from tests import csg_restate
+from tests.hostprog import run_child
 from tests.util import TOL, random_gauge, random_spinor, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -250,10 +249,7 @@ def test_solve_iterations(gold, L):
 # ---- 7. the drop-in symbols, in a process of their own
 @pytest.mark.parametrize("mode", ["coherent", "resident"])
 def test_dropin_symbols(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "csg_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_child("csg_dropin_child.py", mode)
     print(out)
     assert out["index_sequence_ok"] and out["zero_trials_ok"]
     assert out["clover_iters"] == out["clover_iters_core"] and len(out["clover_iters"]) == 3
@@ -263,7 +259,6 @@ def test_dropin_symbols(mode):
 
 
 def test_dropin_refuses_a_list_of_21():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "csg_dropin_child.py"), "too_long"], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    r = run_child("csg_dropin_child.py", "too_long", check=False)
     assert r.returncode not in (0, -6, -11, 134, 139), (r.returncode, r.stderr[-2000:])
     assert "more than 20 vectors" in r.stderr

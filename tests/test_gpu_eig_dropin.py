@@ -6,31 +6,26 @@ The reference is the dense spectrum of the CPU oracle's operators, computed by t
 residual is at most prec = 1e-9 there, so |theta - lambda| <= prec + 1e-12 lambda_max (the bound of tests/test_gpu_eig.py with
 the residual replaced by its own bound, because these entry points return no residual).
 """
-import json
-import os
-import subprocess
-import sys
-
 import pytest
+
+from tests.hostprog import last_json, run_child
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PREC = 1e-9
 WARN_MAX = "Warning: largest eigenvalue for monomial ndpoly_heavy larger than upper bound!"
 WARN_MIN = "Warning: smallest eigenvalue for monomial ndpoly_heavy smaller than lower bound!"
 
 
 def _child(mode):
-    return subprocess.run([sys.executable, os.path.join(ROOT, "tests", "eig_dropin_child.py"), mode], cwd=ROOT, stdout=subprocess.PIPE,
-                          stderr=subprocess.PIPE, text=True, timeout=300)
+    return run_child("eig_dropin_child.py", mode, check=False)      # (the tests read its stderr too)
 
 
 @pytest.fixture(scope="module", params=["lazy", "resident"])
 def run(request):
     r = _child(request.param)
     assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads(r.stdout.strip().splitlines()[-1]), r.stderr
+    return last_json(r), r.stderr
 
 
 def test_eigenvalues_bi_returns_the_first_eigenvalue_and_the_number_converged(run):

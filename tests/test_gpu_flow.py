@@ -15,14 +15,13 @@ reference by 2.7e-15 at most (bound 1.7e-14), P by 1.1e-16 (3.2e-15), E by 8.9e-
 shapes the links by 1.4e-15 at most after 2 steps; the integrator-order ratio is 7.86."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import flow_restate as fr
 from tests import gauge_restate as gr
+from tests.hostprog import run_child
 from tests.util import random_gauge
 
 pytestmark = pytest.mark.gpu
@@ -255,10 +254,7 @@ def test_through_the_drop_in(mode, tmp_path, fx4):
     device-side update_gauge, the moved links are the ones measured while the host's stay behind."""
     s = fx4[0]
     b = Bounds(s)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "flow_dropin_child.py"), mode], cwd=str(tmp_path),
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_child("flow_dropin_child.py", mode, cwd=str(tmp_path))
     print(out)
     b.check("drop-in resident links", (out["E"], out["Q"]), (s["resident"]["E"], s["resident"]["Q"]))
     text = open(os.path.join(str(tmp_path), "gradflow.%06d" % s["traj"])).read()
@@ -282,7 +278,6 @@ def test_through_the_drop_in(mode, tmp_path, fx4):
 
 def test_drop_in_ends_the_program_on_an_unopenable_file(tmp_path):
     """as the reference's fatal_error does: a message and a non-zero exit status, no abort, no fault"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "flow_dropin_child.py"), "unopenable"], cwd=str(tmp_path),
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    r = run_child("flow_dropin_child.py", "unopenable", cwd=str(tmp_path), check=False)
     assert r.returncode not in (0, -6, -11, 134, 139), (r.returncode, r.stderr[-2000:])
     assert "Couldn't open gradflow.000009" in r.stderr and "returned without" not in r.stdout

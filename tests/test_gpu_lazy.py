@@ -8,6 +8,7 @@ import time
 import numpy as np
 import pytest
 
+from tests.hostprog import run_child
 from tests.util import TOL, random_gauge, random_spinor, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -319,11 +320,7 @@ def test_faults_of_the_host_program_reach_its_own_handler():
     """VERDICT r2 item 7 (chain test): a host program with a SIGSEGV handler of its own, installed BEFORE the lazy mode's -- its faults
     (a guard page) must still reach it while fields are stale and watched, and the library's own faults must be served as before.
     A process of its own: in this one the library's handler is long installed (tests/lazy_chain_child.py)."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "lazy_chain_child.py")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    r = run_child("lazy_chain_child.py", cwd=None, check=False)
     assert r.returncode == 0 and r.stdout.strip().startswith("OK"), (r.returncode, r.stdout[-500:], r.stderr[-1500:])
 
 
@@ -334,14 +331,10 @@ def test_arrays_that_cannot_be_watched(where, why):
     results the coherent mode's, no fault served.  And with the test hook that watches them anyway, the first fault ends the process
     with a message within seconds -- it fails loudly, it does not hang (tests/lazy_unwatchable_child.py)."""
     import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    child = [sys.executable, os.path.join(root, "tests", "lazy_unwatchable_child.py"), where]
     env = dict(os.environ, TMLQCD_HIP_LAZY_DEBUG="1")
     env.pop("TMLQCD_HIP_LAZY_FORCE_WATCH", None)
-    r = subprocess.run(child, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    r = run_child("lazy_unwatchable_child.py", where, cwd=None, env=env, check=False)
     assert r.returncode == 0 and r.stdout.strip().startswith("OK") and r.stdout.strip().endswith("faults served 0"), (r.returncode, r.stdout[-500:], r.stderr[-1500:])
     assert "not watched, copied per call: " + why in r.stderr, r.stderr[-1500:]
-    r = subprocess.run(child, env=dict(env, TMLQCD_HIP_LAZY_FORCE_WATCH="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    r = run_child("lazy_unwatchable_child.py", where, cwd=None, env=dict(env, TMLQCD_HIP_LAZY_FORCE_WATCH="1"), timeout=120, check=False)
     assert r.returncode == 1 and "must not be watched" in r.stderr and "OK" not in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-1500:])

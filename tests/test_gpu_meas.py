@@ -15,14 +15,13 @@ Measured on one MI355X (also in the header of profiles/r13_meas_speed.log): over
 the Polyakov loop 6e-4 and the oriented plaquettes 1.3e-3 of theirs."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import gauge_restate as gr
 from tests import meas_restate as mr
+from tests.hostprog import last_json, run_child
 from tests.util import random_gauge, random_spinor
 
 pytestmark = pytest.mark.gpu
@@ -314,8 +313,7 @@ def test_oriented_plaquettes_shapes(dims):
 
 # ------------------------------------------------------------------------------------------------ drop-in
 def _child(mode, cwd):
-    return subprocess.run([sys.executable, os.path.join(ROOT, "tests", "meas_dropin_child.py"), mode], cwd=str(cwd),
-                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    return run_child("meas_dropin_child.py", mode, cwd=str(cwd), check=False)      # (the tests read its stderr too)
 
 
 @pytest.mark.parametrize("mode", ["coherent", "resident"])
@@ -327,7 +325,7 @@ def test_through_the_drop_in(mode, tmp_path):
     V = int(np.prod(dims))
     r = _child(mode, tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = last_json(r)
     print(out)
     d0, d3 = s["slices"]["dir0"], s["slices"]["dir3"]
     for k in ("pp", "pa", "p4"):
@@ -373,5 +371,5 @@ def test_drop_in_on_unopenable_files(tmp_path):
     b.mkdir()
     r = _child("unopenable_polyakov", b)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert json.loads(r.stdout.strip().splitlines()[-1]) == {"rc": -1}
+    assert last_json(r) == {"rc": -1}
     assert "Could not open file polyakovloop_dir3 for writing" in r.stderr

@@ -1,23 +1,16 @@
 """GPU: the drop-in cg_mms_tm (include/tmlqcd_dropin.h) with the solver parameters the rat monomial and invert_eo.c build, in
 every residency mode (one child process each, tests/mms_dropin_child.py), and the generic path for an M_psi the library does
 not know, against tests/golden/ref_mms_4x4.npz; cg_her's generic path in the same modes against tests/golden/ref_fields_4x4.npz."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
+from tests.hostprog import run_child
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("mode", ["coherent", "lazy", "resident"])
 def test_dropin_cg_mms_tm_in_every_residency_mode(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mms_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_child("mms_dropin_child.py", mode)
     for name in ("qtm", "qpm_full", "qtm_generic"):
         assert out[name] < 1e-9, (name, out[name])
         assert out[name + "_iters"] <= 1, (name, out)

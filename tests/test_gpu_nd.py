@@ -6,12 +6,11 @@ mixing pass ("nd_fused" 0).
 """
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.hostprog import run_child
 from tests.util import TOL, random_gauge, random_spinor, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -156,10 +155,7 @@ def test_t_split_context_is_refused():
 
 @pytest.mark.parametrize("mode", ["coherent", "lazy", "resident"])
 def test_dropin_symbols_in_every_residency_mode(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "nd_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    errs = json.loads(r.stdout.strip().splitlines()[-1])
+    errs = run_child("nd_dropin_child.py", mode)
     for k, v in errs.items():
         if k.endswith("_iters"):
             assert v <= 1, (k, v)

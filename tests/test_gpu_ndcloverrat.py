@@ -2,21 +2,16 @@
 statements restated over the CPU oracle (tests/ndsw_restate.py: deriv_Sb, sw_spinor_eo, sw_all from oracle/tm_oracle.c), on 4^4
 and a ragged shape; the refusals; one molecular-dynamics trajectory with everything resident; the drop-in symbols on host arrays.
 tests/test_ndsw_restate.py pins the restatement to the reference's own outputs."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import ndsw_restate as sw
+from tests.hostprog import run_child
 from tests.util import TOL, random_gauge, random_spinor, rel_err
 from tmlqcd_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KAPPA, C_SW, THETA = sw.KAPPA, sw.C_SW, sw.THETA
 MUBAR, EPSBAR, INVMAXEV = sw.FIXTURE
 MSHIFT = MUBAR * MUBAR - EPSBAR * EPSBAR
@@ -275,10 +270,7 @@ def test_trajectory_conserves_its_hamiltonian_to_second_order_and_is_reversible(
 # ---------------------------------------------------------------- drop-in
 @pytest.mark.parametrize("mode", ["coherent", "resident"])
 def test_dropin_symbols(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ndsw_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    errs = json.loads(r.stdout.strip().splitlines()[-1])
+    errs = run_child("ndsw_dropin_child.py", mode)
     assert {"sw_invert_nd_failures", "core_sw_invert_nd_failures", "sw_invert_nd_host_copy", "Qsw_pm_ndpsi", "Qsw_pm_ndpsi_aliased", "cg_mms_tm_nd", "ndcloverrat_derivative"} <= set(errs)
     for k, v in errs.items():
         if k.endswith("_iters"):

@@ -6,8 +6,6 @@ Bounds against the fixture: 8 x the deviation the restatement itself has from th
 below TOL) -- the chain of 48 factors and the Clenshaw sums amplify rounding, the GPU contracts to FMA and sums in another order."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ import pytest
 from oracle.nd_restate import cplx, hop_over, real
 from tests import ndsw_restate as sw
 from tests import poly_restate
+from tests.hostprog import run_child
 from tests.poly_restate import gpu_bound, roots_of
 from tests.util import TOL, random_gauge, random_spinor, rel_err
 from tmlqcd_amd import synthetic as syn
@@ -405,15 +404,8 @@ def test_refusals_leave_the_accumulator_alone():
 
 
 # ---------------------------------------------------------------- 7: drop-in
-def _child(mode):
-    return subprocess.run([sys.executable, os.path.join(ROOT, "tests", "poly_dropin_child.py"), mode], cwd=ROOT,
-                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-
-
 def test_drop_in_symbols_equal_the_core_results():
-    r = _child("coherent")
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_child("poly_dropin_child.py", "coherent")
     print(out)
     for k, v in out["errs"].items():
         assert v == 0.0, k
@@ -421,7 +413,7 @@ def test_drop_in_symbols_equal_the_core_results():
 
 
 def test_drop_in_ends_with_a_message_when_phmc_exact_poly_is_set():
-    r = _child("exact_poly")
+    r = run_child("poly_dropin_child.py", "exact_poly", check=False)
     assert r.returncode not in (0, -6, -11, 134, 139), (r.returncode, r.stderr[-2000:])
     assert "phmc_exact_poly == 1" in r.stderr
     assert "returned" not in r.stdout

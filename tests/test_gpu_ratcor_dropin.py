@@ -3,12 +3,11 @@ called from a host stub on host fields, in both residency modes, against the ref
 fresh child process per mode (tests/ratcor_dropin_child.py), as the other *_dropin_child.py.  Bounds: tests/ratcor_restate.py::gpu_bound."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 from tests import ratcor_restate as rr
+from tests.hostprog import run_child
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,10 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("mode", ["coherent", "resident"])
 def test_dropin_symbols(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ratcor_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    errs = json.loads(r.stdout.strip().splitlines()[-1])
+    errs = run_child("ratcor_dropin_child.py", mode)
     print(errs)
     s = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_ratcor_scalars_4x4.json")))
     assert errs["sw_invert_failures"] == 0.0 and errs["sw_invert_nd_failures"] == 0.0

@@ -1,20 +1,17 @@
 """GPU: the drop-in's propagator / source I/O in a process of its own (tests/spinor_io_dropin_child.py): point source, cg_her,
 tmlqcd_hip_write_spinor, read_spinor into fresh arrays -- in coherent and in resident mode, e/o pairs and lexicographic fields."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from tests.hostprog import run_child
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("mode", ["coherent", "resident"])
 def test_source_solve_write_read(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "spinor_io_dropin_child.py"), mode], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    r = run_child("spinor_io_dropin_child.py", mode, check=False)      # (the library's prints are read too, and end up after the JSON line)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     print(out)

@@ -11,7 +11,6 @@ g_update_gauge_copy and scribbled on its links, the second accepted -- with what
   drawn on the host (one upload per trajectory); accept and reject themselves move nothing and leave g_gauge_field alone until
   tmlqcd_hip_sync_gauge_to_host.
 The transfer counts are the library's own (tmlqcd_hip_transfer_counts: gauge up, gauge down, momenta up, momenta down)."""
-import json
 import os
 import subprocess
 import sys
@@ -20,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests import traj_restate as tj
+from tests.hostprog import last_json, run_child
 from tests.traj_restate import U53 as U, chain_diff, chain_energy, chain_norms
 
 pytestmark = pytest.mark.gpu
@@ -35,10 +35,9 @@ def within(got, want, n):
 def runs():
     out = {}
     for mode in ("coherent", "resident"):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "traj_dropin_child.py"), mode], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                           text=True, timeout=300)
+        r = run_child("traj_dropin_child.py", mode, cwd=None, check=False)
         assert r.returncode == 0, (mode, r.stderr[-3000:])
-        out[mode] = json.loads(r.stdout.strip().splitlines()[-1])
+        out[mode] = last_json(r)
         print(mode, out[mode])
     return out
 

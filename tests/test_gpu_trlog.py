@@ -4,7 +4,6 @@ tests/test_gpu_md_trajectory.py with its tr-log taken on the device, and the dro
 T-split ranks.
 
 Bound: |got - want| <= TOL * sum over the sites of |per-site term| -- the project's fp64 tolerance on the natural scale of the sum."""
-import json
 import os
 import subprocess
 import sys
@@ -14,6 +13,7 @@ import pytest
 
 from tests import cloverrat_restate as cr
 from tests import ndsw_restate as sw
+from tests.hostprog import run_child
 from tests.test_gpu_md_trajectory import CloverDetTrajectory
 from tests.util import TOL, random_gauge
 
@@ -128,10 +128,7 @@ def _host_scale(lat, mu):
 
 # ---------------------------------------------------------------- drop-in
 def test_dropin_symbols():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "trlog_dropin_child.py")], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    errs = json.loads(r.stdout.strip().splitlines()[-1])
+    errs = run_child("trlog_dropin_child.py")
     print(errs)
     assert {"device_sw_trace_0_0", "device_sw_trace_1_0.23", "device_sw_trace_nd_0", "upload_sw_trace", "device_failures"} <= set(errs)
     for k, v in errs.items():

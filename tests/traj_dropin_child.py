@@ -12,60 +12,32 @@ with the six calls of the trajectory frame in the reference's order:
 and prints what it saw as one JSON line: host links, flags, the library's transfer counters around every step, the values with what
 the host's own loops give for them."""
 import ctypes as C
-import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import hostprog  # noqa: E402
 from tests import traj_restate as tj  # noqa: E402
+from tests.hostprog import HF  # noqa: E402
 from tests.util import random_spinor  # noqa: E402
 
-VP, dbl, INT = C.c_void_p, C.c_double, C.c_int
+VP, dbl = C.c_void_p, C.c_double
 DIMS = (4, 4, 4, 4)
 KAPPA, MU, BETA = 0.125, 0.25, 5.6
 NSTEPS, EPS = 2, 0.05
 EO, OE = 0, 1
 
 
-class HF(C.Structure):        # hamiltonian_field.h:26-32
-    _fields_ = [("gaugefield", VP), ("momenta", VP), ("derivative", VP), ("update_gauge_copy", INT), ("traj_counter", INT)]
-
-
 def main(mode):
     resident = mode == "resident"
     V = int(np.prod(DIMS))
     N = V // 2
-    tmp = tempfile.mkdtemp()
-    host = os.path.join(tmp, "libhost.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-fPIC", "-shared", "-o", host, os.path.join(ROOT, "tests", "host_stub", "globals.c"), "-lm"])
-    stub = C.CDLL(host, mode=C.RTLD_GLOBAL)
-    d = C.CDLL(os.path.join(ROOT, "tmlqcd_amd", "lib", "libtmlqcd_dropin.so"), mode=C.RTLD_GLOBAL)
-    stub.stub_init.restype = VP
-    stub.stub_init.argtypes = [INT] * 4
-    stub.stub_boundary.argtypes = [dbl] * 5
-    stub.stub_set_mu.argtypes = [dbl]
-    P = C.POINTER(HF)
-    for name, res, args in (("tmlqcd_hip_gauge_snapshot", None, [P]), ("tmlqcd_hip_moment_energy", dbl, [P]), ("tmlqcd_hip_gauge_snapshot_diff", dbl, [P]),
-                            ("tmlqcd_hip_accept_links", None, [P, INT]), ("tmlqcd_hip_reject_links", None, [P]),
-                            ("tmlqcd_hip_force_norms", None, [P, C.POINTER(dbl), C.POINTER(dbl)]), ("tmlqcd_hip_transfer_counts", None, [C.POINTER(C.c_ulong)]),
-                            ("tmlqcd_hip_update_gauge", None, [dbl, P]), ("tmlqcd_hip_update_momenta", None, [dbl, P]),
-                            ("tmlqcd_hip_sync_gauge_to_host", None, [P]), ("tmlqcd_hip_sync_momenta_to_host", None, [P]),
-                            ("tmlqcd_hip_flush_derivative", None, [P]), ("tmlqcd_hip_gauge_derivative", None, [P, dbl, dbl, dbl, INT, dbl]),
-                            ("deriv_Sb", None, [INT, VP, VP, P, dbl]), ("cg_her", INT, [VP, VP, INT, dbl, INT, INT, VP]),
-                            ("Qtm_plus_psi", None, [VP, VP]), ("Qtm_minus_psi", None, [VP, VP]), ("H_eo_tm_inv_psi", None, [VP, VP, INT, dbl]),
-                            ("Hopping_Matrix", None, [INT, VP, VP]), ("tmlqcd_hip_set_residency", None, [INT]), ("tmlqcd_hip_finalize", None, [])):
-        f = getattr(d, name)
-        f.restype, f.argtypes = res, args
-
+    stub, _, d = hostprog.load()
     g = tj.gauge(DIMS)
-    gptr = stub.stub_init(*DIMS)
-    C.memmove(gptr, g.ctypes.data, g.nbytes)
-    stub.stub_boundary(KAPPA, 0., 0., 0., 0.)
+    gptr = hostprog.init_lattice(stub, *DIMS, g, KAPPA)
     stub.stub_set_mu(MU)
     grows = (VP * V)(*[gptr + 4 * 144 * i for i in range(V)])
     host_links = np.frombuffer((dbl * (V * 72)).from_address(gptr), dtype=np.float64).reshape(V, 4, 3, 3, 2)
@@ -178,8 +150,7 @@ def main(mode):
     out["accept"] = a
     out["norms"] = norms
     d.tmlqcd_hip_finalize()
-    print(json.dumps(out))
-    sys.stdout.flush()
+    hostprog.emit(out)
 
 
 if __name__ == "__main__":
