@@ -948,7 +948,12 @@ int tmhip_get_option(tmhip_ctx *ctx, const char *name, int *value);
  * rotation 0, 1, 2, links without an exact rotation}.  tmhip_gauge_pack_build_ms: device time of the last build. */
 int tmhip_gauge_pack_stats(tmhip_ctx *ctx, long long out[5]);
 int tmhip_gauge_pack_build_ms(tmhip_ctx *ctx, double *ms);
-/* stencil launches of this context that read the packed copy so far */
+/* bytes per link the stencil reads of the twin, built now if it is stale: 104 (the two kept rows in their compact form: low words as they
+ * are, high words as 26-bit fields with a five-bit exponent and one escape per link -- exact, like everything else here), 112 (some link has
+ * a kept real at or above 2, a subnormal, or two reals below 2^-30: the rows as plain doubles), 0 (some link has no rotation: read in full).
+ * "gauge_pack_compact" -1 (default) | 1: the 104-byte form where the whole field fits it; 0: never (A/B runs, tests). */
+int tmhip_gauge_pack_format(tmhip_ctx *ctx, int *bytes_per_link);
+/* stencil launches of this context that read the packed copy (either form) so far */
 int tmhip_gauge_pack_launches(tmhip_ctx *ctx, long long *n);
 /* max |row2 - conj(row0 x row1)| over all links of the resident gauge field */
 int tmhip_gauge_su3_deviation(tmhip_ctx *ctx, double *maxdev);

@@ -163,7 +163,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
   ctx->opt_bicg_fused = 1;
   ctx->opt_eig_basis = 24; ctx->opt_eig_cheb = 4; ctx->opt_eig_fused = 1;   // the fastest measured at 32^4 (profiles/r19_eig_speed.log)
   ctx->gauge_recon_dev = -1.0;
-  ctx->opt_gauge_pack = -1; ctx->opt_gauge_pack_rot = -1;
+  ctx->opt_gauge_pack = -1; ctx->opt_gauge_pack_rot = -1; ctx->opt_gauge_pack_compact = -1;
   TMHIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   {  // boundary pipeline (pack, exchange, boundary kernels) must not queue behind the interior kernel's blocks
     int lo = 0, hi = 0;
@@ -345,6 +345,7 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   }
   else if (!strcmp(name, "gauge_pack")) { if (value < -1 || value > 1) TMHIP_FAIL("gauge_pack must be -1 (automatic), 0 (never read the packed links) or 1"); ctx->opt_gauge_pack = value; }
   else if (!strcmp(name, "gauge_pack_rot")) { if (value < -1 || value > 2) TMHIP_FAIL("gauge_pack_rot must be -1 (the first rotation that verifies) or the rotation to try first, 0, 1 or 2"); ctx->opt_gauge_pack_rot = value; ctx->gpack_state = 0; }
+  else if (!strcmp(name, "gauge_pack_compact")) { if (value < -1 || value > 1) TMHIP_FAIL("gauge_pack_compact must be -1 (the 104-byte form where the field fits it), 0 (never: the 112-byte form) or 1"); ctx->opt_gauge_pack_compact = value; ctx->gpack_state = 0; }
   else if (!strcmp(name, "hopsplit")) { if (value < -1 || value > 1) TMHIP_FAIL("hopsplit must be -1 (automatic), 0 or 1"); ctx->opt_hopsplit = value; }
   else if (!strcmp(name, "lds32")) { if (value < 0 || value > 1) TMHIP_FAIL("lds32 must be 0 or 1"); ctx->opt_stg32 = value; }
   else if (!strcmp(name, "lds")) { if (value < 0 || value > 1) TMHIP_FAIL("lds must be 0 (gather kernel) or 1 (per-wave LDS staging of the own-site spinors)"); ctx->opt_stg = value; }

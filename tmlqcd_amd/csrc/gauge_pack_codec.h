@@ -1,7 +1,8 @@
 // The codec of the packed link read (TmhipGaugePack, tmhip_internal.h): the third row of an SU(3) link from the
-// other two, and the 16-byte tail that says how far the stored row lies from that rebuild.  Plain inline functions, host and device:
-// gauge_pack_kernel (md_update.hip) encodes and verifies with them, hop_dir<.., GAUX 15, ..> (hopping_impl.inc) decodes with them,
-// tests/test_gauge_pack_codec.py compiles them into a host program.  Nothing here depends on HIP.
+// other two, the 16-byte tail that says how far the stored row lies from that rebuild, and the compact form of the two kept rows
+// (88 instead of 96 bytes: the end of this file).  Plain inline functions, host and device: gauge_pack_kernel (md_update.hip)
+// encodes and verifies with them, hop_dir<.., GAUX 15 | 16, ..> (hopping_impl.inc) decodes with them, tests/test_gauge_pack_codec.py
+// and tests/test_gauge_pack104_codec.py compile them into host programs.  Nothing here depends on HIP.
 //
 // Tail, 128 bits as four 32-bit words, bit n of the tail = bit n % 32 of word n / 32:
 //   bits 21 k .. 21 k + 20, k = 0..5 : d_k, a 21-bit two's-complement integer; k = 2 e + (0: re, 1: im) of element e of the rebuilt row
@@ -103,4 +104,80 @@ TMHIP_HD void tmhip_gpack_decode(const double (&w)[6], const uint32_t (&t)[4], d
 #pragma unroll
 #endif
   for (int k = 0; k < 6; k++) c[k] = tmhip_gpack_apply(w[k], tmhip_gpack_field(t, k));
+}
+
+// ---- the compact form of the two kept rows: 88 bytes for twelve reals, exact ("gauge_pack_compact", the 104-byte read) ----
+// Every real of a link that has a rotation is below 2 in magnitude, and all but a stray one are at or above 2^-30: five bits of
+// exponent do the work of eleven.  The twelve reals, in the order a0.re a0.im a1.re .. a2.im b0.re .. b2.im:
+//   lo[k]            bits 31..0 of real k as they are (three 16-byte planes)
+//   h[0..9], 320 bits, bit n = bit n % 32 of word n / 32 (two 16-byte planes and one 8-byte plane):
+//     bits 26 k .. 26 k + 25 : the field of real k -- bit 25 the sign, bits 24..20 the exponent code c, bits 19..0 bits 51..32 of the double
+//                              c = 0: biased exponent 0 (+-0.0);  c = 1..31: biased exponent 992 + c, magnitudes in [2^-30, 2)
+//     bits 312 .. 315        : the index of the one escaped real of the link, 15: none
+//     bits 316 .. 319        : ext = 1..15 -- the escaped real's biased exponent is 992 + c - 31 ext, down to 528 (2^-495)
+// A rebuilt real below about 5e-7 never fits the tail (its offset is about 0.5 / |x| ulps), so a tiny real always sits in a kept
+// row: the escape is what keeps a field with one such real compact.  A pair of rows "fits compact" when every real is +-0.0 or lies
+// in [2^-30, 2), except at most one in [2^-495, 2^-30); anything else -- a value at or above 2, a subnormal, a NaN, an infinity, a
+// second small real -- does not, and tmhip_gpack104_encode says so.  Integer operations only.
+constexpr int TMHIP_GPACK104_FIELD = 26;
+constexpr uint32_t TMHIP_GPACK104_EBASE = 992, TMHIP_GPACK104_ESTEP = 31, TMHIP_GPACK104_EXTMAX = 15;
+
+// field k of h (k is a constant wherever this is called from an unrolled loop)
+TMHIP_HD uint32_t tmhip_gpack104_field(const uint32_t (&h)[10], int k) {
+  const int o = TMHIP_GPACK104_FIELD * k, w = o >> 5, sh = o & 31;
+  uint32_t v = h[w] >> sh;
+  if (sh + TMHIP_GPACK104_FIELD > 32) v |= h[w + 1] << (32 - sh);
+  return v & ((1u << TMHIP_GPACK104_FIELD) - 1u);
+}
+// the high word of a real from its field; base: what a non-zero exponent code is lifted by, 992 << 20 for a real without the escape
+TMHIP_HD uint32_t tmhip_gpack104_high(uint32_t f, uint32_t base = TMHIP_GPACK104_EBASE << 20) {
+  const uint32_t x = f & 0x1FFFFFFu;
+  return (x + ((x >> 20) ? base : 0u)) | ((f >> 25) << 31);
+}
+
+// twelve reals -> lo, h; false: the rows do not fit compact (the planes are then defined, and wrong)
+TMHIP_HD bool tmhip_gpack104_encode(const double (&v)[12], uint32_t (&lo)[12], uint32_t (&h)[10]) {
+  bool fits = true;
+  uint32_t esc = 15u, ext = 0u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int w = 0; w < 10; w++) h[w] = 0u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int k = 0; k < 12; k++) {
+    const uint64_t u = tmhip_gpack_bits(v[k]);
+    lo[k] = (uint32_t)u;
+    const uint32_t hi = (uint32_t)(u >> 32), e = (hi >> 20) & 0x7FFu, m = hi & 0xFFFFFu;
+    uint32_t c = 0u;
+    if (e == 0u) fits = fits && m == 0u && lo[k] == 0u;                                  // +-0.0; a subnormal does not fit
+    else if (e > TMHIP_GPACK104_EBASE && e <= TMHIP_GPACK104_EBASE + 31u) c = e - TMHIP_GPACK104_EBASE;
+    else if (e <= TMHIP_GPACK104_EBASE && e + TMHIP_GPACK104_ESTEP * TMHIP_GPACK104_EXTMAX > TMHIP_GPACK104_EBASE && esc == 15u) {
+      esc = (uint32_t)k;
+      ext = (TMHIP_GPACK104_EBASE + 31u - e) / TMHIP_GPACK104_ESTEP;                      // the smallest ext that brings c to 1..31
+      c = e + TMHIP_GPACK104_ESTEP * ext - TMHIP_GPACK104_EBASE;
+    } else fits = false;                                                                 // >= 2, inf, NaN, below 2^-495, or a second small real
+    const uint32_t f = (hi >> 31) << 25 | c << 20 | m;
+    const int o = TMHIP_GPACK104_FIELD * k, w = o >> 5, sh = o & 31;
+    h[w] |= f << sh;
+    if (sh + TMHIP_GPACK104_FIELD > 32) h[w + 1] |= f >> (32 - sh);
+  }
+  h[9] |= (esc | ext << 4) << 24;
+  return fits;
+}
+
+// lo, h -> twelve reals.  The escape is a select per real on what its exponent code is lifted by -- a compare and a select, no
+// branch: behind a wave-uniform branch (a ballot of "index != 15") it would cost one scalar branch per link, but the branch cuts
+// every hop of the stencil into basic blocks, and the instance then spills 1.6 kB per lane under its bound of three waves per SIMD
+// (256 registers left to itself), where the straight-line form takes 144 registers.
+TMHIP_HD void tmhip_gpack104_decode(const uint32_t (&lo)[12], const uint32_t (&h)[10], double (&v)[12]) {
+  const uint32_t esc = (h[9] >> 24) & 15u, plain = TMHIP_GPACK104_EBASE << 20, escaped = plain - ((TMHIP_GPACK104_ESTEP * (h[9] >> 28)) << 20);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int k = 0; k < 12; k++) {
+    const uint32_t hi = tmhip_gpack104_high(tmhip_gpack104_field(h, k), esc == (uint32_t)k ? escaped : plain);
+    v[k] = tmhip_gpack_real((uint64_t)hi << 32 | lo[k]);
+  }
 }

@@ -11,7 +11,7 @@ struct HopArgs {
   const ET *in;
   const ET *p;
   const ET *gauge;  // already offset to the parity of the output sites
-  TmhipGaugePack pack;   // GAUX 15 instances: the packed twin of the gauge copy, offset to the parity like `gauge`
+  TmhipGaugePack pack;   // GAUX 15 / 16 instances: the packed twin of the gauge copy, offset to the parity like `gauge`
   const ET *halo_up, *halo_dn;
   const ET *cw;      // clover epilogues: sw (6 blocks) or sw_inv (8 blocks) of the output sites, [blk][9][gs]
   const ET *dotv;   // EPI_TM_SUB_G5_DOT: field whose real scalar product with the output is accumulated
@@ -126,9 +126,11 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
                                         const unsigned char *lds = nullptr, int jl = 0, const TmhipGaugePack &pk = TmhipGaugePack{}) {
   (void)j2; (void)pk;
   V2T pa[3], pb[3];
-  V2T ra[3], rb[3], rc[3]; v4u tl = {};   // GAUX 15: the two stored rows, the rebuilt one, the tail (its offsets and the rotation)
-  (void)ra; (void)rb; (void)rc; (void)tl;
-  static_assert(GAUX != 15 || !HALO, "the packed link read has no boundary form");
+  constexpr bool PACKED = GAUX == 15 || GAUX == 16;   // 15: the 112-byte form, 16: the 104-byte form (compact rows)
+  V2T ra[3], rb[3], rc[3]; v4u tl = {};   // PACKED: the two stored rows, the rebuilt one, the tail (its offsets and the rotation)
+  v4u cl[3] = {}, ch[2] = {}; v2u ch2 = {};   // GAUX 16: the compact rows as loaded -- low words, packed high words
+  (void)ra; (void)rb; (void)rc; (void)tl; (void)cl; (void)ch; (void)ch2;
+  static_assert(!PACKED || !HALO, "the packed link read has no boundary form");
   if (HALO) {
     V2T h[6];
     ld6_fresh(h, halo, (size_t)face, j, 0);   // written by the exchange while this kernel may already have been running: never from L1
@@ -148,7 +150,7 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
     } else {
       ld6<false>(s, in, (size_t)ns, j, 0); ld6<false>(s + 6, in, (size_t)ns, j, 1);
     }
-    if constexpr (GAUX == 15) {
+    if constexpr (PACKED) {
       // Packed link read: the link's seven loads are requested right behind the spinor's, and the spinor is projected (48 -> 24
       // registers) while they are in flight; the rebuild and the selects below then have the room they need.  Left to itself
       // the compiler asks for the link first and rebuilds it with the whole neighbour spinor outstanding: 176 registers for EPI_TM_SUB_G5
@@ -156,11 +158,28 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
       __builtin_amdgcn_sched_barrier(0);
       // (scalar plane base + one 32-bit lane offset per load: a direction's planes of one parity span < 4 GiB, pack_setup)
       const unsigned int ugs = (unsigned int)gs, ui = (unsigned int)i;
-      const char *prow = reinterpret_cast<const char *>(pk.rows + (size_t)D * 6 * gs);
+      if constexpr (GAUX == 16) {
+        // the compact rows: three planes of low words, two and a half of packed high words -- 88 bytes in six loads
+        const char *plo = reinterpret_cast<const char *>(pk.lo + (size_t)D * 3 * gs), *phi = reinterpret_cast<const char *>(pk.hi + (size_t)D * 2 * gs);
   #pragma unroll
-      for (int e = 0; e < 3; e++) {
-        ra[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)e * ugs + ui) * 16u)));
-        rb[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)(3 + e) * ugs + ui) * 16u)));
+        for (int e = 0; e < 3; e++) {
+          const v4u *q = reinterpret_cast<const v4u *>(plo + (size_t)(((unsigned int)e * ugs + ui) * 16u));
+          cl[e] = NT ? __builtin_nontemporal_load(q) : *q;
+        }
+  #pragma unroll
+        for (int e = 0; e < 2; e++) {
+          const v4u *q = reinterpret_cast<const v4u *>(phi + (size_t)(((unsigned int)e * ugs + ui) * 16u));
+          ch[e] = NT ? __builtin_nontemporal_load(q) : *q;
+        }
+        const v2u *q2 = reinterpret_cast<const v2u *>(reinterpret_cast<const char *>(pk.hi2 + (size_t)D * gs) + (size_t)(ui * 8u));
+        ch2 = NT ? __builtin_nontemporal_load(q2) : *q2;
+      } else {
+        const char *prow = reinterpret_cast<const char *>(pk.rows + (size_t)D * 6 * gs);
+  #pragma unroll
+        for (int e = 0; e < 3; e++) {
+          ra[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)e * ugs + ui) * 16u)));
+          rb[e] = ldc<NT>(reinterpret_cast<const v2d *>(prow + (size_t)(((unsigned int)(3 + e) * ugs + ui) * 16u)));
+        }
       }
       const v4u *pt = reinterpret_cast<const v4u *>(reinterpret_cast<const char *>(pk.tail + (size_t)D * gs) + (size_t)(ui * 16u));
       tl = NT ? __builtin_nontemporal_load(pt) : *pt;
@@ -177,12 +196,24 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
       if (D == 6) { pa[c] = V2T{s0.x - s2.y, s0.y + s2.x}; pb[c] = V2T{s1.x + s3.y, s1.y - s3.x}; }  // s0+i s2, s1-i s3
       if (D == 7) { pa[c] = V2T{s0.x + s2.y, s0.y - s2.x}; pb[c] = V2T{s1.x - s3.y, s1.y + s3.x}; }  // s0-i s2, s1+i s3
     }
-    if constexpr (GAUX == 15) {
+    if constexpr (PACKED) {
       // (the projected half-spinor is pinned here: an empty statement the compiler cannot move the additions past)
 #pragma unroll
       for (int c = 0; c < 3; c++) asm volatile("" : "+v"(pa[c]), "+v"(pb[c]));
       __builtin_amdgcn_sched_barrier(0);
     }
+#ifndef HOP_GAUGE_PACKED
+    if constexpr (GAUX == 16) {
+      // the twelve kept reals from their compact form, directly behind the projection: the neighbour spinor is down to 24 registers
+      // before these 24 are made of the 22 that were loaded (integer work, gauge_pack_codec.h)
+      const uint32_t lo[12] = {cl[0].x, cl[0].y, cl[0].z, cl[0].w, cl[1].x, cl[1].y, cl[1].z, cl[1].w, cl[2].x, cl[2].y, cl[2].z, cl[2].w};
+      const uint32_t hw[10] = {ch[0].x, ch[0].y, ch[0].z, ch[0].w, ch[1].x, ch[1].y, ch[1].z, ch[1].w, ch2.x, ch2.y};
+      double v12[12];
+      tmhip_gpack104_decode(lo, hw, v12);
+#pragma unroll
+      for (int e = 0; e < 3; e++) { ra[e] = V2T{v12[2 * e], v12[2 * e + 1]}; rb[e] = V2T{v12[6 + 2 * e], v12[7 + 2 * e]}; }
+    }
+#endif
   }
   const ET *gd = g + (size_t)D * 9 * gs + i;
   V2T u[9];
@@ -204,8 +235,8 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
     }
   }
 #else
-  if constexpr (GAUX == 15) {
-    // packed read ("gauge_pack"): two rows and the 16-byte tail -- 112 bytes; the third row is rebuilt and moved by the tail's
+  if constexpr (PACKED) {
+    // packed read ("gauge_pack"): two rows (GAUX 16: decoded from their compact form above) and the 16-byte tail -- 112 or 104 bytes; the third row is rebuilt and moved by the tail's
     // offsets (integer additions on the bit patterns) by the functions that verified it bit for bit when the copy was built
     // (gauge_pack_codec.h, gauge_pack_kernel in md_update.hip), and the rows go back to their places by selects on the tail's
     // rotation: every load is uniform across the wave, the result is the stored link
@@ -270,7 +301,7 @@ __device__ __forceinline__ void hop_dir(V2T (&acc)[12], const ET *__restrict__ i
   }
   // (packed link read: nothing of the next hop is requested before this one is added up -- as in the other instances, there by the
   // compiler's own choice -- so that the registers of the rebuild are free again)
-  if constexpr (GAUX == 15) __builtin_amdgcn_sched_barrier(0);
+  if constexpr (PACKED) __builtin_amdgcn_sched_barrier(0);
 }
 
 // TSKIP (T-split rank, DESIGN.md section 7): the launch still covers ALL sites of the rank, but the one hop that crosses the rank
@@ -350,7 +381,7 @@ __device__ __forceinline__ void faces_count_in(const HopArgs &a, unsigned int or
 template <int EPI, int TSKIP, bool NTIO, int BS, int MINW, int GAUX = -1, int STG = 0>
 __global__ __launch_bounds__(BS, MINW) void hop_kernel(const HopArgs a) {
   static_assert(STG == 0 || (STG == 64 && HOP_SITES == 1), "the LDS-staged variant: one site per thread, whole blocks");
-  static_assert(GAUX != 15 || (STG == 64 && TSKIP == 0), "the packed link read exists in the staged kernel of unsplit lattices only");
+  static_assert((GAUX != 15 && GAUX != 16) || (STG == 64 && TSKIP == 0), "the packed link read exists in the staged kernel of unsplit lattices only");
   // gauge links: used once per call -> non-temporal (0.19 -> 0.16 ms at 32^4).  GAUX = -2 (small unsplit lattices, 64-thread blocks, the
   // gauge copy under ~200 MB: launch_variant): NOT marked streaming, so the links stay in the 256 MiB Infinity Cache from one call to
   // the next: 12^4 10.5 -> 8.8, 16^4 15.3 -> 12.1, 20^4 25.3 -> 21.9 us per launch; beyond the cache it is a loss (24^4 53 -> 62,
@@ -1031,7 +1062,11 @@ static void launch_variant(const HopArgs &a, hipStream_t st, const HopLaunch &o)
         if (o.recon == 12) { launch_one<EPI, TSKIP, true, 256, 3, 12, 64>(a, st, o); return; }
 #ifndef HOP_GAUGE_PACKED
         if constexpr (!TSKIP) {
-          if (o.pack) { launch_one<EPI, 0, true, 256, 3, 15, 64>(a, st, o); if (o.pack_count) ++*o.pack_count; return; }   // bit-exact 112-byte link read ("gauge_pack")
+          if (o.pack) {   // bit-exact packed link read ("gauge_pack"): 104 bytes where the twin was built compact, else 112
+            if (o.pack == 16) launch_one<EPI, 0, true, 256, 3, 16, 64>(a, st, o); else launch_one<EPI, 0, true, 256, 3, 15, 64>(a, st, o);
+            if (o.pack_count) ++*o.pack_count;
+            return;
+          }
         }
 #endif
       }
@@ -1148,7 +1183,8 @@ static int pack_setup(tmhip_ctx *ctx, HopArgs &a, HopLaunch &o, int ieo, int epi
   if (!usable) return 0;
   const size_t off = (size_t)(ieo ? 1 : 0) * 8 * ctx->gs;
   a.pack.rows = ctx->gpack.rows + off * 6; a.pack.tail = ctx->gpack.tail + off;
-  o.pack = 1; o.pack_count = &ctx->gpack_launches;
+  a.pack.lo = ctx->gpack.lo + off * 3; a.pack.hi = ctx->gpack.hi + off * 2; a.pack.hi2 = ctx->gpack.hi2 + off;
+  o.pack = ctx->gpack_bytes == 104 ? 16 : 15; o.pack_count = &ctx->gpack_launches;   // the GAUX value of the instance that reads the twin as built
 #else
   (void)ctx; (void)a; (void)o; (void)ieo; (void)epi; (void)split;
 #endif

@@ -317,10 +317,16 @@ int tmhip_resort_gauge(tmhip_ctx *ctx) {
 // (gauge_pack_codec.h: six 21-bit offsets in ulps), decoded again by the function the stencil uses and compared with the stored row
 // as 64-bit integers.  The first rotation that reproduces all six reals is stored; a link without one is counted in count[2] and the
 // field is then not read packed at all.  count[0..1]: links on rotation 1 / 2 (one atomic per wave that has any).
-__global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__ g, v2d *__restrict__ rows, v4u *__restrict__ tail, int gs, int Vh, int first,
-                                                         unsigned int *count) {
+// compact: the two kept rows are written in the 88-byte form of gauge_pack_codec.h instead (pk.lo, pk.hi, pk.hi2 in the place of
+// pk.rows), decoded again by the stencil's function and compared as 64-bit integers; count[3]: links that have a rotation -- chosen
+// exactly as without the flag -- but whose kept rows do not fit that form.
+__global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__ g, const TmhipGaugePack pk, int gs, int Vh, int first, unsigned int *count,
+                                                         int compact) {
+  v2d *__restrict__ rows = const_cast<v2d *>(pk.rows);
+  v4u *__restrict__ tail = const_cast<v4u *>(pk.tail);
   const int i = blockIdx.x * 256 + threadIdx.x;
   int chosen = 0;   // 0..2: rotation, 3: none, -1: no link
+  bool nofit = false;   // compact: the link has a rotation and its kept rows do not fit the 88-byte form
   if (i >= Vh) chosen = -1;
   else {
     const size_t slot = (size_t)blockIdx.y * gs + i;
@@ -357,16 +363,33 @@ __global__ __launch_bounds__(256) void gauge_pack_kernel(const v2d *__restrict__
         if (same) chosen = r;
       }
     }
+    if (compact) {
+      const double k12[12] = {ka[0].x, ka[0].y, ka[1].x, ka[1].y, ka[2].x, ka[2].y, kb[0].x, kb[0].y, kb[1].x, kb[1].y, kb[2].x, kb[2].y};
+      double t12[12];
+      uint32_t lo[12], h[10];
+      bool same = tmhip_gpack104_encode(k12, lo, h);
+      tmhip_gpack104_decode(lo, h, t12);
 #pragma unroll
-    for (int e = 0; e < 3; e++) {
-      rows[((size_t)blockIdx.y * 6 + e) * gs + i] = ka[e];
-      rows[((size_t)blockIdx.y * 6 + 3 + e) * gs + i] = kb[e];
+      for (int e = 0; e < 12; e++) same = same && tmhip_gpack_bits(t12[e]) == tmhip_gpack_bits(k12[e]);
+      nofit = chosen != 3 && !same;
+      v4u *lop = const_cast<v4u *>(pk.lo) + (size_t)blockIdx.y * 3 * gs + i, *hip = const_cast<v4u *>(pk.hi) + (size_t)blockIdx.y * 2 * gs + i;
+#pragma unroll
+      for (int e = 0; e < 3; e++) lop[(size_t)e * gs] = v4u{lo[4 * e], lo[4 * e + 1], lo[4 * e + 2], lo[4 * e + 3]};
+#pragma unroll
+      for (int e = 0; e < 2; e++) hip[(size_t)e * gs] = v4u{h[4 * e], h[4 * e + 1], h[4 * e + 2], h[4 * e + 3]};
+      const_cast<v2u *>(pk.hi2)[slot] = v2u{h[8], h[9]};
+    } else {
+#pragma unroll
+      for (int e = 0; e < 3; e++) {
+        rows[((size_t)blockIdx.y * 6 + e) * gs + i] = ka[e];
+        rows[((size_t)blockIdx.y * 6 + 3 + e) * gs + i] = kb[e];
+      }
     }
     tail[slot] = v4u{kt[0], kt[1], kt[2], kt[3]};
   }
 #pragma unroll
-  for (int v = 1; v <= 3; v++) {
-    const unsigned long long m = __ballot(chosen == v);
+  for (int v = 1; v <= 4; v++) {
+    const unsigned long long m = __ballot(v == 4 ? nofit : chosen == v);
     if (m && (threadIdx.x & 63) == 0) atomicAdd(count + (v - 1), (unsigned int)__popcll(m));
   }
 }
@@ -393,22 +416,33 @@ int tmhip_gauge_pack_prepare(tmhip_ctx *ctx, bool *usable) {
       unsigned char *m = (unsigned char *)ctx->gpack_mem;
       ctx->gpack.rows = (const v2d *)m;
       ctx->gpack.tail = (const v4u *)(m + n * 96);
+      ctx->gpack.lo = (const v4u *)m;              // the compact rows lie where the six row planes do: 48 + 32 + 8 of their 96 bytes per link
+      ctx->gpack.hi = (const v4u *)(m + n * 48);
+      ctx->gpack.hi2 = (const v2u *)(m + n * 80);
       ctx->gpack_count = (unsigned int *)(m + n * 112);
     }
-    TMHIP_CHECK(hipMemsetAsync(ctx->gpack_count, 0, 3 * sizeof(unsigned int), ctx->stream));
-    TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[0], ctx->stream));
     const int first = ctx->opt_gauge_pack_rot < 0 ? 0 : ctx->opt_gauge_pack_rot;
-    hipLaunchKernelGGL(gauge_pack_kernel, dim3((ctx->Vh + 255) / 256, 16), dim3(256), 0, ctx->stream, (const v2d *)ctx->gauge, (v2d *)ctx->gpack.rows,
-                       (v4u *)ctx->gpack.tail, ctx->gs, ctx->Vh, first, ctx->gpack_count);
-    TMHIP_CHECK(hipGetLastError());
-    TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[1], ctx->stream));
-    unsigned int h[3] = {0, 0, 0};
-    TMHIP_CHECK(hipMemcpyAsync(h, ctx->gpack_count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    unsigned int h[4] = {0, 0, 0, 0};
+    // the compact form first; a field with rotations throughout but a link that does not fit it is built once more in the 112-byte form
+    // (the rotations, and with them the first three counters, are the same in both launches)
+    int compact = ctx->opt_gauge_pack_compact != 0 ? 1 : 0;
+    TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[0], ctx->stream));
+    for (;;) {
+      TMHIP_CHECK(hipMemsetAsync(ctx->gpack_count, 0, sizeof(h), ctx->stream));
+      hipLaunchKernelGGL(gauge_pack_kernel, dim3((ctx->Vh + 255) / 256, 16), dim3(256), 0, ctx->stream, (const v2d *)ctx->gauge, ctx->gpack, ctx->gs, ctx->Vh, first,
+                         ctx->gpack_count, compact);
+      TMHIP_CHECK(hipGetLastError());
+      TMHIP_CHECK(hipEventRecord(ctx->gpack_ev[1], ctx->stream));
+      TMHIP_CHECK(hipMemcpyAsync(h, ctx->gpack_count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+      TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+      if (!(compact && h[2] == 0 && h[3] != 0)) break;
+      compact = 0;
+    }
     TMHIP_CHECK(hipEventElapsedTime(&ctx->gpack_build_ms, ctx->gpack_ev[0], ctx->gpack_ev[1]));
     ctx->gpack_stats[1] = h[0]; ctx->gpack_stats[2] = h[1]; ctx->gpack_stats[3] = h[2];
     ctx->gpack_stats[0] = (long long)16 * ctx->Vh - h[0] - h[1] - h[2];
     ctx->gpack_state = h[2] == 0 ? 1 : 2;
+    ctx->gpack_bytes = h[2] != 0 ? 0 : (compact ? 104 : 112);
   }
   *usable = ctx->gpack_state == 1;
   return 0;
@@ -424,6 +458,16 @@ int tmhip_gauge_pack_stats(tmhip_ctx *ctx, long long out[5]) {
   if (tmhip_gauge_pack_prepare(ctx, &usable)) return 1;
   out[0] = usable ? 1 : 0;
   for (int k = 0; k < 4; k++) out[1 + k] = ctx->gpack_stats[k];
+  return 0;
+}
+
+int tmhip_gauge_pack_format(tmhip_ctx *ctx, int *bytes_per_link) {
+  if (!bytes_per_link) TMHIP_FAIL("tmhip_gauge_pack_format: null argument");
+  if (!ctx->gauge_set) TMHIP_FAIL("tmhip_gauge_pack_format called before tmhip_set_gauge");
+  TMHIP_CHECK(hipSetDevice(ctx->device));
+  bool usable = false;
+  if (tmhip_gauge_pack_prepare(ctx, &usable)) return 1;
+  *bytes_per_link = usable ? ctx->gpack_bytes : 0;
   return 0;
 }
 

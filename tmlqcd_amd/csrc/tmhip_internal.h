@@ -88,10 +88,17 @@ struct TmhipDirect {
 // stored third row from its rebuild out of the other two, and two bits that say which cyclic rotation of the rows was stored:
 // 96 + 16 = 112 bytes instead of 144.  Rotation r: rows r and r + 1 (mod 3) are kept, row r + 2 is tmhip_su3_row_rebuild of them
 // plus the offsets.  The bit layout, the rebuild and the encode / decode pair live in gauge_pack_codec.h.
+// The compact form ("gauge_pack_compact") stores the twelve kept reals in 88 bytes -- their low words as they are, their high words as
+// 26-bit fields with a five-bit exponent, one escape per link -- in the place of the six row planes: 88 + 16 = 104 bytes.  A field
+// some link of which does not fit that form is built in the 112-byte form; one allocation serves either.
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 struct TmhipGaugePack {
-  const v2d *rows;            // [8][6][gs]: kept row a (elements 0..2), kept row b (elements 0..2)
+  const v2d *rows;            // [8][6][gs]: kept row a (elements 0..2), kept row b (elements 0..2)   (112-byte form)
   const v4u *tail;            // [8][gs]
+  const v4u *lo;              // [8][3][gs]: low words of the twelve kept reals                      (104-byte form, in the place of rows)
+  const v4u *hi;              // [8][2][gs]: words 0..7 of their packed high words
+  const v2u *hi2;             // [8][gs]:    words 8..9, the escape in the top byte
 };
 
 struct tmhip_ctx {
@@ -197,7 +204,7 @@ struct tmhip_ctx {
   void *flow;                         // gradient flow in progress (flow.hip): two link buffers and Z, from tmhip_flow_begin to tmhip_flow_end
   void *meas;                         // online measurements (meas.hip): partial sums and the pinned results of a call, allocated on first use
   double gauge_recon_dev;   // max |U_row2 - conj(row0 x row1)| over all links of the resident gauge field (-1: not measured)
-  // packed twin of the gauge copy (112 bytes per link, bit-exact: DESIGN.md section 6, "packed gauge read"), built on first use like gauge32
+  // packed twin of the gauge copy (104 or 112 bytes per link, bit-exact: DESIGN.md section 6, "packed gauge read"), built on first use like gauge32
   void *gpack_mem;          // one allocation behind the two plane sets of gpack
   TmhipGaugePack gpack;     // device planes, [2 parities][8 directions][..][gs] each (null until the first build)
   int gpack_state;          // 0 stale, 1 built and every link has an exact rotation (the stencil may read it), 2 built, some link has none
@@ -205,7 +212,9 @@ struct tmhip_ctx {
   bool gpack_ev_made;       // gpack_ev exist
   long long gpack_launches; // stencil launches that read the packed copy so far (tmhip_gauge_pack_launches: what the tests look at)
   long long gpack_stats[4]; // links stored on rotation 0, 1, 2 / links without an exact rotation, of the last build
-  unsigned int *gpack_count;// device: [0..1] links on rotation 1, 2, [2] links without one
+  unsigned int *gpack_count;// device: [0..1] links on rotation 1, 2, [2] links without one, [3] links with a rotation that do not fit compact
+  int gpack_bytes;          // bytes per link the stencil reads of the twin as built: 104 (compact rows), 112, or 0 (state 2: read in full)
+  int opt_gauge_pack_compact;   // -1 (default) and 1: the compact rows where the whole field fits them; 0: never (A/B runs, tests)
   int opt_gauge_pack;       // -1 automatic (default) and 1: read the packed copy where it is valid and the instance exists; 0: never
   int opt_gauge_pack_rot;   // -1: the first rotation that verifies; 0..2: try that one first (tests)
   float gpack_build_ms;     // device time of the last build (HIP events)

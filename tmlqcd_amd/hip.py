@@ -138,7 +138,7 @@ def load_library():
         "tmhip_bench_spinor_io": [vp, vp, vp, i, i, i, pd],
         "tmhip_gauge_su3_deviation": [vp, pd],
         "tmhip_gauge_pack_stats": [vp, C.POINTER(C.c_longlong)], "tmhip_gauge_pack_build_ms": [vp, pd],
-        "tmhip_gauge_pack_launches": [vp, C.POINTER(C.c_longlong)],
+        "tmhip_gauge_pack_launches": [vp, C.POINTER(C.c_longlong)], "tmhip_gauge_pack_format": [vp, C.POINTER(i)],
         "tmhip_derivative_zero": [vp],
         "tmhip_swpm_zero": [vp], "tmhip_sw_spinor_eo": [vp, i, vp, vp, d], "tmhip_sw_deriv": [vp, i, d],
         "tmhip_sw_all": [vp, vp, d, d], "tmhip_get_swpm": [vp, vp, vp],
@@ -457,6 +457,13 @@ class Lattice:
         out = (C.c_longlong * 5)()
         _ck(self.lib.tmhip_gauge_pack_stats(self.h, out), "tmhip_gauge_pack_stats")
         return tuple(int(v) for v in out)
+
+    def gauge_pack_format(self):
+        """bytes per link the stencil reads of the packed twin: 104 (compact rows, option gauge_pack_compact), 112, or 0 where the
+        field is read in full; builds the twin if it is stale."""
+        out = C.c_int()
+        _ck(self.lib.tmhip_gauge_pack_format(self.h, C.byref(out)), "tmhip_gauge_pack_format")
+        return out.value
 
     def gauge_pack_launches(self):
         """stencil launches that read the packed copy so far"""

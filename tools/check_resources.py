@@ -28,6 +28,8 @@ RULES = [
     (r"^void hop64::hop_kernel<(\d+), ([013]), true, 256, (3|1), -1, 64>", "fp64 staged"),
     # ... and its packed link read (GAUX 15, "gauge_pack"): twisted-mass epilogues of unsplit lattices, three waves per SIMD, no scratch
     (r"^void hop64::hop_kernel<(\d+), 0, true, 256, 3, 15, 64>", "fp64 staged packed"),
+    # ... and the 104-byte form of it (GAUX 16, "gauge_pack_compact"): the same eight epilogues, the same floor
+    (r"^void hop64::hop_kernel<(\d+), 0, true, 256, 3, 16, 64>", "fp64 staged packed 104"),
     # the shifted residual epilogue of the multi-shift CG (EPI 12, mms.hip) in the gather kernel: one more field than its sibling EPI 9
     # (190 VGPRs, two waves per SIMD); its staged form above keeps three
     (r"^void hop64::hop_kernel<12, 0, true, (64|256), 1, (-1|-2), 0>", "fp64 gather shifted res", 2),

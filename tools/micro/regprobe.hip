@@ -21,4 +21,7 @@ template __global__ void hop_kernel<PROBE_EPI, 3, true, 64, 3, -1, 0>(const HopA
 // the packed link read (GAUX 15) under its bound of three waves per SIMD and left to itself
 template __global__ void hop_kernel<PROBE_EPI, 0, true, 256, 3, 15, 64>(const HopArgs);
 template __global__ void hop_kernel<PROBE_EPI, 0, true, 256, 1, 15, 64>(const HopArgs);
+// ... and its 104-byte form (GAUX 16)
+template __global__ void hop_kernel<PROBE_EPI, 0, true, 256, 3, 16, 64>(const HopArgs);
+template __global__ void hop_kernel<PROBE_EPI, 0, true, 256, 1, 16, 64>(const HopArgs);
 }  // namespace hop64
