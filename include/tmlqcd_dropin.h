@@ -227,6 +227,20 @@ void Q_tau1_sub_const_ndpsi(spinor *const l_strange, spinor *const l_charm, spin
 int cg_her_nd(spinor *const P_up, spinor *P_dn, spinor *const Q_up, spinor *const Q_dn, const int max_iter, double eps_sq,
               const int rel_prec, const int N, matrix_mult_nd f);
 int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *solver_params);
+/* ---- operator/tm_operators_nd_32.c, solver/rg_mixed_cg_her_nd.h: the fp32 doublet and the mixed-precision doublet solve ----
+ * The three operators act on HOST spinor32 arrays of VOLUME/2 sites like the fp32 twins above: operands are copied in and results out
+ * on every call; (float) g_mubar, (float) g_epsbar and (float) phmc_invmaxev * phmc_invmaxev are read as the reference reads them.
+ * The output pair may be the input pair. */
+typedef void (*matrix_mult_nd32)(spinor32 *const, spinor32 *const, spinor32 *const, spinor32 *const);   /* solver/matrix_mult_typedef_nd.h:32 */
+void Qtm_pm_ndpsi_32(spinor32 *const l_strange, spinor32 *const l_charm, spinor32 *const k_strange, spinor32 *const k_charm);   /* tm_operators_nd_32.c:215 */
+void M_ee_inv_ndpsi_32(spinor32 *const l_s, spinor32 *const l_c, spinor32 *const k_s, spinor32 *const k_c, const float mu, const float eps);   /* :137 */
+void M_oo_sub_g5_ndpsi_32(spinor32 *const l_s, spinor32 *const l_c, spinor32 *const k_s, spinor32 *const k_c, spinor32 *const j_s,
+                          spinor32 *const j_c, const float mu, const float eps);                                                   /* :200 */
+/* solver/rg_mixed_cg_her_nd.c:189-341, `solver_params_t` by value as for rg_mixed_cg_her above (mcg_delta is the field read).  Runs on
+ * the device, with the fields resident as for cg_her_nd, for f = Qtm_pm_ndpsi on N = VOLUME/2 sites: the fp32 operator is then
+ * Qtm_pm_ndpsi_32 whatever f32 is.  Anything else (Qsw_pm_ndpsi has no fp32 twin here) ends the program with a message. */
+int rg_mixed_cg_her_nd(spinor *const P_up, spinor *const P_dn, spinor *const Q_up, spinor *const Q_dn, tmlqcd_solver_params solver_params,
+                       const int max_iter, const double eps_sq, const int rel_prec, const int N, matrix_mult_nd f, matrix_mult_nd32 f32);
 /* ---- the clover doublet: operator/tm_operators_nd.h (Qsw_*), operator/clovertm_operators.h (the _nd functions), operator/clover_leaf.h ----
  * fp64, unsplit lattices.  The device's clover term must belong to the current links (tmlqcd_hip_sw_term, or the host's sw_term followed
  * by tmlqcd_hip_update_clover), and sw_invert_nd(mubar^2 - epsbar^2) must have run on it, as ndrat_monomial.c:89-91 does; otherwise every
@@ -239,7 +253,8 @@ int cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spin
  * degenerate clover symbol called after sw_invert_nd without tmlqcd_hip_sw_invert in between uploads the host's sw / sw_inv again --
  * whose first half now holds the doublet's inverse -- and drops sw_inv_nd.
  * tmlqcd_hip_sw_invert_failures() returns six_invert's count of near-singular pivots of the last inversion (the reference prints it).
- * Not here: the fp32 twins (Qsw_pm_ndpsi_32), Qsw_pm_ndbipsi, clover_nd. */
+ * Not here: the clover doublet's fp32 twin (Qsw_pm_ndpsi_32; the twisted-mass doublet's, Qtm_pm_ndpsi_32, is above), Qsw_pm_ndbipsi,
+ * clover_nd. */
 void sw_invert_nd(const double mshift);                                                                                  /* clover_invert.c:440 */
 void sw_deriv_nd(const int ieo);                                                                                         /* clover_deriv.c:156 */
 int tmlqcd_hip_sw_invert_failures(void);

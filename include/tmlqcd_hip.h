@@ -282,7 +282,7 @@ int tmhip_eig_small(int n, double *A /* n*n, in: symmetric, out: eigenvectors by
 
 /* ---- non-degenerate twisted-mass doublet (operator/tm_operators_nd.c) ------------------------
  * A doublet is a pair of EO fields (strange = up, charm = dn).  Unsplit lattices only: a context with nproc_t > 1 refuses every
- * entry point below with a message.  Wilson twisted mass, fp64 (no clover term, no fp32 twins). */
+ * entry point below with a message.  Wilson twisted mass, fp64, no clover term (the clover doublet and the fp32 twins follow below). */
 /* g_mubar, g_epsbar (global.h:202) and phmc_invmaxev (phmc.h:31; default 1), read by the operators and solvers at call time */
 int tmhip_set_nd(tmhip_ctx *ctx, double mubar, double epsbar, double invmaxev);
 /* M_ee_inv_ndpsi(l_s,l_c,k_s,k_c,mu,eps)          tm_operators_nd.c:639-696; l may be k */
@@ -346,6 +346,28 @@ int tmhip_cg_her_nd_op(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmh
                        int rel_prec, int N, int op, int *iters);
 int tmhip_cg_mms_tm_nd_op(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmhip_field *Qup, tmhip_field *Qdn, const double *shifts,
                           int nshifts, int max_iter, double eps_sq, int rel_prec, int op, int *iters);
+/* ---- the fp32 doublet and the mixed-precision doublet solve (operator/tm_operators_nd_32.c, solver/rg_mixed_cg_her_nd.c) ----------
+ * Wilson twisted mass on unsplit lattices: a T-split context or its loopback rehearsal is refused with a message before any launch.
+ * The operators act on fp32 EO fields (tmhip_field_alloc32) and read the fp32 twin of the links, built on first use.  mu, eps, nrm and
+ * phmc_invmaxev^2 are rounded to float as the reference's casts do.  The doublet stencil reads every link in full, 18 reals, whatever
+ * "gauge_recon" says.  "nd_fused" 1 (default) / 0: one doublet stencil per hop with the mixing as its epilogue / two
+ * tmhip_hopping_matrix_32 launches per hop and one mixing kernel, the same operator. */
+/* M_ee_inv_ndpsi_32(l_s,l_c,k_s,k_c,mu,eps)   tm_operators_nd_32.c:137-149; l may be k */
+int tmhip_M_ee_inv_ndpsi_32(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, float mu, float eps);
+/* M_oo_sub_g5_ndpsi_32(l_s,l_c,k_s,k_c,j_s,j_c,mu,eps)   :200-213; l may be k or j */
+int tmhip_M_oo_sub_g5_ndpsi_32(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c, tmhip_field *j_s,
+                               tmhip_field *j_c, float mu, float eps);
+/* Qtm_pm_ndpsi_32(l_s,l_c,k_s,k_c)   :215-263 with mubar, epsbar, invmaxev of tmhip_set_nd: four launches; l may be k */
+int tmhip_Qtm_pm_ndpsi_32(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tmhip_field *k_s, tmhip_field *k_c);
+/* rg_mixed_cg_her_nd(P_up,P_dn,Q_up,Q_dn,solver_params,max_iter,eps_sq,rel_prec,N,f,f32)   solver/rg_mixed_cg_her_nd.c:189-341 with
+ * f = Qtm_pm_ndpsi, f32 = Qtm_pm_ndpsi_32 (op must be TMHIP_ND_OP_QTM_PM: the clover doublet has no fp32 twin and is refused) and
+ * delta = solver_params.mcg_delta, on fp64 EO fields.  Zero start; fp32 inner loops with float scalars (non-pipelined, Fletcher-Reeves)
+ * until the iterated residual has dropped by delta, then P += x and the true residual in fp64; fp64 inner loops once
+ * iter_out >= N_outer - 2.  *iters = the reference's return value, iter_out + iter_in_sp + iter_in_dp or -1; the three counts are
+ * returned as well (each pointer may be NULL).  Sums over the two flavours are added before the scalar step; fp32 sums accumulate in
+ * double and are then rounded. */
+int tmhip_rg_mixed_cg_her_nd(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_field *Q_up, tmhip_field *Q_dn, int max_iter, double eps_sq,
+                             int rel_prec, int N, int op, double delta, int *iters, int *iter_out, int *iter_in_sp, int *iter_in_dp);
 /* sw_deriv_nd(ieo)   operator/clover_deriv.c:156-243: swp += (1+T) sw_inv_nd summed over the chiralities, swm += their difference */
 int tmhip_sw_deriv_nd(tmhip_ctx *ctx, int ieo);
 /* The monomial of type NDCLOVERRAT (monomial/ndrat_monomial.c): the bodies of tmhip_ndrat_* with Qsw_pm_ndpsi, Qsw_tau1_sub_const_ndpsi and
@@ -890,7 +912,9 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *   "cg_self" 1 (default) | 0: small unsplit lattices (the hop-split stencil) -- the fused CG iteration adds up its partial sums inside the residual stencil
  *                (alpha) and the (P, p) kernel (stopping test, beta) instead of two one-block sum + scalar kernels in between
  *   "nd_fused" 1 (default) | 0: the doublet operators (tmhip_*_ndpsi, the nd solvers) -- 1: one stencil per hop for both flavours with the
- *                flavour mixing in its epilogue; 0: two single-flavour stencils per hop and a mixing pass
+ *                flavour mixing in its epilogue; 0: two single-flavour stencils per hop and a mixing pass.  It sets
+ *                the form of the fp32 doublet (tmhip_Qtm_pm_ndpsi_32, the inner loops of tmhip_rg_mixed_cg_her_nd) as well, whose default
+ *                is the faster form at 32^4 of profiles/r20_nd32_speed.log: 1
  *   "rat_batch" shifts per group of the rat / ndrat force (clamped to [1, 32], default 12, the fastest of 1 / 2 / 4 / 12
  *                measured at 16^4 and 32^4 with np = 12, profiles/r08_rat_speed.log): one tmhip_deriv_Sb_batch launch per parity and group
  *                and, for the clover types (ndcloverrat, cloverrat), one tmhip_sw_spinor_eo_batch launch per parity and group; 1: the per-call

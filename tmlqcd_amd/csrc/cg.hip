@@ -9,50 +9,9 @@
 //
 // Shared by the three solvers of this file (cg_her, mixed_cg_her, rg_mixed_cg_her): the polling loop (tmhip_poll_loop,
 // tmhip_internal.h -- also the loop of nd.hip and mms.hip), the iteration with the vector updates in kernels of their own
-// (cg_enqueue_iteration) and the iteration with everything in stencil epilogues (cg_enqueue_fused_qtm).
-#include "tmhip_internal.h"
-
-static inline v4f *F4(tmhip_field *f) { return reinterpret_cast<v4f *>(f->d32); }   // fp32 field as six float4 planes
-
-struct CgState {
-  double normsq, pro, err, alpha, beta, squarenorm, eps_sq;
-  int rel_prec, done, iters, it;
-  // inner loop of mixed_cg_her (mixed_cg_her.c:141): stop when err <= innereps * sqnrm_outer, after max_inner
-  // iterations, or when 1.3 err already meets the outer target
-  int inner; int max_inner; double innereps, sqnrm_outer;
-  // inner loops of rg_mixed_cg_her (rg_mixed_cg_her.c:74-176), inner = 2 (float scalars) / 3 (double scalars):
-  // run while rho > delta * rhomax and iter_base + j <= max_total; leave early when 1.3 rho < eps_sq
-  double delta, rhomax; int iter_base, max_total;
-  // fused Qtm_pm_psi iteration: alpha is known (and P += alpha p still owed) between the two scalar updates
-  int x_pending;
-};
-
-// two copies of the state (the self-summing small-lattice iteration reads one and writes the other) and {pro, alpha} of the running iteration
-static int cg_state_alloc(tmhip_ctx *ctx) {
-  if (ctx->cg_state) return 0;
-  TMHIP_CHECK(hipMalloc(&ctx->cg_state, 2 * sizeof(CgState) + 2 * sizeof(double)));
-  TMHIP_CHECK(hipMemsetAsync(ctx->cg_state, 0, 2 * sizeof(CgState) + 2 * sizeof(double), ctx->stream));
-  return 0;
-}
-
-__device__ __forceinline__ void cg_block_reduce_store(double v, double *partials) {
-  __shared__ double wsum[LA_BS / 64];
-  v = tmhip_wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) wsum[w] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < LA_BS / 64; k++) s += wsum[k];
-    partials[blockIdx.y * gridDim.x + blockIdx.x] = s;
-  }
-}
-
-// The field kernels are written once for both precisions: V = v2d (fp64 field, twelve planes of complex doubles) or v4f (fp32
-// field, six planes of component pairs); scalars have the element type, sums are accumulated in double.
-__device__ __forceinline__ double la_dot(v2d a, v2d b) { return a.x * b.x + a.y * b.y; }
-__device__ __forceinline__ double la_dot(v4f a, v4f b) { return ((double)a.x * b.x + (double)a.y * b.y) + ((double)a.z * b.z + (double)a.w * b.w); }
+// (cg_enqueue_iteration) and the iteration with everything in stencil epilogues (cg_enqueue_fused_qtm).  The state block, its scalar
+// step and the restart logic of the reliable-update solver live in cg_common.h: the doublet's rg_mixed_cg_her_nd (nd32.hip) runs on them too.
+#include "cg_common.h"
 
 // pro = <sf2, sf0>   (cg_her.c:93)
 template <class V>
@@ -186,7 +145,6 @@ __global__ __launch_bounds__(LA_BS) void cg_xp_self_kernel(v2d *__restrict__ X, 
 }
 
 // fixed-order sum of the per-block partials into *out (same scheme as linalg.hip)
-#define CG_SUM_BS 1024   // one block; the fused stencils deliver one partial per wave (8192 at 32^4), so use the widest block
 // (no look at st->done: after convergence the sum is computed and ignored, which is cheaper than a dependent load in front of it)
 __global__ __launch_bounds__(CG_SUM_BS) void cg_sum_kernel(const double *__restrict__ partials, int n, double *out, const CgState *st) {
   __shared__ double sm[CG_SUM_BS / 64];
@@ -200,58 +158,6 @@ __global__ __launch_bounds__(CG_SUM_BS) void cg_sum_kernel(const double *__restr
 #pragma unroll
     for (int w = 0; w < CG_SUM_BS / 64; w++) tot += sm[w];
     *out = tot;
-  }
-}
-
-// WHICH 0: after the dot  -> alpha = normsq / pro            (cg_her.c:93-94)
-// WHICH 1: after |sf0|^2  -> stopping test, beta, normsq      (cg_her.c:101-126)
-template <int WHICH>
-__device__ __forceinline__ void cg_scalar_update(CgState *st, const double *sum, double *hist, int hist_len) {
-  if (WHICH == 0) {
-    st->pro = *sum;
-    if (st->inner == 2 || st->inner == 1) st->alpha = (double)((float)st->normsq / (float)st->pro);   // float pro, alpha_cg: rg_mixed_cg_her.c:126, mixed_cg_her.c:67-69,127-128
-    else st->alpha = st->normsq / st->pro;
-    st->x_pending = 1;
-  } else if (st->inner >= 2) {
-    st->it += 1;
-    bool stop;
-    if (st->inner == 2) {          // rg_mixed_cg_her.c:122-145, scalars in float like the reference
-      const float rho = (float)*sum, eps = (float)st->eps_sq, delta = (float)st->delta;
-      float rhomax = (float)st->rhomax;
-      st->err = rho;
-      st->beta = (double)(rho / (float)st->normsq);
-      st->normsq = rho;
-      stop = 1.3 * rho < eps;
-      if (!stop) {
-        if (rho > rhomax) rhomax = rho;
-        st->rhomax = rhomax;
-        stop = !(rho > delta * rhomax && st->it + st->iter_base <= st->max_total);
-      }
-    } else {                       // inner_loop_high, rg_mixed_cg_her.c:74-108
-      const double rho = *sum;
-      st->err = rho;
-      st->beta = rho / st->normsq;
-      st->normsq = rho;
-      stop = 1.3 * rho < st->eps_sq;
-      if (!stop) {
-        if (rho > st->rhomax) st->rhomax = rho;
-        stop = !(rho > st->delta * st->rhomax && st->it + st->iter_base <= st->max_total);
-      }
-    }
-    if (stop) { st->done = 1; st->iters = st->it; }
-  } else {
-    const double err = st->inner ? (double)(float)*sum : *sum;   // mixed_cg_her.c:67-69: err, beta_cg, sqnrm2 are floats in the inner loop
-    st->err = err;
-    st->it += 1;
-    if (hist && st->it - 1 < hist_len) hist[st->it - 1] = err;
-    bool conv;
-    if (st->inner)
-      conv = (err <= st->innereps * st->sqnrm_outer) || (st->it - 1 == st->max_inner) ||
-             ((1.3 * err <= st->eps_sq) && (st->rel_prec == 0)) || ((1.3 * err <= st->eps_sq * st->squarenorm) && (st->rel_prec == 1));
-    else
-      conv = ((err <= st->eps_sq) && (st->rel_prec == 0)) || ((err <= st->eps_sq * st->squarenorm) && (st->rel_prec == 1));
-    if (conv) { st->done = 1; st->iters = st->it; }
-    else { st->beta = st->inner ? (double)((float)err / (float)st->normsq) : err / st->normsq; st->normsq = err; }
   }
 }
 
@@ -272,35 +178,7 @@ __global__ __launch_bounds__(64) void cg_scalar_kernel(CgState *st, const double
   if (l < NW) reinterpret_cast<double *>(st)[l] = reinterpret_cast<const double *>(&ls)[l];
 }
 
-// single rank: the fixed-order sum of the partials and the scalar update in one launch (no all-reduce in between)
-template <int WHICH>
-__global__ __launch_bounds__(CG_SUM_BS) void cg_sum_scalar_kernel(const double *__restrict__ partials, int n, double *out, CgState *st, double *hist,
-                                                                  int hist_len) {
-  // The state is fetched into LDS by the last wave while the others are already loading partials: the scalar update then works
-  // on LDS instead of walking a chain of dependent global loads (done, inner, normsq, ...) after the reduction.
-  static_assert(sizeof(CgState) % sizeof(double) == 0 && sizeof(CgState) / sizeof(double) <= 64, "CgState is copied as doubles by one wave");
-  constexpr int NW = sizeof(CgState) / sizeof(double);
-  __shared__ CgState ls;
-  __shared__ double sm[CG_SUM_BS / 64];
-  const int lw = (int)threadIdx.x - (CG_SUM_BS - 64);
-  if (lw >= 0 && lw < NW) reinterpret_cast<double *>(&ls)[lw] = reinterpret_cast<const double *>(st)[lw];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < n; i += CG_SUM_BS) acc += partials[i];
-  acc = tmhip_wave_sum(acc);                       // fixed order: strided per-lane sums, butterfly per wave, then the 16 wave sums
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (ls.done) { if (WHICH == 0 && threadIdx.x == 0) st->x_pending = 0; return; }   // block-uniform
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-#pragma unroll
-    for (int w = 0; w < CG_SUM_BS / 64; w++) tot += sm[w];
-    *out = tot;
-    cg_scalar_update<WHICH>(&ls, &tot, hist, hist_len);
-  }
-  __syncthreads();
-  if (lw >= 0 && lw < NW) reinterpret_cast<double *>(st)[lw] = reinterpret_cast<const double *>(&ls)[lw];
-}
-
+// (single rank: cg_sum_scalar_kernel of cg_common.h, the fixed-order sum and the scalar update in one launch)
 // T-split ranks over the direct carrier: the same, with the sum over the ranks (tmhip_direct_sum_wave: one wave storing into every
 // rank's block) between the local sum and the scalar update -- ONE launch per reduction instead of sum kernel + all-reduce + scalar kernel
 template <int WHICH>
@@ -647,37 +525,34 @@ extern "C" int tmhip_mixed_cg_restarts(tmhip_ctx *ctx, int *inner_iters, int cap
 }
 
 // ------------------------------------------------------------------ reliable-update mixed CG
-// inner_loop / inner_loop_high of rg_mixed_cg_her.c:74-176 (non-pipelined, Fletcher-Reeves beta): returns j, updates *rho1
-static int rg_inner_loop(tmhip_ctx *ctx, int op, bool fp32, bool fused, CgFields f, double *rho1, double delta, double eps_sq, int N,
-                         int iter_base, int max_iter, int *j_out) {
-  CgState *st = (CgState *)ctx->cg_state;
-  CgState h;
-  memset(&h, 0, sizeof(h));
-  h.normsq = *rho1; h.rhomax = *rho1; h.delta = delta; h.eps_sq = eps_sq;
-  h.inner = fp32 ? 2 : 3; h.iter_base = iter_base; h.max_total = max_iter;
-  *j_out = 0;
-  // the reference tests the loop condition before the first iteration as well (rho = rhomax => rho > delta rhomax iff delta < 1)
-  const bool enter = fp32 ? ((float)*rho1 > (float)delta * (float)*rho1) : (*rho1 > delta * *rho1);
-  if (!enter || iter_base > max_iter) return 0;
-  TMHIP_CHECK(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  const int batch = ctx->opt_cg_batch > 0 ? ctx->opt_cg_batch : 4;
-  const double t_rel = delta * *rho1, t_abs = eps_sq / 1.3;      // the two exits of rg_mixed_cg_her.c:122-145 (rhomax >= rho1)
-  const double tgt = t_rel > t_abs ? t_rel : t_abs;              // as in tmhip_mixed_cg_her: poll every iteration close to the restart
-  // runs until `done`; the device-side test counts against max_iter itself, so more than max_iter + batch enqueued iterations is a failure
-  if (tmhip_poll_loop(ctx, max_iter + batch, false, batch, 1.0e3 * tgt, &st->done, &st->err, 0, true,
-                      [&](int) { return cg_enqueue_iteration(ctx, op, fp32, fused, f, st, N); })) return 1;
-  TMHIP_CHECK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-  TMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (!h.done) TMHIP_FAIL("rg_mixed_cg_her: inner loop did not terminate");
-  *j_out = h.iters;
-  *rho1 = h.normsq;
-  return 0;
-}
+// The single-flavour fields of rg_mixed_solve (cg_common.h): rg_mixed_cg_her.c:211-219
+struct RgFields {
+  tmhip_ctx *ctx; int op, N; bool fused;
+  tmhip_field *P, *Q;
+  tmhip_field *qhigh, *rhigh, *xhigh, *phigh, *q, *p, *r, *x;
+  int source_norm(double *s) { return tmhip_square_norm(ctx, Q, N, 1, s); }
+  int start() { return tmhip_field_zero(ctx, x) || tmhip_field_zero(ctx, P) || tmhip_assign(ctx, phigh, Q, N) || tmhip_assign(ctx, rhigh, Q, N); }
+  int rhigh_norm(double *s) { return tmhip_square_norm(ctx, rhigh, N, 1, s); }
+  int restart32() { return tmhip_assign_to_32(ctx, r, rhigh, N) || tmhip_assign_to_32(ctx, p, rhigh, N); }
+  int zero_x32() { return tmhip_field_zero(ctx, x); }
+  int loop32(double *rho, double delta, double eps, int base, int max_iter, int *j) {
+    CgFields f = {x, p, q, r};
+    return rg_inner_loop(ctx, "rg_mixed_cg_her", true, rho, delta, eps, base, max_iter, j,
+                         [&](CgState *st) { return cg_enqueue_iteration(ctx, op, true, fused, f, st, N); });
+  }
+  int loop64(double *rho, double delta, double eps, int base, int max_iter, int *j) {
+    CgFields f = {xhigh, phigh, qhigh, rhigh};
+    return rg_inner_loop(ctx, "rg_mixed_cg_her", false, rho, delta, eps, base, max_iter, j,
+                         [&](CgState *st) { return cg_enqueue_iteration(ctx, op, false, false, f, st, N); });
+  }
+  int accumulate32() { return tmhip_add_from_32(ctx, P, x, N); }
+  int true_residual(double *s) { return tmhip_apply_op(ctx, op, qhigh, P) || tmhip_diff(ctx, rhigh, Q, qhigh, N) || tmhip_square_norm(ctx, rhigh, N, 1, s); }
+  int restart64() { return tmhip_assign(ctx, phigh, rhigh, N) || tmhip_field_zero(ctx, xhigh); }
+  int accumulate64() { return tmhip_assign_add_mul_r(ctx, P, xhigh, 1.0, N); }
+};
 
-/* solver/rg_mixed_cg_her.c:180-347.  fp32 CG with true reliable updates: the inner loop runs until the iterated
- * residual has dropped by `delta` relative to its maximum since the last update, then the solution is accumulated
- * and the residual recomputed in fp64; when the outer-iteration estimate N_outer is nearly used up the solver
- * falls back to fp64 inner loops.  Returns the reference's count iter_out + iter_in_sp + iter_in_dp, or -1. */
+/* solver/rg_mixed_cg_her.c:180-347: rg_mixed_solve (cg_common.h) on single-flavour fields.  Returns the reference's count
+ * iter_out + iter_in_sp + iter_in_dp, or -1. */
 extern "C" int tmhip_rg_mixed_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field *Q, int max_iter, double eps_sq, int rel_prec, int N,
                                      int op, double delta_in, int *iters, int *iter_out_p, int *iter_sp_p, int *iter_dp_p) {
   if (!P || !Q || P->kind != Q->kind || P->prec || Q->prec) TMHIP_FAIL("rg_mixed_cg_her needs two fp64 fields of one kind");
@@ -690,68 +565,8 @@ extern "C" int tmhip_rg_mixed_cg_her(tmhip_ctx *ctx, tmhip_field *P, tmhip_field
   if (!ctx->sf_extra && tmhip_field_alloc(ctx, TMHIP_FIELD_EO, &ctx->sf_extra)) return 1;
   const bool split = ctx->g.nproc_t > 1 || ctx->loopback;
   const bool fused = ctx->opt_cg_fused_dot && tmhip_fused_dot32_ok(ctx) && (!split || ctx->opt_cg_fused_dot >= 2);   // the older mode-0 fusion is unsplit only
-  const float delta = (float)delta_in;                                /* :185 */
-  int iter_in_sp = 0, iter_in_dp = 0, iter_out = 0, high_control = 0, j;
-  double rho_dp, sourcesquarenorm, target_eps_sq;
-  float rho_sp;
-  tmhip_field *qhigh = ctx->sf[0], *rhigh = ctx->sf[1], *xhigh = ctx->sf[2], *phigh = ctx->sf_extra;   /* :211-214 */
-  tmhip_field *q = ctx->sf32[0], *p = ctx->sf32[1], *r = ctx->sf32[2], *x = ctx->sf32[3];             /* :216-219 */
-  if (tmhip_square_norm(ctx, Q, N, 1, &sourcesquarenorm)) return 1;
-  target_eps_sq = rel_prec == 1 ? eps_sq * sourcesquarenorm : eps_sq;  /* :225-232 */
-  const int N_outer = (int)ceil(log10(sourcesquarenorm * delta / target_eps_sq));   /* :236 */
-  if (tmhip_field_zero(ctx, x) || tmhip_field_zero(ctx, P)) return 1;
-  if (tmhip_assign(ctx, phigh, Q, N) || tmhip_assign(ctx, rhigh, Q, N)) return 1;
-  if (tmhip_square_norm(ctx, rhigh, N, 1, &rho_dp)) return 1;
-  if (tmhip_assign_to_32(ctx, r, rhigh, N)) return 1;
-  rho_sp = (float)rho_dp;
-  if (tmhip_assign_to_32(ctx, p, rhigh, N)) return 1;                   /* assign_32(p, r): same rounding of the same source */
-#define RG_SP_LOOP()                                                                                                   \
-  do {                                                                                                                 \
-    double rho1 = rho_sp;                                                                                              \
-    CgFields f = {x, p, q, r};                                                                                         \
-    if (rg_inner_loop(ctx, op, true, fused, f, &rho1, delta, (double)(float)target_eps_sq, N,                          \
-                      iter_out + iter_in_sp + iter_in_dp, max_iter, &j)) return 1;                                     \
-    rho_sp = (float)rho1; iter_in_sp += j;                                                                             \
-  } while (0)
-#define RG_RETURN(val)                                                                                                 \
-  do {                                                                                                                 \
-    *iters = (val);                                                                                                    \
-    if (iter_out_p) *iter_out_p = iter_out;                                                                            \
-    if (iter_sp_p) *iter_sp_p = iter_in_sp;                                                                            \
-    if (iter_dp_p) *iter_dp_p = iter_in_dp;                                                                            \
-    return 0;                                                                                                          \
-  } while (0)
-  RG_SP_LOOP();
-  for (iter_out = 1; iter_out < N_outer; ++iter_out) {
-    if (high_control == 0) {                                           /* :260-269 */
-      if (tmhip_add_from_32(ctx, P, x, N)) return 1;
-      if (tmhip_apply_op(ctx, op, qhigh, P)) return 1;
-      if (tmhip_diff(ctx, rhigh, Q, qhigh, N)) return 1;
-      if (tmhip_square_norm(ctx, rhigh, N, 1, &rho_dp)) return 1;
-    }
-    if (high_control == 1) {                                           /* :272-286 double precision fail-safe */
-      if (tmhip_assign(ctx, phigh, rhigh, N) || tmhip_field_zero(ctx, xhigh)) return 1;
-      CgFields f = {xhigh, phigh, qhigh, rhigh};
-      if (rg_inner_loop(ctx, op, false, false, f, &rho_dp, delta, target_eps_sq, N, iter_out + iter_in_sp + iter_in_dp, max_iter, &j)) return 1;
-      iter_in_dp += j;
-      rho_sp = (float)rho_dp;
-      if (tmhip_assign_add_mul_r(ctx, P, xhigh, 1.0, N)) return 1;     /* add(P, P, xhigh) */
-      if (tmhip_apply_op(ctx, op, qhigh, P)) return 1;
-      if (tmhip_diff(ctx, rhigh, Q, qhigh, N)) return 1;
-      if (tmhip_square_norm(ctx, rhigh, N, 1, &rho_dp)) return 1;
-    }
-    const int total = iter_in_sp + iter_in_dp + iter_out;
-    if (rho_dp <= target_eps_sq || total >= max_iter) RG_RETURN(total >= max_iter ? -1 : total);   /* :294-307 */
-    if (iter_out >= N_outer - 2) {                                     /* :310-313 */
-      high_control = 1;
-      continue;
-    }
-    if (tmhip_assign_to_32(ctx, r, rhigh, N) || tmhip_assign_to_32(ctx, p, rhigh, N)) return 1;   /* :315-318 */
-    rho_sp = (float)rho_dp;
-    if (tmhip_field_zero(ctx, x)) return 1;
-    RG_SP_LOOP();
-  }
-  RG_RETURN(-1);                                                       /* :326-330 convergence failure */
-#undef RG_SP_LOOP
-#undef RG_RETURN
+  RgFields f = {ctx, op, N, fused, P, Q,
+                ctx->sf[0], ctx->sf[1], ctx->sf[2], ctx->sf_extra,                /* qhigh, rhigh, xhigh, phigh  :211-214 */
+                ctx->sf32[0], ctx->sf32[1], ctx->sf32[2], ctx->sf32[3]};          /* q, p, r, x                  :216-219 */
+  return rg_mixed_solve(f, max_iter, eps_sq, rel_prec, delta_in, iters, iter_out_p, iter_sp_p, iter_dp_p);
 }

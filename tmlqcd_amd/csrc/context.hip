@@ -155,7 +155,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
     ctx->flag_timeout_ticks = (unsigned long long)(sec * 1.0e8);
   }
   ctx->opt_stg = 1; ctx->opt_stg32 = 0; ctx->opt_hopsplit = -1; ctx->opt_occ32 = 0; ctx->opt_recon = 0; ctx->opt_swall_order = 2; ctx->opt_swterm_order = 1; ctx->opt_gauge_cache = -1;
-  ctx->opt_nd_fused = 1; ctx->invmaxev = 1.0;
+  ctx->opt_nd_fused = 1; ctx->opt_nd_fused32 = 1; ctx->invmaxev = 1.0;   // fp32: the faster form at 32^4 (profiles/r20_nd32_speed.log)
   ctx->opt_rat_batch = 12;
   ctx->opt_poly_batch = 12;
   ctx->opt_ratcor_fused = 1;
@@ -226,6 +226,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   tmhip_poly_destroy(ctx);
   tmhip_rat_destroy(ctx);
   tmhip_nd_destroy(ctx);
+  tmhip_nd32_destroy(ctx);
   tmhip_mms_destroy(ctx);
   tmhip_flow_destroy(ctx);
   tmhip_meas_destroy(ctx);
@@ -351,7 +352,7 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "lds")) { if (value < 0 || value > 1) TMHIP_FAIL("lds must be 0 (gather kernel) or 1 (per-wave LDS staging of the own-site spinors)"); ctx->opt_stg = value; }
   else if (!strcmp(name, "cg_self")) ctx->opt_cg_self = value != 0;
   else if (!strcmp(name, "cg_sync")) ctx->opt_cg_sync = value;
-  else if (!strcmp(name, "nd_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_fused must be 0 (two single-flavour stencils + a mixing pass) or 1 (doublet stencil)"); ctx->opt_nd_fused = value; }
+  else if (!strcmp(name, "nd_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_fused must be 0 (two single-flavour stencils + a mixing pass) or 1 (doublet stencil)"); ctx->opt_nd_fused = ctx->opt_nd_fused32 = value; }
   else if (!strcmp(name, "rat_batch")) ctx->opt_rat_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
   else if (!strcmp(name, "poly_batch")) ctx->opt_poly_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
   else if (!strcmp(name, "ratcor_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("ratcor_fused must be 0 (the reference's call sequence on the single kernels) or 1 (rat_sum and diff_sqnorm)"); ctx->opt_ratcor_fused = value; }

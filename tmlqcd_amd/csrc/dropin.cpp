@@ -72,7 +72,7 @@ struct Session {
   bool deriv_pending = false;      // a force is accumulating in the device's derivative, not yet in hf->derivative
   bool deriv_made = false;         // some force has run on the device: its derivative accumulator exists
   tmhip_field *full_tmp = nullptr; // FULL-lattice scratch of Q_pm_psi / D_dagg_psi (tm_operators.c:380-397)
-  tmhip_field *f32[3] = {nullptr, nullptr, nullptr};   // device fields of the fp32 host-pointer symbols (Hopping_Matrix_32 ...)
+  tmhip_field *f32[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // device fields of the fp32 host-pointer symbols (Hopping_Matrix_32 ...)
 
   tmhip_ctx *context() {
     if (!c) {
@@ -332,7 +332,7 @@ void tmlqcd_hip_finalize(void) {
   if (!ses.c) return;
   release_all_mirrors(ses.c);
   if (ses.full_tmp) { tmhip_field_free(ses.c, ses.full_tmp); ses.full_tmp = nullptr; }
-  for (int k = 0; k < 3; k++) if (ses.f32[k]) { tmhip_field_free(ses.c, ses.f32[k]); ses.f32[k] = nullptr; }
+  for (int k = 0; k < 6; k++) if (ses.f32[k]) { tmhip_field_free(ses.c, ses.f32[k]); ses.f32[k] = nullptr; }
   tmhip_destroy(ses.c);
   ses.c = nullptr;
   ses.gauge_uploaded = false;
@@ -836,6 +836,30 @@ void Qtm_pm_psi_32(spinor32 *const l, spinor32 *const k) {
   CK(tmhip_Qtm_pm_psi_32(c, fl, fk));
   CK(tmhip_field_download32(c, fl, l, VOLUME / 2));
 }
+// The fp32 doublet (operator/tm_operators_nd_32.c): inputs in pool fields 0..3, outputs in 4, 5, so l may be k or j as in the reference
+void Qtm_pm_ndpsi_32(spinor32 *const l_s, spinor32 *const l_c, spinor32 *const k_s, spinor32 *const k_c) {   /* :215-263 */
+  tmhip_ctx *c = ses.refresh_nd("Qtm_pm_ndpsi_32");
+  tmhip_field *fks = in32(c, 0, k_s, VOLUME / 2), *fkc = in32(c, 1, k_c, VOLUME / 2), *fls = f32(c, 4), *flc = f32(c, 5);
+  CK(tmhip_Qtm_pm_ndpsi_32(c, fls, flc, fks, fkc));
+  CK(tmhip_field_download32(c, fls, l_s, VOLUME / 2));
+  CK(tmhip_field_download32(c, flc, l_c, VOLUME / 2));
+}
+void M_ee_inv_ndpsi_32(spinor32 *const l_s, spinor32 *const l_c, spinor32 *const k_s, spinor32 *const k_c, const float mu, const float eps) {   /* :137-149 */
+  tmhip_ctx *c = ses.refresh_nd("M_ee_inv_ndpsi_32");
+  tmhip_field *fks = in32(c, 0, k_s, VOLUME / 2), *fkc = in32(c, 1, k_c, VOLUME / 2), *fls = f32(c, 4), *flc = f32(c, 5);
+  CK(tmhip_M_ee_inv_ndpsi_32(c, fls, flc, fks, fkc, mu, eps));
+  CK(tmhip_field_download32(c, fls, l_s, VOLUME / 2));
+  CK(tmhip_field_download32(c, flc, l_c, VOLUME / 2));
+}
+void M_oo_sub_g5_ndpsi_32(spinor32 *const l_s, spinor32 *const l_c, spinor32 *const k_s, spinor32 *const k_c, spinor32 *const j_s,
+                          spinor32 *const j_c, const float mu, const float eps) {   /* :200-213 */
+  tmhip_ctx *c = ses.refresh_nd("M_oo_sub_g5_ndpsi_32");
+  tmhip_field *fks = in32(c, 0, k_s, VOLUME / 2), *fkc = in32(c, 1, k_c, VOLUME / 2), *fjs = in32(c, 2, j_s, VOLUME / 2), *fjc = in32(c, 3, j_c, VOLUME / 2);
+  tmhip_field *fls = f32(c, 4), *flc = f32(c, 5);
+  CK(tmhip_M_oo_sub_g5_ndpsi_32(c, fls, flc, fks, fkc, fjs, fjc, mu, eps));
+  CK(tmhip_field_download32(c, fls, l_s, VOLUME / 2));
+  CK(tmhip_field_download32(c, flc, l_c, VOLUME / 2));
+}
 float square_norm_32(const spinor32 *const P, const int N, const int parallel) {   /* linalg/square_norm_32.c:95 */
   tmhip_ctx *c = ses.refresh(false);
   need_N32(N, "square_norm_32");
@@ -1039,6 +1063,20 @@ int rg_mixed_cg_her(spinor *const P, spinor *const Q, tmlqcd_solver_params solve
   apply(c, TMHIP_FIELD_EO, P, Q, nullptr, [&](Ctx, Fld fp, Fld fq, Fld) {
     CK(tmhip_rg_mixed_cg_her(c, fp, fq, max_iter, eps_sq, rel_prec, N, op, solver_params.mcg_delta, &iters, nullptr, nullptr, nullptr));
   });
+  return iters;
+}
+
+/* solver/rg_mixed_cg_her_nd.c:189-341 with (f, f32) = (Qtm_pm_ndpsi, Qtm_pm_ndpsi_32), device-resident; residency as cg_her_nd */
+int rg_mixed_cg_her_nd(spinor *const P_up, spinor *const P_dn, spinor *const Q_up, spinor *const Q_dn, tmlqcd_solver_params solver_params,
+                       const int max_iter, const double eps_sq, const int rel_prec, const int N, matrix_mult_nd f, matrix_mult_nd32) {
+  const int op = dev_nd_op_of(f, N);
+  if (op < 0 || !tmhip_op_taken(tmhip_nd_op_row_of(op), TMHIP_S_MIXED)) die("rg_mixed_cg_her_nd: only f = Qtm_pm_ndpsi on VOLUME/2 sites runs on the device");
+  tmhip_ctx *c = ses.refresh_nd("rg_mixed_cg_her_nd");
+  tmhip_field *fqu = in(c, Q_up, TMHIP_FIELD_EO), *fqd = in(c, Q_dn, TMHIP_FIELD_EO);
+  tmhip_field *fpu = out(c, P_up, TMHIP_FIELD_EO), *fpd = out(c, P_dn, TMHIP_FIELD_EO);   /* zero start: P is written only */
+  int iters = -1;
+  CK(tmhip_rg_mixed_cg_her_nd(c, fpu, fpd, fqu, fqd, max_iter, eps_sq, rel_prec, N, op, solver_params.mcg_delta, &iters, nullptr, nullptr, nullptr));
+  done(c, P_up); done(c, P_dn);
   return iters;
 }
 

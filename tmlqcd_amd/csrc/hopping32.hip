@@ -16,26 +16,7 @@
 #define HOP_SPINOR_PACKED 1
 namespace hop32 {
 TMHIP_SCALAR_COMPLEX_OPS(v2f, float)
-typedef float vf4 __attribute__((ext_vector_type(4)));
-template <bool NT> __device__ __forceinline__ void ld6(V2T *s, const ET *f, size_t stride, int j, int blk) {
-  const vf4 *p = reinterpret_cast<const vf4 *>(f);
-#pragma unroll
-  for (int m = 0; m < 3; m++) {
-    const vf4 *q = p + (size_t)(3 * blk + m) * stride + j;
-    const vf4 v = NT ? __builtin_nontemporal_load(q) : *q;
-    s[2 * m] = V2T{v.x, v.y}; s[2 * m + 1] = V2T{v.z, v.w};
-  }
-}
-template <bool NT> __device__ __forceinline__ void st6(ET *f, size_t stride, int j, int blk, const V2T *s) {
-  vf4 *p = reinterpret_cast<vf4 *>(f);
-#pragma unroll
-  for (int m = 0; m < 3; m++) {
-    const vf4 v = vf4{s[2 * m].x, s[2 * m].y, s[2 * m + 1].x, s[2 * m + 1].y};
-    vf4 *q = p + (size_t)(3 * blk + m) * stride + j;
-    if (NT) __builtin_nontemporal_store(v, q);
-    else *q = v;
-  }
-}
+#include "spinor32_io.inc"   // vf4, ld6, st6
 // system-scope (sc0 sc1) loads of the six components 6 blk .. 6 blk + 5: see hopping_common.h
 __device__ __forceinline__ void ld6_fresh(V2T *s, const ET *f, size_t stride, int j, int blk) {
   const vf4 *p = reinterpret_cast<const vf4 *>(f);

@@ -8,7 +8,8 @@
 // and applied to the two projected half-spinors, and the mixing runs in the epilogue on the two accumulators, so a
 // Qtm_pm_ndpsi is four launches and nothing else.  The flavour swaps the reference writes as argument orders (tau_1) are
 // pointer choices here.  Option "nd_fused" 0 builds the same operator from two single-flavour stencil launches (EPI_STORE)
-// per hop plus one mixing pass (nd_mix_kernel) -- the A/B of DESIGN.md section 4.
+// per hop plus one mixing pass (nd_mix_kernel) -- the A/B of DESIGN.md section 4.  What does not depend on the precision -- the spin
+// algebra of a hop, the mixing, the neighbour indices, the grid rule -- lives in nd_common.h and serves the fp32 twin (nd32.hip) too.
 //
 // The solvers share one device-resident engine (nd_solve): the coefficients of the multi-shift recurrences live in a
 // MshiftState and are updated by one-block kernels (the recurrences themselves: mshift.h, shared with mms.hip), the field
@@ -16,21 +17,13 @@
 // cg_her_nd is the one-shift, sigma = 0 case with its own start (P != 0 allowed) and return convention.
 #include "hopping_common.h"
 #include "mshift.h"
+#include "nd_common.h"
 
 namespace {
 TMHIP_SCALAR_COMPLEX_OPS(v2d, double)
 TMHIP_SPINOR_IO_PLANES
 
-__device__ __forceinline__ v2d cfma(v2d a, v2d b, v2d c) {   // c + a*b
-  const v2d t = __builtin_elementwise_fma(v2d{a.x, a.x}, b, c);
-  return __builtin_elementwise_fma(v2d{-a.y, a.y}, v2d{b.y, b.x}, t);
-}
-__device__ __forceinline__ v2d cfmac(v2d a, v2d b, v2d c) {  // c + conj(a)*b
-  const v2d t = __builtin_elementwise_fma(v2d{a.x, a.x}, b, c);
-  return __builtin_elementwise_fma(v2d{a.y, -a.y}, v2d{b.y, b.x}, t);
-}
-__device__ __forceinline__ v2d cmul(v2d a, v2d b) { return __builtin_elementwise_fma(v2d{-a.y, a.y}, v2d{b.y, b.x}, v2d{a.x, a.x} * b); }
-__device__ __forceinline__ v2d cmulc(v2d a, v2d b) { return __builtin_elementwise_fma(v2d{a.y, -a.y}, v2d{b.y, b.x}, v2d{a.x, a.x} * b); }
+using ndc::cfma; using ndc::cfmac; using ndc::cmul; using ndc::cmulc; using ndc::nd_project; using ndc::nd_apply;   // nd_common.h
 
 enum { ND_EE_INV = 0, ND_OO = 1, ND_OO_DOT = 2, ND_OO_SUBC = 3,
        // the clover doublet (Qsw_*_ndpsi): the same four roles, then the two halves of NDSW_EE on their own (site-local kernel only)
@@ -50,60 +43,6 @@ struct NdArgs {
   const v2d *sw, *swi;       // NDSW_*: 1+T of the output sites' parity [6][9][gs], sw_inv_nd [8][9][gs] (block 2a + chirality)
   double cz[2];              // ND_OO_SUBC: out -= cz (.) the OTHER flavour's k (Q_tau1_sub_const_ndpsi: its k arrive swapped)
 };
-
-// projection (1 -+ gamma_mu) of one spinor for hop D = 2 mu + (0: +mu, 1: -mu); the same lines as hop_dir (hopping_impl.inc)
-template <int D>
-__device__ __forceinline__ void nd_project(const v2d (&s)[12], v2d (&pa)[3], v2d (&pb)[3]) {
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const v2d s0 = s[c], s1 = s[3 + c], s2 = s[6 + c], s3 = s[9 + c];
-    if (D == 0) { pa[c] = s0 + s2; pb[c] = s1 + s3; }
-    if (D == 1) { pa[c] = s0 - s2; pb[c] = s1 - s3; }
-    if (D == 2) { pa[c] = v2d{s0.x - s3.y, s0.y + s3.x}; pb[c] = v2d{s1.x - s2.y, s1.y + s2.x}; }
-    if (D == 3) { pa[c] = v2d{s0.x + s3.y, s0.y - s3.x}; pb[c] = v2d{s1.x + s2.y, s1.y - s2.x}; }
-    if (D == 4) { pa[c] = s0 + s3; pb[c] = s1 - s2; }
-    if (D == 5) { pa[c] = s0 - s3; pb[c] = s1 + s2; }
-    if (D == 6) { pa[c] = v2d{s0.x - s2.y, s0.y + s2.x}; pb[c] = v2d{s1.x + s3.y, s1.y - s3.x}; }
-    if (D == 7) { pa[c] = v2d{s0.x + s2.y, s0.y - s2.x}; pb[c] = v2d{s1.x - s3.y, s1.y + s3.x}; }
-  }
-}
-
-// link times half-spinor, ka, and the reconstruction into the accumulator
-template <int D>
-__device__ __forceinline__ void nd_apply(v2d (&acc)[12], const v2d (&u)[9], const v2d (&pa)[3], const v2d (&pb)[3], v2d ka) {
-  v2d ca[3], cb[3];
-  if ((D & 1) == 0) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      ca[r] = cfma(u[3 * r + 2], pa[2], cfma(u[3 * r + 1], pa[1], cmul(u[3 * r], pa[0])));
-      cb[r] = cfma(u[3 * r + 2], pb[2], cfma(u[3 * r + 1], pb[1], cmul(u[3 * r], pb[0])));
-    }
-#pragma unroll
-    for (int r = 0; r < 3; r++) { ca[r] = cmul(ka, ca[r]); cb[r] = cmul(ka, cb[r]); }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      ca[r] = cfmac(u[6 + r], pa[2], cfmac(u[3 + r], pa[1], cmulc(u[r], pa[0])));
-      cb[r] = cfmac(u[6 + r], pb[2], cfmac(u[3 + r], pb[1], cmulc(u[r], pb[0])));
-    }
-#pragma unroll
-    for (int r = 0; r < 3; r++) { ca[r] = cmulc(ka, ca[r]); cb[r] = cmulc(ka, cb[r]); }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const v2d a = ca[c], b = cb[c];
-    acc[c] += a;
-    acc[3 + c] += b;
-    if (D == 0) { acc[6 + c] += a; acc[9 + c] += b; }
-    if (D == 1) { acc[6 + c] -= a; acc[9 + c] -= b; }
-    if (D == 2) { acc[9 + c] += v2d{a.y, -a.x}; acc[6 + c] += v2d{b.y, -b.x}; }
-    if (D == 3) { acc[9 + c] += v2d{-a.y, a.x}; acc[6 + c] += v2d{-b.y, b.x}; }
-    if (D == 4) { acc[9 + c] += a; acc[6 + c] -= b; }
-    if (D == 5) { acc[9 + c] -= a; acc[6 + c] += b; }
-    if (D == 6) { acc[6 + c] += v2d{a.y, -a.x}; acc[9 + c] += v2d{-b.y, b.x}; }
-    if (D == 7) { acc[6 + c] += v2d{-a.y, a.x}; acc[9 + c] += v2d{b.y, -b.x}; }
-  }
-}
 
 // one hop of both flavours: the link is read once
 template <int D, bool NT>
@@ -131,7 +70,6 @@ __device__ __forceinline__ double nd_epilogue(const NdArgs &a, int i, const v2d 
   double d = 0.0;
 #pragma unroll
   for (int b = 0; b < 2; b++) {       // spins 0, 1 | spins 2, 3
-    const v2d zs = v2d{1.0, b == 0 ? -mu : mu}, zc = v2d{1.0, b == 0 ? mu : -mu};
     v2d ks[6], kc[6], os[6], oc[6];
     if (EPI == ND_EE_INV) {
 #pragma unroll
@@ -139,18 +77,7 @@ __device__ __forceinline__ double nd_epilogue(const NdArgs &a, int i, const v2d 
     } else {
       ld6<false>(ks, a.k_s, ns, i, b); ld6<false>(kc, a.k_c, ns, i, b);
     }
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-      const v2d phi1 = cmul(zs, ks[c]) + eps * kc[c];   // _complex_times_vector + _vector_add_mul
-      const v2d phi2 = cmul(zc, kc[c]) + eps * ks[c];
-      if (EPI == ND_EE_INV) {
-        os[c] = a.nrm * phi1; oc[c] = a.nrm * phi2;
-      } else {
-        const v2d js = va[6 * b + c], jc = vb[6 * b + c];
-        os[c] = a.scale * (b == 0 ? phi1 - js : js - phi1);   // then mul_r(l, phmc_invmaxev, ..)
-        oc[c] = a.scale * (b == 0 ? phi2 - jc : jc - phi2);
-      }
-    }
+    ndc::nd_mix6<EPI == ND_EE_INV>(b, mu, eps, EPI == ND_EE_INV ? a.nrm : a.scale, ks, kc, &va[6 * b], &vb[6 * b], os, oc);
     if (EPI == ND_OO_SUBC) {          // l_strange -= Cpol z k_strange, l_charm -= Cpol z k_charm (tm_operators_nd.c:349-374); k_s, k_c hold (k_charm, k_strange)
       const v2d cz = v2d{a.cz[0], a.cz[1]};
 #pragma unroll
@@ -290,37 +217,22 @@ __device__ __forceinline__ void nd_hop_body(const NdArgs a) {
   const int i = bid * BS + (int)threadIdx.x;
   double d = 0.0;
   if (bid < a.map_nb && i < a.Vh) {
-    const int LZh = a.LZh;
-    const int k = i % LZh;
-    int r = i / LZh;
-    const int y = r % a.LY;
-    r /= a.LY;
-    const int x = r % a.LX;
-    const int t = r / a.LX;
-    const int o = (t + x + y + a.par_off) & 1;   // z = 2k + o  (geometry_eo.c:807-811)
-    const int XYZh = a.face, YZh = a.YZh;
-    const int jtp = (t + 1 < a.T) ? i + XYZh : i - (a.T - 1) * XYZh;
-    const int jtm = (t > 0) ? i - XYZh : i + (a.T - 1) * XYZh;
-    const int jxp = (x + 1 < a.LX) ? i + YZh : i - (a.LX - 1) * YZh;
-    const int jxm = (x > 0) ? i - YZh : i + (a.LX - 1) * YZh;
-    const int jyp = (y + 1 < a.LY) ? i + LZh : i - (a.LY - 1) * LZh;
-    const int jym = (y > 0) ? i - LZh : i + (a.LY - 1) * LZh;
-    const int jzp = o ? ((k + 1 < LZh) ? i + 1 : i - (LZh - 1)) : i;
-    const int jzm = o ? i : ((k > 0) ? i - 1 : i + (LZh - 1));
+    int j[8];
+    ndc::nd_neighbours(a, i, j);
     v2d aa[12], ab[12];
 #pragma unroll
     for (int c = 0; c < 12; c++) { aa[c] = czero(); ab[c] = czero(); }
     const v2d ka0 = cbcast(a.ka[0][0], a.ka[0][1]), ka1 = cbcast(a.ka[1][0], a.ka[1][1]);
     const v2d ka2 = cbcast(a.ka[2][0], a.ka[2][1]), ka3 = cbcast(a.ka[3][0], a.ka[3][1]);
     const size_t ns = (size_t)a.ns, gs = (size_t)a.gs;
-    nd_hop_dir<0, NT>(aa, ab, a.in_a, a.in_b, ns, jtp, a.gauge, gs, i, ka0);
-    nd_hop_dir<1, NT>(aa, ab, a.in_a, a.in_b, ns, jtm, a.gauge, gs, i, ka0);
-    nd_hop_dir<2, NT>(aa, ab, a.in_a, a.in_b, ns, jxp, a.gauge, gs, i, ka1);
-    nd_hop_dir<3, NT>(aa, ab, a.in_a, a.in_b, ns, jxm, a.gauge, gs, i, ka1);
-    nd_hop_dir<4, NT>(aa, ab, a.in_a, a.in_b, ns, jyp, a.gauge, gs, i, ka2);
-    nd_hop_dir<5, NT>(aa, ab, a.in_a, a.in_b, ns, jym, a.gauge, gs, i, ka2);
-    nd_hop_dir<6, NT>(aa, ab, a.in_a, a.in_b, ns, jzp, a.gauge, gs, i, ka3);
-    nd_hop_dir<7, NT>(aa, ab, a.in_a, a.in_b, ns, jzm, a.gauge, gs, i, ka3);
+    nd_hop_dir<0, NT>(aa, ab, a.in_a, a.in_b, ns, j[0], a.gauge, gs, i, ka0);
+    nd_hop_dir<1, NT>(aa, ab, a.in_a, a.in_b, ns, j[1], a.gauge, gs, i, ka0);
+    nd_hop_dir<2, NT>(aa, ab, a.in_a, a.in_b, ns, j[2], a.gauge, gs, i, ka1);
+    nd_hop_dir<3, NT>(aa, ab, a.in_a, a.in_b, ns, j[3], a.gauge, gs, i, ka1);
+    nd_hop_dir<4, NT>(aa, ab, a.in_a, a.in_b, ns, j[4], a.gauge, gs, i, ka2);
+    nd_hop_dir<5, NT>(aa, ab, a.in_a, a.in_b, ns, j[5], a.gauge, gs, i, ka2);
+    nd_hop_dir<6, NT>(aa, ab, a.in_a, a.in_b, ns, j[6], a.gauge, gs, i, ka3);
+    nd_hop_dir<7, NT>(aa, ab, a.in_a, a.in_b, ns, j[7], a.gauge, gs, i, ka3);
     d = nd_epilogue_any<EPI>(a, i, aa, ab);
   }
   if (nd_epi_dot(EPI)) tmhip_wave_partial(d, a.partials, blockIdx.x * (BS / 64) + (int)(threadIdx.x >> 6));
@@ -476,11 +388,8 @@ static void nd_fill(NdArgs &a, tmhip_ctx *ctx, int ieo) {
 
 template <int EPI, int BS>
 static void nd_launch_hop(tmhip_ctx *ctx, NdArgs a, int *npart) {
-  int nb = (ctx->Vh + BS - 1) / BS;
-  a.map_nb = nb;
-  if (ctx->opt_xcd && nb >= 64) { a.nxcd_chunk = (nb + 7) / 8; nb = 8 * a.nxcd_chunk; }
-  // the links stay in the Infinity Cache between calls while the gauge copy is small (the rule of hop_kernel's GAUX = -2)
-  const bool cached = ctx->opt_gauge_cache < 0 ? (size_t)2 * 72 * ctx->gs * sizeof(v2d) <= (size_t)200 << 20 : ctx->opt_gauge_cache != 0;
+  const int nb = ndc::nd_grid(ctx, BS, &a.map_nb, &a.nxcd_chunk);
+  const bool cached = ndc::nd_gauge_cached(ctx, sizeof(v2d));
   if constexpr (EPI >= NDSW_EE) {
     if (cached) hipLaunchKernelGGL((ndsw_hop_kernel<EPI, BS, false>), dim3(nb), dim3(BS), 0, ctx->stream, a);
     else hipLaunchKernelGGL((ndsw_hop_kernel<EPI, BS, true>), dim3(nb), dim3(BS), 0, ctx->stream, a);

@@ -37,7 +37,7 @@ enum { TMHIP_SW_NONE = 0, TMHIP_SW_TERM = 1, TMHIP_SW_TERM_MINUS_MU = 2 };
   X(MSW_PLUS,       Msw_plus_psi,        EO,     TERM,           0,    TMHIP_S_BICG)                      \
   X(D_PSI,          D_psi,               FULL,   NONE,           0,    TMHIP_S_BICG)
 #define TMHIP_ND_OP_TABLE(X)                                                                              \
-  X(QTM_PM,         Qtm_pm_ndpsi,        EO,     NONE,           0,    TMHIP_S_ND)                        \
+  X(QTM_PM,         Qtm_pm_ndpsi,        EO,     NONE,           1,    TMHIP_S_ND)                        \
   X(QSW_PM,         Qsw_pm_ndpsi,        EO,     TERM,           0,    TMHIP_S_ND)
 
 struct tmhip_op_row { int id; const char *name; int kind, clover, fp32, solvers; };

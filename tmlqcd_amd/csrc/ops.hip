@@ -38,8 +38,9 @@ int tmhip_ndsw_ready(tmhip_ctx *ctx, const char *who, bool need_inv) {
   return 0;
 }
 
-int tmhip_nd_op_check(tmhip_ctx *ctx, const char *who, int op) {
+int tmhip_nd_op_check(tmhip_ctx *ctx, const char *who, int op, int solver) {
   const tmhip_op_row *r = tmhip_nd_op_row_of(op);
   if (!r) TMHIP_FAIL("%s: %d is no doublet operator id (TMHIP_ND_OP_*)", who, op);
+  if (!tmhip_op_taken(r, solver)) TMHIP_FAIL("%s does not take %s (doublet operator id %d)", who, r->name, op);
   return r->clover != TMHIP_SW_NONE ? tmhip_ndsw_ready(ctx, who, true) : 0;
 }

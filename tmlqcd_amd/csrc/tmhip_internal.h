@@ -194,6 +194,8 @@ struct tmhip_ctx {
   // non-degenerate doublet (nd.hip): g_mubar, g_epsbar (global.h:202), phmc_invmaxev (phmc.h:31); work fields and solver state
   double mubar, epsbar, invmaxev;
   void *nd; int nd_active_shifts;
+  void *nd32;                         // fp32 doublet (nd32.hip): operator scratch, the fields of rg_mixed_cg_her_nd and its block sums
+  int opt_nd_fused32;                 // "nd_fused" of the fp32 doublet operator: set with opt_nd_fused, with a default of its own
   void *rat;                          // rational monomials (rational.hip): solution and work fields
   int opt_rat_batch;                  // shifts per deriv_Sb_batch launch of the rat / ndrat force
   int opt_ratcor_fused;               // 1 (default): apply_Z of the correction monomials on tmhip_rat_sum / tmhip_diff_sqnorm; 0: the reference's call sequence on the singles
@@ -427,7 +429,7 @@ int tmhip_apply_nd_op(tmhip_ctx *ctx, int op, tmhip_field *l_s, tmhip_field *l_c
 // The first statement of every solver entry point, before anything is allocated, enqueued or written: refuses, naming `who`, an id
 // outside the table, a row `solver` (TMHIP_S_*) does not take, fields of another kind than the row's, a missing clover prerequisite.
 int tmhip_op_check(tmhip_ctx *ctx, const char *who, int solver, int op, int kind);
-int tmhip_nd_op_check(tmhip_ctx *ctx, const char *who, int op);
+int tmhip_nd_op_check(tmhip_ctx *ctx, const char *who, int op, int solver = TMHIP_S_ND);   // TMHIP_S_MIXED: the rows with an fp32 twin
 int tmhip_ndsw_ready(tmhip_ctx *ctx, const char *who, bool need_inv);   // the clover doublet's prerequisite: 1+T resident and -- need_inv -- sw_inv_nd valid
 int tmhip_Q_pm_psi(tmhip_ctx *ctx, tmhip_field *l, tmhip_field *k);     // mms.hip: row TMHIP_OP_Q_PM_FULL, on FULL fields
 int tmhip_prepare_fp32(tmhip_ctx *ctx);
@@ -435,6 +437,7 @@ int tmhip_exchange_gauge_halo(tmhip_ctx *ctx);   // md_update.hip: t = 0 / T-1 s
 int tmhip_resort_gauge(tmhip_ctx *ctx);   // md_update.hip: stencil gauge copy from the device-resident lexicographic links
 int tmhip_prepare_clover32(tmhip_ctx *ctx);  // fp32 gauge copy + fp32 scratch / solver fields
 void tmhip_nd_destroy(tmhip_ctx *ctx);   // nd.hip: work fields and state of the doublet
+void tmhip_nd32_destroy(tmhip_ctx *ctx); // nd32.hip: work fields of the fp32 doublet and of rg_mixed_cg_her_nd
 void tmhip_rat_destroy(tmhip_ctx *ctx);  // rational.hip: solution and work fields of the rational monomials
 void tmhip_poly_destroy(tmhip_ctx *ctx); // poly.hip: work fields of the polynomial monomial
 void tmhip_mms_destroy(tmhip_ctx *ctx);  // mms.hip: work fields and state of the single-flavour multi-shift CG

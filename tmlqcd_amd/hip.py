@@ -199,7 +199,11 @@ def load_library():
         "tmhip_cg_her_nd": [vp, vp, vp, vp, vp, i, d, i, i, C.POINTER(i)],
         "tmhip_cg_mms_tm_nd": [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, i, d, i, C.POINTER(i)],
         "tmhip_nd_active_shifts": [vp],
-        "tmhip_cg_mms_tm": [vp, C.POINTER(vp), vp, pd, i, i, d, i, i, i, C.POINTER(i), pd],
+        "tmhip_M_ee_inv_ndpsi_32": [vp, vp, vp, vp, vp, C.c_float, C.c_float],
+        "tmhip_M_oo_sub_g5_ndpsi_32": [vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float],
+        "tmhip_Qtm_pm_ndpsi_32": [vp, vp, vp, vp, vp],
+        "tmhip_rg_mixed_cg_her_nd": [vp, vp, vp, vp, vp, i, d, i, i, i, d, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)],
+        "tmhip_cg_mms_tm":[vp, C.POINTER(vp), vp, pd, i, i, d, i, i, i, C.POINTER(i), pd],
         "tmhip_mms_active_shifts": [vp],
         "tmhip_mms_form": [vp],
         "tmhip_deriv_Sb_batch": [vp, i, i, C.POINTER(vp), C.POINTER(vp), pd],
@@ -1274,6 +1278,25 @@ class Lattice:
         else:
             _ck(self.lib.tmhip_cg_her_nd_op(self.h, P_up.h, P_dn.h, Q_up.h, Q_dn.h, max_iter, eps_sq, rel_prec, N, ND_OPS[op], C.byref(it)), "cg_her_nd_op")
         return it.value
+
+    # --- fp32 doublet and the mixed-precision doublet solve (operator/tm_operators_nd_32.c, solver/rg_mixed_cg_her_nd.c) ---
+    def M_ee_inv_ndpsi_32(self, l_s, l_c, k_s, k_c, mu, eps):
+        _ck(self.lib.tmhip_M_ee_inv_ndpsi_32(self.h, l_s.h, l_c.h, k_s.h, k_c.h, mu, eps), "M_ee_inv_ndpsi_32")
+
+    def M_oo_sub_g5_ndpsi_32(self, l_s, l_c, k_s, k_c, j_s, j_c, mu, eps):
+        _ck(self.lib.tmhip_M_oo_sub_g5_ndpsi_32(self.h, l_s.h, l_c.h, k_s.h, k_c.h, j_s.h, j_c.h, mu, eps), "M_oo_sub_g5_ndpsi_32")
+
+    def Qtm_pm_ndpsi_32(self, l_s, l_c, k_s, k_c):
+        """tm_operators_nd_32.c:215-263 on fp32 fields (field32), with mubar, epsbar, invmaxev of set_nd; l may be k."""
+        _ck(self.lib.tmhip_Qtm_pm_ndpsi_32(self.h, l_s.h, l_c.h, k_s.h, k_c.h), "Qtm_pm_ndpsi_32")
+
+    def rg_mixed_cg_her_nd(self, P_up, P_dn, Q_up, Q_dn, max_iter, eps_sq, rel_prec, N, delta=5.0e-5, op="Qtm_pm_ndpsi"):
+        """solver/rg_mixed_cg_her_nd.c:189 with f = Qtm_pm_ndpsi, f32 = Qtm_pm_ndpsi_32; delta = solver_params.mcg_delta.
+        Returns (iterations as the reference counts them or -1, (iter_out, iter_in_sp, iter_in_dp))."""
+        it, a, b, c = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _ck(self.lib.tmhip_rg_mixed_cg_her_nd(self.h, P_up.h, P_dn.h, Q_up.h, Q_dn.h, max_iter, eps_sq, rel_prec, N, ND_OPS[op], delta,
+                                              C.byref(it), C.byref(a), C.byref(b), C.byref(c)), "rg_mixed_cg_her_nd")
+        return it.value, (a.value, b.value, c.value)
 
     def cg_mms_tm_nd(self, Q_up, Q_dn, shifts, max_iter, eps_sq, rel_prec, P=None, op=None):
         """solver/cg_mms_tm_nd.c with M_ndpsi = Qtm_pm_ndpsi: (iterations, [(Pup_i, Pdn_i) ...]), one pair per shift; P: pairs to

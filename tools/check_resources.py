@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/bicgstab.ru.txt lib/eig.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/poly.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/bicgstab.ru.txt lib/eig.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/nd32.ru.txt lib/poly.ru.txt
 """
 import re
 import subprocess
@@ -61,6 +61,10 @@ RULES = [
     # epilogues -- two 6x6 block products per flavour and chirality, streamed one 3x3 block at a time: no scratch, two waves per SIMD
     (r"^void ndsw_hop_kernel<(\d+), (64|256), (true|false)>", "clover doublet stencil", 2),
     (r"^void ndsw_mix_kernel<(\d+)>", "clover doublet site-local", 2),
+    # the fp32 doublet (nd32.hip): the doublet stencil on float2 arithmetic with the mixing as its epilogue -- no scratch and the gather
+    # kernels' three waves per SIMD -- and the site-local mixing kernel, a stream of eight fields
+    (r"^void nd32_hop_kernel<(\d+), (64|256), (true|false)>", "fp32 doublet stencil", 3),
+    (r"^void nd32_mix_kernel<(\d+)>", "fp32 doublet site-local", 3),
     (r"^(void )?sw_invert_nd_kernel", "sw_invert_nd", 2),
     (r"^(void )?sw_deriv_nd_kernel", "sw_deriv_nd", 2),
     # the batched clover outer products of the rational forces: one wave per block n of swm / swp, 36 doubles of accumulators
