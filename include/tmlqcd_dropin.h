@@ -241,6 +241,10 @@ void M_oo_sub_g5_ndpsi_32(spinor32 *const l_s, spinor32 *const l_c, spinor32 *co
  * Qtm_pm_ndpsi_32 whatever f32 is.  Anything else (Qsw_pm_ndpsi has no fp32 twin here) ends the program with a message. */
 int rg_mixed_cg_her_nd(spinor *const P_up, spinor *const P_dn, spinor *const Q_up, spinor *const Q_dn, tmlqcd_solver_params solver_params,
                        const int max_iter, const double eps_sq, const int rel_prec, const int N, matrix_mult_nd f, matrix_mult_nd32 f32);
+/* solver/mixed_cg_mms_tm_nd.c:69-511: the fp32 multi-shift CG with reliable updates (solver = mixedcgmmsnd, solver/monomial_solve.c:252-268).
+ * Runs on the device, with the fields resident as for cg_mms_tm_nd, for M_ndpsi = Qtm_pm_ndpsi, M_ndpsi32 = Qtm_pm_ndpsi_32 and
+ * sdim = VOLUME/2 (up to 32 shifts); anything else ends the program with a message, as cg_mms_tm_nd does. */
+int mixed_cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *solver_params);
 /* ---- the clover doublet: operator/tm_operators_nd.h (Qsw_*), operator/clovertm_operators.h (the _nd functions), operator/clover_leaf.h ----
  * fp64, unsplit lattices.  The device's clover term must belong to the current links (tmlqcd_hip_sw_term, or the host's sw_term followed
  * by tmlqcd_hip_update_clover), and sw_invert_nd(mubar^2 - epsbar^2) must have run on it, as ndrat_monomial.c:89-91 does; otherwise every

@@ -368,6 +368,21 @@ int tmhip_Qtm_pm_ndpsi_32(tmhip_ctx *ctx, tmhip_field *l_s, tmhip_field *l_c, tm
  * double and are then rounded. */
 int tmhip_rg_mixed_cg_her_nd(tmhip_ctx *ctx, tmhip_field *P_up, tmhip_field *P_dn, tmhip_field *Q_up, tmhip_field *Q_dn, int max_iter, double eps_sq,
                              int rel_prec, int N, int op, double delta, int *iters, int *iter_out, int *iter_in_sp, int *iter_in_dp);
+/* mixed_cg_mms_tm_nd(Pup,Pdn,Qup,Qdn,solver_params)   solver/mixed_cg_mms_tm_nd.c:69-511 with M_ndpsi = Qtm_pm_ndpsi, M_ndpsi32 =
+ * Qtm_pm_ndpsi_32 (op must be TMHIP_ND_OP_QTM_PM: the clover doublet has no fp32 twin and is refused), on fp64 EO fields, unsplit
+ * lattices, 1 <= nshifts <= 32.  The arguments are those of tmhip_cg_mms_tm_nd_op.  |Q|^2 < 1e-4: what tmhip_cg_mms_tm_nd_op returns,
+ * same bits (:110-113).  Otherwise every P[s] is zeroed (:264-267) and the loop of :276-462 runs in fp32 on the device: Qtm_pm_ndpsi_32
+ * plus sigma_0, alpha, r and |r|^2, the stopping test (:307; the reference leaves the loop BEFORE the x update of that iteration, and
+ * so does this), the zita / alpha recurrences, the reliable-update decision (:326-334, rel_delta = 1e-10), x_s += alpha_s d_s, the
+ * betas, d_s = beta_s d_s + zita_s r.  Scalars are doubles, rounded to float where the reference casts them; fp32 sums accumulate in
+ * double and are then rounded to float.  A reliable update (:364-442) is done by the host after its poll: P[s] += x_s, x_d += x_0,
+ * r_d = Q - (A + sigma_0) x_d in fp64, the "got larger" exit for shift 0, x = 0, r = (float) r_d, new betas and d.  Every tenth
+ * iteration the last active shift leaves when alpha^2 |d|^2 <= eps_sq on the updated d (:445-459) and its x is added to its P; at
+ * the end the remaining x_s are added (:466-475).  *iters = the iteration j that met the precision, or -1 after max_iter iterations;
+ * *rel_updates, *removed (each may be NULL) = reliable updates done, shifts removed; tmhip_nd_active_shifts reports what is left.
+ * One host poll per "cg_batch" iterations; the result does not depend on it, nor on "mms32_fused". */
+int tmhip_mixed_cg_mms_tm_nd(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmhip_field *Qup, tmhip_field *Qdn, const double *shifts, int nshifts,
+                             int max_iter, double eps_sq, int rel_prec, int op, int *iters, int *rel_updates, int *removed);
 /* sw_deriv_nd(ieo)   operator/clover_deriv.c:156-243: swp += (1+T) sw_inv_nd summed over the chiralities, swm += their difference */
 int tmhip_sw_deriv_nd(tmhip_ctx *ctx, int ieo);
 /* The monomial of type NDCLOVERRAT (monomial/ndrat_monomial.c): the bodies of tmhip_ndrat_* with Qsw_pm_ndpsi, Qsw_tau1_sub_const_ndpsi and
@@ -915,6 +930,14 @@ int tmhip_event_elapsed_ms(tmhip_ctx *ctx, int slot_start, int slot_stop, double
  *                flavour mixing in its epilogue; 0: two single-flavour stencils per hop and a mixing pass.  It sets
  *                the form of the fp32 doublet (tmhip_Qtm_pm_ndpsi_32, the inner loops of tmhip_rg_mixed_cg_her_nd) as well, whose default
  *                is the faster form at 32^4 of profiles/r20_nd32_speed.log: 1
+ *   "mms32_fused" 1 (default) | 0: the vector part of an iteration of tmhip_mixed_cg_mms_tm_nd after the shift-0 residual kernel and the
+ *                one-block beta kernel -- 1: ONE pass over all shifts and both flavours that reads x_s, d_s and the shared r and writes x_s and
+ *                d_s (four field passes of 96 B/site per shift and flavour); 0: the fp64 solver's shape, an x pass and a d pass (six).  The same
+ *                element operations in the same order: identical bits.  Default: the faster form at 32^4 of profiles/r21_mixed_mms_speed.log
+ *   "nd_mms_mixed" 0 (default) | 1: 1 routes the multi-shift solves of the Wilson twisted-mass doublet monomials (tmhip_ndrat_derivative /
+ *                _heatbath / _acc, tmhip_apply_Z_nd and the ndratcor calls with TMHIP_ND_OP_QTM_PM) through tmhip_mixed_cg_mms_tm_nd, what
+ *                solver_params.type == MIXEDCGMMSND does in the reference (monomial/ndrat_monomial.c:107,228,291); the clover doublet keeps
+ *                tmhip_cg_mms_tm_nd_op.  0: nothing changes
  *   "rat_batch" shifts per group of the rat / ndrat force (clamped to [1, 32], default 12, the fastest of 1 / 2 / 4 / 12
  *                measured at 16^4 and 32^4 with np = 12, profiles/r08_rat_speed.log): one tmhip_deriv_Sb_batch launch per parity and group
  *                and, for the clover types (ndcloverrat, cloverrat), one tmhip_sw_spinor_eo_batch launch per parity and group; 1: the per-call

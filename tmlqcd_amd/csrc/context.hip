@@ -155,6 +155,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
     ctx->flag_timeout_ticks = (unsigned long long)(sec * 1.0e8);
   }
   ctx->opt_stg = 1; ctx->opt_stg32 = 0; ctx->opt_hopsplit = -1; ctx->opt_occ32 = 0; ctx->opt_recon = 0; ctx->opt_swall_order = 2; ctx->opt_swterm_order = 1; ctx->opt_gauge_cache = -1;
+  ctx->opt_mms32_fused = 1; ctx->opt_nd_mms_mixed = 0;   // mms32_fused: the faster form at 32^4 (profiles/r21_mixed_mms_speed.log)
   ctx->opt_nd_fused = 1; ctx->opt_nd_fused32 = 1; ctx->invmaxev = 1.0;   // fp32: the faster form at 32^4 (profiles/r20_nd32_speed.log)
   ctx->opt_rat_batch = 12;
   ctx->opt_poly_batch = 12;
@@ -355,6 +356,8 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "nd_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_fused must be 0 (two single-flavour stencils + a mixing pass) or 1 (doublet stencil)"); ctx->opt_nd_fused = ctx->opt_nd_fused32 = value; }
   else if (!strcmp(name, "rat_batch")) ctx->opt_rat_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
   else if (!strcmp(name, "poly_batch")) ctx->opt_poly_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
+  else if (!strcmp(name, "mms32_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("mms32_fused must be 0 (an x pass and a d pass) or 1 (x and d of all shifts in one pass)"); ctx->opt_mms32_fused = value; }
+  else if (!strcmp(name, "nd_mms_mixed")) { if (value < 0 || value > 1) TMHIP_FAIL("nd_mms_mixed must be 0 (cg_mms_tm_nd) or 1 (mixed_cg_mms_tm_nd for the Wilson tm doublet)"); ctx->opt_nd_mms_mixed = value; }
   else if (!strcmp(name, "ratcor_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("ratcor_fused must be 0 (the reference's call sequence on the single kernels) or 1 (rat_sum and diff_sqnorm)"); ctx->opt_ratcor_fused = value; }
   else if (!strcmp(name, "poly_fail_alloc")) ctx->opt_poly_fail_alloc = value < 0 ? 0 : value;
   else if (!strcmp(name, "csg_batch")) { if (value < 0 || value > 1) TMHIP_FAIL("csg_batch must be 0 (complex singles) or 1 (batched kernels)"); ctx->opt_csg_batch = value; }

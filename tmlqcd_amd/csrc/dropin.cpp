@@ -1080,6 +1080,23 @@ int rg_mixed_cg_her_nd(spinor *const P_up, spinor *const P_dn, spinor *const Q_u
   return iters;
 }
 
+/* solver/mixed_cg_mms_tm_nd.c:69-511 with (M_ndpsi, M_ndpsi32) = (Qtm_pm_ndpsi, Qtm_pm_ndpsi_32), device-resident; residency as cg_mms_tm_nd */
+int mixed_cg_mms_tm_nd(spinor **const Pup, spinor **const Pdn, spinor *const Qup, spinor *const Qdn, tmlqcd_solver_params *sp) {
+  const int op = dev_nd_op_of(sp->M_ndpsi, sp->sdim);
+  if (op < 0 || !tmhip_op_taken(tmhip_nd_op_row_of(op), TMHIP_S_MIXED) || (void *)sp->M_ndpsi32 != (void *)&Qtm_pm_ndpsi_32)
+    die("mixed_cg_mms_tm_nd: only M_ndpsi = Qtm_pm_ndpsi with M_ndpsi32 = Qtm_pm_ndpsi_32 on VOLUME/2 sites runs on the device");
+  const int n = sp->no_shifts;
+  if (n < 1 || n > 32) die("mixed_cg_mms_tm_nd: no_shifts must be in [1, 32]");
+  tmhip_ctx *c = ses.refresh_nd("mixed_cg_mms_tm_nd");
+  tmhip_field *fqu = in(c, Qup, TMHIP_FIELD_EO), *fqd = in(c, Qdn, TMHIP_FIELD_EO);
+  tmhip_field *fu[32], *fd[32];
+  for (int s = 0; s < n; s++) { fu[s] = out(c, Pup[s], TMHIP_FIELD_EO); fd[s] = out(c, Pdn[s], TMHIP_FIELD_EO); }
+  int iters = -1;
+  CK(tmhip_mixed_cg_mms_tm_nd(c, fu, fd, fqu, fqd, sp->shifts, n, sp->max_iter, sp->squared_solver_prec, sp->rel_prec, op, &iters, nullptr, nullptr));
+  for (int s = 0; s < n; s++) { done(c, Pup[s]); done(c, Pdn[s]); }
+  return iters;
+}
+
 // ------------------------------------------------------------------ fermion force
 /* deriv_Sb.c:401-700 */
 void deriv_Sb(const int ieo, spinor *const l, spinor *const k, hamiltonian_field_t *const hf, const double factor) {

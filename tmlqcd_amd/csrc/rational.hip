@@ -333,7 +333,7 @@ int tmhip_ndrat_derivative(tmhip_ctx *ctx, tmhip_field *pf_up, tmhip_field *pf_d
   if (!mu || !rmu || !iters || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndrat_derivative: null argument or not an fp64 one-parity field");
   TmhipRat *r = (TmhipRat *)ctx->rat;
   if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np)) return 1;
-  if (tmhip_cg_mms_tm_nd(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, iters)) return 1;   // :111
+  if (tmhip_nd_mms_solve(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, TMHIP_ND_OP_QTM_PM, iters)) return 1;   // :107-111
   return ndrat_force_body(ctx, r->chi_up, r->chi_dn, mu, rmu, np, invmaxev);
 }
 
@@ -346,7 +346,7 @@ static int ndrat_heatbath_body(tmhip_ctx *ctx, bool sw, tmhip_field *pf_up, tmhi
   double ea, eb;
   if (tmhip_square_norm(ctx, pf_up, ctx->Vh, 1, &ea) || tmhip_square_norm(ctx, pf_dn, ctx->Vh, 1, &eb)) return 1;   // :214,217
   *energy0 = ea + eb;
-  if (tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, nu, np, max_iter, eps_sq, rel_prec, sw ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, iters)) return 1;   // :232
+  if (tmhip_nd_mms_solve(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, nu, np, max_iter, eps_sq, rel_prec, sw ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, iters)) return 1;   // :232
   for (int j = np - 1; j >= 0; j--) {   // pf += i rnu_j (Q_h tau^1 - i nu_j) chi_j   (:239-254)
     if (sw ? tmhip_Qsw_tau1_sub_const_ndpsi(ctx, r->w[0], r->w[1], r->chi_up[j], r->chi_dn[j], 0.0, nu[j], 1.0, invmaxev)
            : tmhip_Q_tau1_sub_const_ndpsi(ctx, r->w[0], r->w[1], r->chi_up[j], r->chi_dn[j], 0.0, nu[j], 1.0, invmaxev)) return 1;
@@ -361,7 +361,7 @@ static int ndrat_acc_body(tmhip_ctx *ctx, bool sw, tmhip_field *pf_up, tmhip_fie
   if (!mu || !rmu || !iters || !energy1 || !rat_eo(pf_up) || !rat_eo(pf_dn)) TMHIP_FAIL("ndrat_acc: null argument or not an fp64 one-parity field");
   TmhipRat *r = (TmhipRat *)ctx->rat;
   if (rat_need(ctx, r->chi_up, np) || rat_need(ctx, r->chi_dn, np) || rat_need(ctx, r->w, 2)) return 1;
-  if (tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, sw ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, iters)) return 1;   // :295
+  if (tmhip_nd_mms_solve(ctx, r->chi_up, r->chi_dn, pf_up, pf_dn, mu, np, max_iter, eps_sq, rel_prec, sw ? TMHIP_ND_OP_QSW_PM : TMHIP_ND_OP_QTM_PM, iters)) return 1;   // :295
   if (tmhip_assign(ctx, r->w[0], pf_up, ctx->Vh) || tmhip_assign(ctx, r->w[1], pf_dn, ctx->Vh)) return 1;                // :299-300
   for (int j = np - 1; j >= 0; j--)                                                                                        // :301-306
     if (tmhip_assign_add_mul_r(ctx, r->w[0], r->chi_up[j], rmu[j], ctx->Vh) || tmhip_assign_add_mul_r(ctx, r->w[1], r->chi_dn[j], rmu[j], ctx->Vh)) return 1;
@@ -536,7 +536,7 @@ static int ratcor_apply_Z(tmhip_ctx *ctx, const RatcorZ &z, tmhip_field *k_up, t
   const double A2 = z.A * z.A;
   int it1;
   auto solve = [&](tmhip_field *q_up, tmhip_field *q_dn, int *it) {
-    return z.nd ? tmhip_cg_mms_tm_nd_op(ctx, r->chi_up, r->chi_dn, q_up, q_dn, z.mu, np, z.max_iter, z.eps_sq, z.rel_prec, z.op, it)
+    return z.nd ? tmhip_nd_mms_solve(ctx, r->chi_up, r->chi_dn, q_up, q_dn, z.mu, np, z.max_iter, z.eps_sq, z.rel_prec, z.op, it)
                 : tmhip_cg_mms_tm(ctx, r->chi_up, q_up, z.mu, np, z.max_iter, z.eps_sq, z.rel_prec, N, z.op, it, nullptr);
   };
   auto Qsq = [&]() { return z.nd ? tmhip_apply_nd_op(ctx, z.op, k_up, k_dn, t_up, t_dn) : tmhip_apply_op(ctx, z.op, k_up, t_up); };   // :209 / :236-237

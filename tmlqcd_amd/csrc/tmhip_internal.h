@@ -196,6 +196,8 @@ struct tmhip_ctx {
   void *nd; int nd_active_shifts;
   void *nd32;                         // fp32 doublet (nd32.hip): operator scratch, the fields of rg_mixed_cg_her_nd and its block sums
   int opt_nd_fused32;                 // "nd_fused" of the fp32 doublet operator: set with opt_nd_fused, with a default of its own
+  int opt_mms32_fused;                // tmhip_mixed_cg_mms_tm_nd: 1 x and d of all shifts in one pass, 0 an x pass and a d pass
+  int opt_nd_mms_mixed;               // 1: the tm doublet monomials solve with tmhip_mixed_cg_mms_tm_nd (MIXEDCGMMSND); default 0
   void *rat;                          // rational monomials (rational.hip): solution and work fields
   int opt_rat_batch;                  // shifts per deriv_Sb_batch launch of the rat / ndrat force
   int opt_ratcor_fused;               // 1 (default): apply_Z of the correction monomials on tmhip_rat_sum / tmhip_diff_sqnorm; 0: the reference's call sequence on the singles
@@ -430,6 +432,9 @@ int tmhip_apply_nd_op(tmhip_ctx *ctx, int op, tmhip_field *l_s, tmhip_field *l_c
 // outside the table, a row `solver` (TMHIP_S_*) does not take, fields of another kind than the row's, a missing clover prerequisite.
 int tmhip_op_check(tmhip_ctx *ctx, const char *who, int solver, int op, int kind);
 int tmhip_nd_op_check(tmhip_ctx *ctx, const char *who, int op, int solver = TMHIP_S_ND);   // TMHIP_S_MIXED: the rows with an fp32 twin
+// the multi-shift solve of the doublet monomials: tmhip_cg_mms_tm_nd_op, or -- "nd_mms_mixed" 1 and the Wilson tm doublet -- tmhip_mixed_cg_mms_tm_nd
+int tmhip_nd_mms_solve(tmhip_ctx *ctx, tmhip_field **Pup, tmhip_field **Pdn, tmhip_field *Qup, tmhip_field *Qdn, const double *shifts, int nshifts,
+                       int max_iter, double eps_sq, int rel_prec, int op, int *iters);
 int tmhip_ndsw_ready(tmhip_ctx *ctx, const char *who, bool need_inv);   // the clover doublet's prerequisite: 1+T resident and -- need_inv -- sw_inv_nd valid
 int tmhip_Q_pm_psi(tmhip_ctx *ctx, tmhip_field *l, tmhip_field *k);     // mms.hip: row TMHIP_OP_Q_PM_FULL, on FULL fields
 int tmhip_prepare_fp32(tmhip_ctx *ctx);

@@ -228,6 +228,7 @@ def load_library():
         "tmhip_H_eo_sw_ndpsi": [vp, vp, vp, vp, vp], "tmhip_Msw_ee_inv_ndpsi": [vp, vp, vp, vp, vp],
         "tmhip_cg_her_nd_op": [vp, vp, vp, vp, vp, i, d, i, i, i, C.POINTER(i)],
         "tmhip_cg_mms_tm_nd_op": [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, i, d, i, i, C.POINTER(i)],
+        "tmhip_mixed_cg_mms_tm_nd": [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, i, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)],
         "tmhip_sw_deriv_nd": [vp, i],
         "tmhip_ndcloverrat_force": [vp, C.POINTER(vp), C.POINTER(vp), pd, pd, i, d, d, d, i],
         "tmhip_ndcloverrat_derivative": [vp, vp, vp, pd, pd, i, d, d, d, i, i, d, i, C.POINTER(i)],
@@ -1315,6 +1316,22 @@ class Lattice:
         else:
             _ck(self.lib.tmhip_cg_mms_tm_nd_op(self.h, up, dn, Q_up.h, Q_dn.h, sh, n, max_iter, eps_sq, rel_prec, ND_OPS[op], C.byref(it)), "cg_mms_tm_nd_op")
         return it.value, P
+
+    def mixed_cg_mms_tm_nd(self, Q_up, Q_dn, shifts, max_iter, eps_sq, rel_prec, P=None, op="Qtm_pm_ndpsi"):
+        """solver/mixed_cg_mms_tm_nd.c with M_ndpsi = Qtm_pm_ndpsi, M_ndpsi32 = Qtm_pm_ndpsi_32: the fp32 multi-shift CG with reliable
+        updates.  Returns (iterations or -1, (reliable updates, shifts removed), [(Pup_i, Pdn_i) ...]); P as in cg_mms_tm_nd.
+        Shifts still active at the end: nd_active_shifts().  Options "mms32_fused" and "cg_batch" change the launches, not the result."""
+        n = len(shifts)
+        if P is None:
+            P = [(self.field(), self.field()) for _ in range(n)]
+        vp = C.c_void_p
+        up = (vp * n)(*[p[0].h for p in P])
+        dn = (vp * n)(*[p[1].h for p in P])
+        sh = (C.c_double * n)(*shifts)
+        it, nrel, nrem = C.c_int(), C.c_int(), C.c_int()
+        _ck(self.lib.tmhip_mixed_cg_mms_tm_nd(self.h, up, dn, Q_up.h, Q_dn.h, sh, n, max_iter, eps_sq, rel_prec, ND_OPS[op], C.byref(it),
+                                              C.byref(nrel), C.byref(nrem)), "mixed_cg_mms_tm_nd")
+        return it.value, (nrel.value, nrem.value), P
 
     def nd_active_shifts(self):
         return self.lib.tmhip_nd_active_shifts(self.h)

@@ -65,6 +65,10 @@ RULES = [
     # kernels' three waves per SIMD -- and the site-local mixing kernel, a stream of eight fields
     (r"^void nd32_hop_kernel<(\d+), (64|256), (true|false)>", "fp32 doublet stencil", 3),
     (r"^void nd32_mix_kernel<(\d+)>", "fp32 doublet site-local", 3),
+    # the vector part of mixed_cg_mms_tm_nd (nd32.hip): streams of float4 planes: no scratch, eight waves per SIMD; the pass over x and d
+    # holds the twelve loads of two planes in flight per lane and keeps six
+    (r"^(void )?mms32_(r|addp)_kernel", "fp32 multi-shift streams", 8),
+    (r"^(void )?mms32_xd_kernel", "fp32 multi-shift x and d pass", 6),
     (r"^(void )?sw_invert_nd_kernel", "sw_invert_nd", 2),
     (r"^(void )?sw_deriv_nd_kernel", "sw_deriv_nd", 2),
     # the batched clover outer products of the rational forces: one wave per block n of swm / swp, 36 doubles of accumulators
