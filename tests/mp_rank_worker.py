@@ -1,8 +1,9 @@
-"""One rank of tests/test_gpu_multiprocess.py::test_next_rows_as_real_processes: `python mp_rank_worker.py RANK WORLD JOB OUTDIR`.
-Every rank owns a T-slab of a global Tg x L^3 lattice, meets the others through the host-staged shared-memory transport
-(tmhip_comm_init_shm) and runs the rows next to the stencil -- D_psi, device-side clover term + inverse and Qsw_pm_psi, the hopping
+"""One rank of tests/test_gpu_multiprocess.py::test_next_rows_as_real_processes: `python mp_rank_worker.py RANK WORLD JOB OUTDIR [LXxLYxLZ]`.
+Every rank owns a T-slab of a global Tg x LX x LY x LZ lattice (8x8x8 unless the trailing argument says otherwise), meets the
+others through the host-staged shared-memory transport (tmhip_comm_init_shm) and runs the rows next to the stencil -- D_psi, device-side clover term + inverse and Qsw_pm_psi, the hopping
 and clover parts of the fermion force, the molecular-dynamics link update with its halo exchange, cg_her / mixed_cg_her on both
-operators -- leaving its slab of every result in OUTDIR/rank<r>.npz.  WORLD = 1: the unsplit lattice (the reference)."""
+operators -- leaving its slab of every result in OUTDIR/rank<r>_of_<world>_<LX>x<LY>x<LZ>.npz.  WORLD = 1: the unsplit lattice
+(the reference)."""
 import os
 import sys
 
@@ -19,23 +20,25 @@ from tmlqcd_amd import Lattice  # noqa: E402
 from tmlqcd_amd import synthetic as syn  # noqa: E402
 
 rank, world, job, outdir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
-Tg, L = 12, 8
+Tg = 12
+LX, LY, LZ = (int(v) for v in sys.argv[5].split("x")) if len(sys.argv) > 5 else (8, 8, 8)
+tag = "%dx%dx%d" % (LX, LY, LZ)
 T = Tg // world
 kappa, mu, csw, theta = 0.13, 0.02, 1.2, (1.0, 0.3, 0.0, -0.2)
-lat = Lattice(T, L, L, L, kappa=kappa, mu=mu, theta=theta, nproc_t=world, proc_t=rank, device=0)
+lat = Lattice(T, LX, LY, LZ, kappa=kappa, mu=mu, theta=theta, nproc_t=world, proc_t=rank, device=0)
 if world > 1:
     lat.comm_init_shm(job)
     if os.environ.get("MP_FACES") == "direct":          # faces as direct stores into the neighbours' IPC-mapped buffers; sums and the other halos stay on the ring
         lat.comm_init_ipc()
         assert lat.comm_faces_direct() == (True, world)  # (all ranks of the test share the one GPU)
-g = syn.gauge_field(21, T, L, L, L, world, rank)
+g = syn.gauge_field(21, T, LX, LY, LZ, world, rank)
 lat.set_gauge(g)
 N, V = lat.Vh, lat.V
 res = {}
 
 # full-lattice operator (lexicographic local field; the parity of a site is global)
-XYZ = L ** 3
-full = np.concatenate([syn.spinor_slice(22, rank * T + t, L, L, L) for t in range(T)])
+XYZ = LX * LY * LZ
+full = np.concatenate([syn.spinor_slice(22, rank * T + t, LX, LY, LZ) for t in range(T)])
 dQ, dP = lat.full_field(full), lat.full_field()
 lat.D_psi(dP, dQ)
 res["D_psi"] = dP.download()
@@ -43,8 +46,8 @@ res["D_psi"] = dP.download()
 # clover term and its inverse on the device from the resident links (neighbours' links across the cut from the halo slabs)
 lat.sw_term(None, kappa, csw)
 lat.sw_invert(0, mu)
-src = syn.spinor_field_eo(23, 0, T, L, L, L, world, rank)
-b = syn.spinor_field_eo(24, 1, T, L, L, L, world, rank)
+src = syn.spinor_field_eo(23, 0, T, LX, LY, LZ, world, rank)
+b = syn.spinor_field_eo(24, 1, T, LX, LY, LZ, world, rank)
 k, q, l, x = lat.field(src), lat.field(b), lat.field(), lat.field()
 lat.op("Qsw_pm_psi", l, k); res["Qsw_pm_psi"] = l.download()
 lat.Qtm_pm_psi(l, k); res["Qtm_pm_psi"] = l.download()
@@ -74,7 +77,7 @@ lat.update_gauge(0.05)
 res["links"] = lat.gauge_download()[:V]
 lat.Hopping_Matrix(0, l, k); res["hop_after_update"] = l.download()
 # ILDG: every rank writes its part of ONE record at its offset (checksum words gathered over the ranks), then all read the file back
-conf = os.path.join(outdir, "conf_%d.lime" % world)
+conf = os.path.join(outdir, "conf_%d_%s.lime" % (world, tag))
 sums = lat.write_gauge_field(conf, 64, "plaquette = 0.5")
 rc, back, info = lat.read_gauge_field(conf, 64)
 res["ildg"] = np.array([rc, sums[0], sums[1], info.suma, info.sumb, info.suma_stored, info.sumb_stored], dtype=np.float64)
@@ -83,6 +86,6 @@ lat.Hopping_Matrix(1, l, k); res["hop_after_read"] = l.download()
 lat.update_momenta(0.1)
 res["momenta"] = lat.momenta_download()
 lat.sync()
-np.savez(os.path.join(outdir, "rank%d_of_%d.npz" % (rank, world)), **res)
+np.savez(os.path.join(outdir, "rank%d_of_%d_%s.npz" % (rank, world, tag)), **res)
 lat.close()
 print("rank %d of %d done" % (rank, world), flush=True)

@@ -88,30 +88,29 @@ def test_bench_with_the_direct_carrier_from_the_start():
     assert "gave up" not in err
 
 
-@pytest.mark.parametrize("world,faces", [(2, "ring"), (3, "ring"), (3, "direct")])
-def test_next_rows_as_real_processes(world, faces, tmp_path):
-    """D_psi, the device-side clover term / inverse and Qsw_pm_psi, cg_her and mixed_cg_her on both operators, both parts of the fermion
-    force, the link update with its halo exchange and update_momenta -- every rank a process of its own (tests/mp_rank_worker.py), slab by
-    slab against the unsplit lattice."""
+def _next_rows(world, faces, tmp_path, spatial=(8, 8, 8)):
+    """One unsplit process and `world` rank processes of tests/mp_rank_worker.py on a 12 x spatial lattice; every assertion of
+    test_next_rows_as_real_processes.  Returns the unsplit process's results."""
     import numpy as np
     worker = os.path.join(ROOT, "tests", "mp_rank_worker.py")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TMLQCD_HIP_FLAG_TIMEOUT_S="60", MP_FACES=faces)
-    job = "mp_%d_%d_%s" % (os.getpid(), world, faces)
-    ref = subprocess.run([sys.executable, worker, "0", "1", job, str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    tag = "%dx%dx%d" % tuple(spatial)
+    job = "mp_%d_%d_%s_%s" % (os.getpid(), world, faces, tag)
+    ref = subprocess.run([sys.executable, worker, "0", "1", job, str(tmp_path), tag], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert ref.returncode == 0, ref.stderr[-3000:]
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), job, str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), job, str(tmp_path), tag], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
              for r in range(world)]
     outs = [p.communicate(timeout=400) for p in procs]
     for p, (so, se) in zip(procs, outs):
         assert p.returncode == 0, se[-3000:]
-    one = np.load(os.path.join(str(tmp_path), "rank0_of_1.npz"))
-    parts = [np.load(os.path.join(str(tmp_path), "rank%d_of_%d.npz" % (r, world))) for r in range(world)]
+    one = np.load(os.path.join(str(tmp_path), "rank0_of_1_%s.npz" % tag))
+    parts = [np.load(os.path.join(str(tmp_path), "rank%d_of_%d_%s.npz" % (r, world, tag))) for r in range(world)]
 
     def slab(a, r):
         n = a.shape[0] // world
         return a[r * n:(r + 1) * n]
     # the configuration file written by `world` ranks is the file one rank writes, byte for byte (the date in the xlf record aside)
-    fa, fb = (open(os.path.join(str(tmp_path), "conf_%d.lime" % w), "rb").read() for w in (1, world))
+    fa, fb = (open(os.path.join(str(tmp_path), "conf_%d_%s.lime" % (w, tag)), "rb").read() for w in (1, world))
     assert len(fa) == len(fb) and sum(x != y for x, y in zip(fa, fb)) <= 32, "the split writers' file differs from the single writer's"
     for r in range(world):
         assert parts[r]["ildg"][0] == 0 and np.array_equal(parts[r]["ildg"][1:], one["ildg"][1:]), (r, parts[r]["ildg"], one["ildg"])   # read status, checksum words
@@ -131,6 +130,63 @@ def test_next_rows_as_real_processes(world, faces, tmp_path):
             for kind in ("cg_", "mixed_"):
                 sc = np.abs(one[kind + name]).max()
                 assert np.abs(parts[r][kind + name] - slab(one[kind + name], r)).max() / sc < 1e-6, (kind, name, r)
+    return one
+
+
+@pytest.mark.parametrize("world,faces", [(2, "ring"), (3, "ring"), (3, "direct")])
+def test_next_rows_as_real_processes(world, faces, tmp_path):
+    """D_psi, the device-side clover term / inverse and Qsw_pm_psi, cg_her and mixed_cg_her on both operators, both parts of the fermion
+    force, the link update with its halo exchange and update_momenta -- every rank a process of its own (tests/mp_rank_worker.py), slab by
+    slab against the unsplit lattice."""
+    _next_rows(world, faces, tmp_path)
+
+
+@pytest.mark.parametrize("world,faces,spatial", [(3, "ring", (6, 4, 10)), (3, "direct", (4, 8, 16)), (2, "direct", (6, 4, 10))],
+                         ids=["3-ring-6x4x10", "3-direct-4x8x16", "2-direct-6x4x10"])
+def test_next_rows_as_real_processes_on_non_cubic_slabs(world, faces, spatial, tmp_path):
+    """The same rows with three pairwise different spatial extents, where an extent used as the wrong stride, a wrap against the wrong
+    extent or a wrong halo-slab offset shows: 6 x 4 x 10 (face 120: the two-kernel split form, a per-lane skipped hop, solvers not
+    fused) and 4 x 8 x 16 (face 256: the one-kernel direct form, fused solver reductions).  Every assertion of the cubic test; and the
+    one-rank leg the slabs are compared with is itself pinned to the CPU oracle (D_psi, Qsw_pm_psi, Qtm_pm_psi at TOL, the derivative
+    at 4 * TOL), so the chain ends at the oracle and not at the device.  The force row's spinor inputs l = Qtm_pm_psi k and x = the
+    last mixed solve are outputs of earlier rows of the worker: the oracle's force is computed from those, l being checked on its own."""
+    import numpy as np
+    from oracle.oraclebind import Oracle
+    from tests.util import TOL, rel_err
+    from tmlqcd_amd import synthetic as syn
+    one = _next_rows(world, faces, tmp_path, spatial)
+    Tg, dims = 12, (12,) + tuple(spatial)
+    kappa, mu, csw, theta = 0.13, 0.02, 1.2, (1.0, 0.3, 0.0, -0.2)                  # tests/mp_rank_worker.py
+    orc = Oracle(*dims, kappa=kappa, mu=mu, theta=theta, threads=8)
+    orc.set_gauge(syn.gauge_field(21, *dims))
+    N, V = orc.Vh, orc.V
+    full = np.concatenate([syn.spinor_slice(22, t, *spatial) for t in range(Tg)])
+    P = np.zeros_like(full)
+    orc.D_psi(P, full)
+    sw = orc.sw_term(kappa, csw)
+    swi, fails = orc.sw_invert(sw, 0, mu)
+    assert fails == 0
+    orc.set_clover(sw, swi)
+
+    def field(a):
+        b = orc.new_field(); b[:N] = a
+        return b
+    k, q = field(syn.spinor_field_eo(23, 0, *dims)), field(syn.spinor_field_eo(24, 1, *dims))
+    ref = {"D_psi": P}
+    for name in ("Qsw_pm_psi", "Qtm_pm_psi"):
+        out = orc.new_field(); orc.op(name, out, k.copy()); ref[name] = out[:N]
+    l, x = field(one["Qtm_pm_psi"]), field(one["mixed_Qsw_pm_psi"])
+    df = np.zeros((orc.VPR, 4, 8))
+    swm, swp = np.zeros((V, 4, 3, 3, 2)), np.zeros((V, 4, 3, 3, 2))
+    orc.deriv_Sb(1, q, k, df, 0.7); orc.deriv_Sb(0, k, q, df, -0.4)
+    orc.sw_spinor_eo(0, swm, swp, k, l, 0.3); orc.sw_spinor_eo(1, swm, swp, q, x, 0.3)
+    orc.sw_deriv(0, swm, swp, mu)
+    orc.sw_all(df, swm, swp, kappa, csw)
+    ref["derivative"] = df[:V]
+    for key, bound in (("D_psi", TOL), ("Qsw_pm_psi", TOL), ("Qtm_pm_psi", TOL), ("derivative", 4 * TOL)):
+        err = rel_err(one[key], ref[key])
+        print("12x%dx%dx%d one rank vs oracle: %s rel err %.3e" % (tuple(spatial) + (key, err)))
+        assert err < bound, (key, err)
 
 
 @pytest.mark.parametrize("world,Tg", [(2, 16), (4, 16), (5, 20)])
