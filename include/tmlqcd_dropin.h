@@ -435,6 +435,18 @@ void oriented_plaquettes_measurement(const int traj, const int id, const int ieo
 void tmlqcd_hip_polyakov_loop(double pl[2], const int dir);
 int tmlqcd_hip_polyakov_loop_dir(const int nstore, const int dir);               /* meas/polyakov_loop.c:325 */
 
+/* ---- LapH: the 3D Laplacian on a time-slice and the eigensystem of all of them (jacobi.h, solver/eigenvalues_Jacobi.c) -------------
+ * Jacobi under its reference name (the build with WITHLAPH, no MPI): l = Jacobi(k, t) on the device links; l and k are host vectors of
+ * SPACEVOLUME su3_vector, copied in and out through two colour-vector fields of the session (they are NOT kept in the registry of
+ * resident fields: every call moves its slice both ways).  l == k, a t outside [0, T) and a T-split run end the program.
+ * tmlqcd_hip_laph_eigensystem stands in for the loop over the time-slices of eigenvalues_Jacobi.c: the nev lowest eigenpairs of every
+ * slice by tmhip_laph_eigensystem (absolute prec on the residual, at most max_apps applications per slice), written into the working
+ * directory as that file's branch without MPI writes them: eigenvalues.%.3d.%.4d (tslice, nstore) and eigenvector.%.3d.%.3d.%.4d (ev,
+ * tslice, nstore).  Returns the number of slices on which all nev pairs converged.
+ * Not built: Lemon / MPI output, jdher_su3vect and cg_her_su3vect, the smearing of the links before the Laplacian. */
+void Jacobi(su3_vector *const l, su3_vector *const k, int t);
+int tmlqcd_hip_laph_eigensystem(const int nev, const double prec, const int max_apps, const int nstore);
+
 /* ---- rational monomials (monomial/ndrat_monomial.c type NDRAT, monomial/rat_monomial.c type RAT) --------------------------------------
  * The bodies of the three monomial functions with the monomial's parameters as arguments (rational_t::mu / rmu / nu / rnu with np entries,
  * EVMaxInv, maxiter, forceprec or accprec, g_relative_precision_flag), as tmlqcd_hip_gauge_derivative does for the gauge monomial; the

@@ -280,6 +280,82 @@ int tmhip_eig_project(tmhip_ctx *ctx, int nv, tmhip_field *const *v_up, tmhip_fi
 int tmhip_basis_rotate(tmhip_ctx *ctx, int n, int k, tmhip_field *const *v_up, tmhip_field *const *v_dn, const double *Y /* n * k */, int N);
 int tmhip_eig_small(int n, double *A /* n*n, in: symmetric, out: eigenvectors by column */, double *w);
 
+/* ---- LapH eigensystem: the gauge-covariant 3D Laplacian on all time-slices (jacobi.c, LapH_ev.c, solver/eigenvalues_Jacobi.c) -----
+ * A colour-vector field is T x LX LY LZ sites of three complex doubles, no spin: one 3D lattice per time-slice.  Host image: the
+ * reference's su3_vector [T][SPACEVOLUME], t slowest, then x, y, z (the ix of geometry_eo.c:851-860; t SPACEVOLUME + ix is the
+ * lexicographic site of g_gauge_field).  Device: three colour planes of VOLUME sites at a stride, a time-slice is a contiguous range
+ * of every plane.  Unsplit contexts only.
+ *   tmhip_laph_apply        out[t] = Jacobi(in[t], t) of jacobi.c:43-72 for t0 <= t < t0 + nt in ONE launch:
+ *                           l(x) = 6 k(x) - sum_{mu=1..3} [ U_mu(x) k(x+mu) + U_mu(x-mu)^dagger k(x-mu) ], the subtractions in the
+ *                           reference's order, on the raw resident links (no boundary phases, no kappa), neighbours wrap inside the
+ *                           slice (an extent of 2: x+mu and x-mu are one site and both terms count).  out != in.  Slices outside the
+ *                           range are not touched.  The links are the lexicographic copy tmhip_set_gauge left and tmhip_update_gauge /
+ *                           tmhip_gauge_restore keep current.
+ *   tmhip_laph_apply_dot    the same and dots[2 t'], dots[2 t' + 1] = Re, Im <in, out> of slice t0 + t' from the same pass
+ *   tmhip_laph_apply_filter out = c1 (A in) + c2 in + c3 prev with coef[3 t' ..] = (c1, c2, c3) of slice t0 + t': the Chebyshev
+ *                           three-term step, no vector pass of its own.  prev may be NULL (c3 is then not read); out differs from in
+ *                           and prev.
+ * Options: "laph_basis" 0 (default: m = nev + 32, at most TMHIP_LAPH_MAX_BASIS) or m itself; "laph_cheb" 16 (default) the degree of the
+ * filter, 0 none -- the fastest of tools/laph_speed.py, profiles/r22_laph_speed.log.  "laph_fused" 1 (default): one stencil launch per call.  0: the plain operator and a separate pass (the dots / the
+ * combination), the cross-check and the baseline of tools/laph_speed.py.
+ * The batched Lanczos pieces, public so that they can be tested: the time-slice is a grid dimension, every scalar is an array over the
+ * slices of the range that stays on the device inside the driver.  active: NULL, or nt flags; a slice whose flag is 0 is frozen --
+ * its blocks return at once, nothing of it is read or written and its entries of the outputs are left as they were.  Every sum is
+ * added in a fixed order (one partial per block, a fixed final pass): the same bits from call to call.
+ *   tmhip_laph_dots      out[(t' nv + i) 2 ..] = Re, Im <v_i, w> of slice t0 + t', i < nv <= TMHIP_LAPH_MAX_BASIS + 1; a launch takes up
+ *                        to 65 vectors (w once, each v_i once), more are taken in chunks
+ *   tmhip_laph_project   w[t] -= sum_i h[t'][i] v_i[t], ascending i (h as tmhip_laph_dots leaves it); sqnorm[t'] = |w[t]|^2 of the
+ *                        result from the same pass.  nv = 0: the norms alone.  w may not be one of the v_i.
+ *   tmhip_laph_normalise out[t] = in[t] / |in[t]| (zero for a slice of norm zero); sqnorm[t'] = |in[t]|^2.  out may be in.
+ *   tmhip_laph_rotate    V[t][:, 0:k] = V[t][:, 0:n] Y_t in place, Y real [nt][n][k], 1 <= k <= n <= TMHIP_LAPH_MAX_BASIS: an
+ *                        element's n values wait in LDS while the k columns are formed in groups of 16; vectors k .. n-1 stay
+ * The driver: tmhip_laph_eigensystem returns the nev lowest eigenpairs of every slice of the range.  Per slice the algorithm is exactly
+ * that of tmhip_eigenvalues with which = 0 (tests/eig_restate.py is its statement): thick restart keeping nev + (m - nev) / 2 of the
+ * m = "laph_basis" vectors, classical Gram-Schmidt twice, convergence on the true residual against the absolute prec, the Chebyshev
+ * filter of degree "laph_cheb" on the lowest end with the interval per slice from one unfiltered cycle by the same rule or from
+ * tmhip_laph_set_interval, max_apps the cap of applications per slice (reaching it is no error).  All slices advance in lock-step: one
+ * launch of every kernel and ONE host synchronisation per Lanczos step for all of them, none inside the filter; a slice that has
+ * converged, hit its cap or met an invariant subspace is frozen while the others finish.  The nt small eigenproblems of a restart are
+ * solved on up to 16 host threads (cyclic Jacobi, csrc/eig_small.h).
+ *   evec       NULL or nev colour-vector fields: evec[i] holds eigenvector i of every slice of the range, unit norm per slice.  ON ENTRY
+ *              evec[0] is the start vector of every slice where its norm is non-zero; a fixed pseudo-random fill starts the others.
+ *   evals      [nt][nev], ascending: Rayleigh quotients with the operator itself;  resid [nt][nev]: the computed |A v - theta v|
+ *   converged  [nt]: pairs with resid <= prec;  apps [nt]: operator applications of the slice
+ * Work memory: m + 3 colour-vector fields, allocated on first use, kept, freed with the context.
+ * tmhip_laph_write writes what the non-MPI branch of eigenvalues_Jacobi.c:176-209 writes into `dir`: eigenvalues.%.3d.%.4d (tslice,
+ * nstore) with one "%e\n" line per eigenvalue, eigenvector.%.3d.%.3d.%.4d (ev, tslice, nstore) with the raw host-order image of the
+ * slice, SPACEVOLUME x 3 complex doubles, no header.
+ * Refused with a message, nothing written: T-split contexts and their loopback rehearsal, no resident links, a slice range outside
+ * [0, T) or of more than 256 slices, nev + 2 > "laph_basis", out == in, fields of another context.
+ * Not built: T-split ranks, fp32 or mixed precision, Lemon / MPI output, more than 126 eigenpairs per slice, exact multiplicities (one
+ * start vector finds one eigenvector per distinct eigenvalue), link smearing (upload smeared links), cg_her_su3vect / jdher_su3vect. */
+#define TMHIP_LAPH_MAX_BASIS 128
+typedef struct tmhip_cvfield tmhip_cvfield;
+int tmhip_cvfield_alloc(tmhip_ctx *ctx, tmhip_cvfield **out);   /* zeroed */
+void tmhip_cvfield_free(tmhip_ctx *ctx, tmhip_cvfield *f);
+int tmhip_cvfield_upload(tmhip_ctx *ctx, tmhip_cvfield *f, const void *host /* [T][SPACEVOLUME][3] complex double */);
+int tmhip_cvfield_download(tmhip_ctx *ctx, tmhip_cvfield *f, void *host);
+/* the slices [t0, t0 + nt) alone: host holds [nt][SPACEVOLUME][3] complex double */
+int tmhip_cvfield_upload_slices(tmhip_ctx *ctx, tmhip_cvfield *f, const void *host, int t0, int nt);
+int tmhip_cvfield_download_slices(tmhip_ctx *ctx, tmhip_cvfield *f, void *host, int t0, int nt);
+int tmhip_cvfield_zero(tmhip_ctx *ctx, tmhip_cvfield *f);
+int tmhip_laph_apply(tmhip_ctx *ctx, tmhip_cvfield *out, tmhip_cvfield *in, int t0, int nt);
+int tmhip_laph_apply_dot(tmhip_ctx *ctx, tmhip_cvfield *out, tmhip_cvfield *in, int t0, int nt, double *dots /* [nt][2] */);
+int tmhip_laph_apply_filter(tmhip_ctx *ctx, tmhip_cvfield *out, tmhip_cvfield *in, tmhip_cvfield *prev /* or NULL */, int t0, int nt,
+                            const double *coef /* [nt][3] */);
+int tmhip_laph_dots(tmhip_ctx *ctx, int nv, tmhip_cvfield *const *v, tmhip_cvfield *w, int t0, int nt, const int *active /* nt or NULL */,
+                    double *out /* [nt][nv][2] */);
+int tmhip_laph_project(tmhip_ctx *ctx, int nv, tmhip_cvfield *const *v, tmhip_cvfield *w, const double *h /* [nt][nv][2] */, int t0, int nt,
+                       const int *active, double *sqnorm /* [nt] */);
+int tmhip_laph_normalise(tmhip_ctx *ctx, tmhip_cvfield *out, tmhip_cvfield *in, int t0, int nt, const int *active, double *sqnorm /* [nt] */);
+int tmhip_laph_rotate(tmhip_ctx *ctx, int n, int k, tmhip_cvfield *const *v, const double *Y /* [nt][n][k] */, int t0, int nt, const int *active);
+int tmhip_laph_set_interval(tmhip_ctx *ctx, double lo, double hi);   /* of every slice; 0, 0 = automatic, per slice */
+int tmhip_laph_eigensystem(tmhip_ctx *ctx, int t0, int nt, int nev, double prec, int max_apps, tmhip_cvfield *const *evec /* nev fields or NULL */,
+                           double *evals, double *resid, int *converged, int *apps);
+/* host seconds of the last tmhip_laph_eigensystem: out[0] in the small eigenproblems, out[1] in the whole call (tools/laph_speed.py) */
+int tmhip_laph_timing(tmhip_ctx *ctx, double out[2]);
+int tmhip_laph_write(tmhip_ctx *ctx, const char *dir, int nstore, int t0, int nt, int nev, tmhip_cvfield *const *evec, const double *evals /* [nt][nev] */);
+
 /* ---- non-degenerate twisted-mass doublet (operator/tm_operators_nd.c) ------------------------
  * A doublet is a pair of EO fields (strange = up, charm = dn).  Unsplit lattices only: a context with nproc_t > 1 refuses every
  * entry point below with a message.  Wilson twisted mass, fp64, no clover term (the clover doublet and the fp32 twins follow below). */

@@ -6,4 +6,4 @@ include/tmlqcd_dropin.h).  This Python package is only a thin ctypes mirror of t
 parity tests and bench.py can drive it; there is no CPU fallback: importing `tmlqcd_amd.hip`
 raises if the HIP library has not been built.
 """
-from .hip import Lattice, Field, load_library, library_path, EO, OE  # noqa: F401
+from .hip import Lattice, Field, CvField, load_library, library_path, EO, OE  # noqa: F401

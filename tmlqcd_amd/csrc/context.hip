@@ -163,6 +163,7 @@ int tmhip_create(const tmhip_geom *geom, int device, tmhip_ctx **out) {
   ctx->opt_csg_batch = 1;
   ctx->opt_bicg_fused = 1;
   ctx->opt_eig_basis = 24; ctx->opt_eig_cheb = 4; ctx->opt_eig_fused = 1;   // the fastest measured at 32^4 (profiles/r19_eig_speed.log)
+  ctx->opt_laph_basis = 0; ctx->opt_laph_cheb = 16; ctx->opt_laph_fused = 1;   // the fastest measured at 16^3 x 32 (profiles/r22_laph_speed.log)
   ctx->gauge_recon_dev = -1.0;
   ctx->opt_gauge_pack = -1; ctx->opt_gauge_pack_rot = -1; ctx->opt_gauge_pack_compact = -1;
   TMHIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
@@ -233,6 +234,7 @@ void tmhip_destroy(tmhip_ctx *ctx) {
   tmhip_meas_destroy(ctx);
   tmhip_bicg_destroy(ctx);
   tmhip_eig_destroy(ctx);
+  tmhip_laph_destroy(ctx);
   for (int i = 0; i < 3; i++) { tmhip_field_free(ctx, ctx->scratch[i]); tmhip_field_free(ctx, ctx->sf[i]); }
   tmhip_field_free(ctx, ctx->sf_extra);
   for (int i = 0; i < 2; i++) tmhip_field_free(ctx, ctx->scratch32[i]);
@@ -366,6 +368,9 @@ int tmhip_set_option(tmhip_ctx *ctx, const char *name, int value) {
   else if (!strcmp(name, "eig_cheb")) { if (value < 0 || value > 256) TMHIP_FAIL("eig_cheb must be 0 (no filter) or the degree of the Chebyshev filter, at most 256"); ctx->opt_eig_cheb = value; }
   else if (!strcmp(name, "eig_restarts")) { if (value < 0) TMHIP_FAIL("eig_restarts must be 0 (no bound) or the number of Lanczos cycles a run may take"); ctx->opt_eig_restarts = value; }
   else if (!strcmp(name, "eig_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("eig_fused must be 0 (the single entry points of the linalg) or 1 (eig_dots, eig_project, basis_rotate)"); ctx->opt_eig_fused = value; }
+  else if (!strcmp(name, "laph_basis")) { if (value != 0 && (value < 3 || value > TMHIP_LAPH_MAX_BASIS)) TMHIP_FAIL("laph_basis = %d: 0 (nev + 32) or the 3 to TMHIP_LAPH_MAX_BASIS = %d vectors of a Lanczos cycle", value, TMHIP_LAPH_MAX_BASIS); ctx->opt_laph_basis = value; }
+  else if (!strcmp(name, "laph_cheb")) { if (value < 0 || value > 256) TMHIP_FAIL("laph_cheb must be 0 (no filter) or the degree of the Chebyshev filter, at most 256"); ctx->opt_laph_cheb = value; }
+  else if (!strcmp(name, "laph_fused")) { if (value < 0 || value > 1) TMHIP_FAIL("laph_fused must be 0 (the plain Laplacian and a pass of its own) or 1 (one stencil launch)"); ctx->opt_laph_fused = value; }
   else if (!strcmp(name, "gauge_global_sums")) { if (value < 0 || value > 1) TMHIP_FAIL("gauge_global_sums must be 0 (the rank's share) or 1 (summed over the ranks)"); ctx->opt_gauge_global_sums = value; }
   else if (!strcmp(name, "cg_batch")) ctx->opt_cg_batch = value > 0 ? value : 1;
   else TMHIP_FAIL("unknown option %s", name);
@@ -378,6 +383,9 @@ int tmhip_get_option(tmhip_ctx *ctx, const char *name, int *value) {
   else if (!strcmp(name, "eig_cheb")) *value = ctx->opt_eig_cheb;
   else if (!strcmp(name, "eig_fused")) *value = ctx->opt_eig_fused;
   else if (!strcmp(name, "eig_restarts")) *value = ctx->opt_eig_restarts;
+  else if (!strcmp(name, "laph_basis")) *value = ctx->opt_laph_basis;
+  else if (!strcmp(name, "laph_cheb")) *value = ctx->opt_laph_cheb;
+  else if (!strcmp(name, "laph_fused")) *value = ctx->opt_laph_fused;
   else TMHIP_FAIL("tmhip_get_option: %s is not an option that can be read back", name);
   return 0;
 }

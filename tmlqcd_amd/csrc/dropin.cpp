@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 extern "C" {
 // ---- globals owned by the host program (global.h, boundary.h) ----
@@ -1271,6 +1272,46 @@ int tmlqcd_hip_polyakov_loop_dir(const int nstore, const int dir) {
   fprintf(ofs, "%4d\t%2d\t%25.16e\t%25.16e\n", nstore, dir, pl[0], pl[1]);
   fclose(ofs);
   return 0;
+}
+
+// ------------------------------------------------------------------ LapH: the 3D Laplacian and its eigensystem (laph.hip)
+// two colour-vector fields of the session's context for the host vectors of Jacobi; made again when the context is
+static tmhip_cvfield *laph_io[2] = {nullptr, nullptr};
+static tmhip_ctx *laph_io_ctx = nullptr;
+static void laph_fields(tmhip_ctx *c) {
+  if (laph_io_ctx == c && laph_io[0]) return;
+  for (int i = 0; i < 2; i++) { tmhip_cvfield_free(c, laph_io[i]); laph_io[i] = nullptr; }
+  for (int i = 0; i < 2; i++) CK(tmhip_cvfield_alloc(c, &laph_io[i]));
+  laph_io_ctx = c;
+}
+/* jacobi.c:43-72 without its MPI exchange: l and k are host vectors of SPACEVOLUME sites, copied in and out */
+void Jacobi(su3_vector *const l, su3_vector *const k, int t) {
+  tmhip_ctx *c = unsplit_gauge_links((const su3 **)g_gauge_field, "Jacobi: no g_gauge_field", "Jacobi: not available on T-split ranks");
+  if (!l || !k || l == k) die("Jacobi: l and k must be two vectors");
+  if (t < 0 || t >= T) die("Jacobi: t is outside [0, T)");
+  laph_fields(c);
+  CK(tmhip_cvfield_upload_slices(c, laph_io[0], k, t, 1));
+  CK(tmhip_laph_apply(c, laph_io[1], laph_io[0], t, 1));
+  CK(tmhip_cvfield_download_slices(c, laph_io[1], l, t, 1));
+}
+/* the loop over the time-slices of eigenvalues_Jacobi.c:120-209 for all of them at once: the nev lowest eigenpairs of every slice and
+ * the files of its branch without MPI in the working directory; returns the number of slices with all nev pairs converged */
+int tmlqcd_hip_laph_eigensystem(const int nev, const double prec, const int max_apps, const int nstore) {
+  tmhip_ctx *c = unsplit_gauge_links((const su3 **)g_gauge_field, "tmlqcd_hip_laph_eigensystem: no g_gauge_field", "tmlqcd_hip_laph_eigensystem: not available on T-split ranks");
+  if (nev < 1 || nev > TMHIP_LAPH_MAX_BASIS - 2) die("tmlqcd_hip_laph_eigensystem: the number of eigenpairs must be in [1, 126]");
+  std::vector<tmhip_cvfield *> ev(nev, nullptr);
+  for (int i = 0; i < nev; i++) CK(tmhip_cvfield_alloc(c, &ev[i]));
+  std::vector<double> evals((size_t)T * nev), resid((size_t)T * nev);
+  std::vector<int> conv(T), apps(T);
+  int done_slices = 0;
+  for (int t0 = 0; t0 < T; t0 += 256) {   // a call of the library takes 256 slices
+    const int nt = T - t0 < 256 ? T - t0 : 256;
+    CK(tmhip_laph_eigensystem(c, t0, nt, nev, prec, max_apps, ev.data(), evals.data() + (size_t)t0 * nev, resid.data() + (size_t)t0 * nev, conv.data() + t0, apps.data() + t0));
+    CK(tmhip_laph_write(c, ".", nstore, t0, nt, nev, ev.data(), evals.data() + (size_t)t0 * nev));
+  }
+  for (int t = 0; t < T; t++) done_slices += conv[t] == nev;
+  for (int i = 0; i < nev; i++) tmhip_cvfield_free(c, ev[i]);
+  return done_slices;
 }
 
 // ------------------------------------------------------------------ polynomial monomial NDPOLY (poly.hip)

@@ -233,6 +233,10 @@ struct tmhip_ctx {
   int opt_eig_cheb;         // degree of the Chebyshev filter of the lowest end (0: none)
   int opt_eig_restarts;     // > 0: a run ends after that many Lanczos cycles (the drop-in's max_iterations); 0 (default): only max_apps bounds it
   int opt_eig_fused;        // 1 (default): eig_dots / eig_project / basis_rotate, coefficients on the device; 0: the same algorithm on the singles of linalg.hip
+  void *laph;               // the LapH eigensystem (laph.hip): basis and work colour vectors, block sums, the filter interval; allocated on first use
+  int opt_laph_basis;       // m: basis vectors of a cycle of tmhip_laph_eigensystem, nev + 2 <= m <= TMHIP_LAPH_MAX_BASIS; 0 (default): nev + 32, at most the maximum
+  int opt_laph_cheb;        // degree of its Chebyshev filter (0: none)
+  int opt_laph_fused;       // 1 (default): the reducing and the filter form of the Laplacian are one stencil launch; 0: the plain operator and a pass of its own
 };
 
 // N is a site count of a one-parity field: 0 is a legal empty loop in the reference (linalg/*.c), anything outside [0, V/2] would
@@ -450,6 +454,7 @@ void tmhip_flow_destroy(tmhip_ctx *ctx); // flow.hip: the buffers of a gradient 
 void tmhip_meas_destroy(tmhip_ctx *ctx); // meas.hip: the reduction buffers of the online measurements
 void tmhip_bicg_destroy(tmhip_ctx *ctx); // bicgstab.hip: work fields and state of BiCGstab
 void tmhip_eig_destroy(tmhip_ctx *ctx);  // eig.hip: basis, work vectors and buffers of the eigensolver
+void tmhip_laph_destroy(tmhip_ctx *ctx); // laph.hip: basis, work colour vectors and buffers of the LapH eigensystem
 // launch geometry shared by linalg.hip and cg.hip
 #define LA_BS 256
 #define LA_UNROLL 4

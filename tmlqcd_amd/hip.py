@@ -266,6 +266,17 @@ def load_library():
         "tmhip_eig_project": [vp, i, C.POINTER(vp), C.POINTER(vp), vp, vp, pd, i, pd],
         "tmhip_basis_rotate": [vp, i, i, C.POINTER(vp), C.POINTER(vp), pd, i],
         "tmhip_eig_small": [i, pd, pd],
+        "tmhip_cvfield_alloc": [vp, C.POINTER(vp)], "tmhip_cvfield_upload": [vp, vp, vp], "tmhip_cvfield_download": [vp, vp, vp],
+        "tmhip_cvfield_zero": [vp, vp], "tmhip_cvfield_upload_slices": [vp, vp, vp, i, i], "tmhip_cvfield_download_slices": [vp, vp, vp, i, i],
+        "tmhip_laph_apply": [vp, vp, vp, i, i], "tmhip_laph_apply_dot": [vp, vp, vp, i, i, pd],
+        "tmhip_laph_apply_filter": [vp, vp, vp, vp, i, i, pd],
+        "tmhip_laph_dots": [vp, i, C.POINTER(vp), vp, i, i, C.POINTER(i), pd],
+        "tmhip_laph_project": [vp, i, C.POINTER(vp), vp, pd, i, i, C.POINTER(i), pd],
+        "tmhip_laph_normalise": [vp, vp, vp, i, i, C.POINTER(i), pd],
+        "tmhip_laph_rotate": [vp, i, i, C.POINTER(vp), pd, i, i, C.POINTER(i)],
+        "tmhip_laph_set_interval": [vp, d, d], "tmhip_laph_timing": [vp, pd],
+        "tmhip_laph_eigensystem": [vp, i, i, i, d, i, C.POINTER(vp), pd, pd, C.POINTER(i), C.POINTER(i)],
+        "tmhip_laph_write": [vp, C.c_char_p, i, i, i, i, C.POINTER(vp), pd],
         "tmhip_get_option": [vp, C.c_char_p, C.POINTER(i)],
     }
     for name, args in sig.items():
@@ -276,6 +287,8 @@ def load_library():
     lib.tmhip_destroy.restype = None
     lib.tmhip_field_free.argtypes = [vp, vp]
     lib.tmhip_field_free.restype = None
+    lib.tmhip_cvfield_free.argtypes = [vp, vp]
+    lib.tmhip_cvfield_free.restype = None
     lib.tmhip_field_even.argtypes = [vp]
     lib.tmhip_field_even.restype = vp
     lib.tmhip_field_odd.argtypes = [vp]
@@ -395,6 +408,40 @@ class Field:
         self.h = None
 
 
+class CvField:
+    """A device-resident colour-vector field (opaque handle): T x LX LY LZ sites of three complex doubles, the reference's
+    su3_vector [T][SPACEVOLUME]; host arrays are float64 [T][SPACEVOLUME][3][2]."""
+
+    def __init__(self, lat):
+        self.lat = lat
+        h = C.c_void_p()
+        _ck(lat.lib.tmhip_cvfield_alloc(lat.h, C.byref(h)), "tmhip_cvfield_alloc")
+        self.h = h
+
+    def _shape(self):
+        return (self.lat.T, self.lat.V // self.lat.T, 3, 2)
+
+    def upload(self, host):
+        if host.shape != self._shape():
+            raise TmHipError("colour-vector fields take float64 [T][SPACEVOLUME][3][2] arrays, got %s" % (host.shape,))
+        _ck(self.lat.lib.tmhip_cvfield_upload(self.lat.h, self.h, _hp(host)), "tmhip_cvfield_upload")
+        return self
+
+    def download(self):
+        out = np.empty(self._shape(), dtype=np.float64)
+        _ck(self.lat.lib.tmhip_cvfield_download(self.lat.h, self.h, _hp(out)), "tmhip_cvfield_download")
+        return out
+
+    def zero(self):
+        _ck(self.lat.lib.tmhip_cvfield_zero(self.lat.h, self.h), "tmhip_cvfield_zero")
+        return self
+
+    def free(self):
+        if self.h is not None and self.lat.h is not None:
+            self.lat.lib.tmhip_cvfield_free(self.lat.h, self.h)
+        self.h = None
+
+
 class Lattice:
     """One rank's lattice on one MI355X: context + operators, mirroring the reference's names."""
 
@@ -445,7 +492,8 @@ class Lattice:
         _ck(self.lib.tmhip_set_option(self.h, name.encode(), int(value)), "tmhip_set_option")
 
     def get_option(self, name):
-        """the value an option has now (the eigensolver's options: "eig_basis", "eig_cheb", "eig_fused", "eig_restarts")"""
+        """the value an option has now (the eigensolvers' options: "eig_basis", "eig_cheb", "eig_fused", "eig_restarts", "laph_basis",
+        "laph_cheb", "laph_fused")"""
         out = C.c_int()
         _ck(self.lib.tmhip_get_option(self.h, name.encode(), C.byref(out)), "tmhip_get_option")
         return out.value
@@ -1241,6 +1289,130 @@ class Lattice:
     def eigenvalues_nd(self, nev, which="lowest", prec=1e-7, max_apps=5000, op="Qtm_pm_ndpsi", vectors=False, start=None, cheb=None):
         """The same for the doublet operators; vectors and start are (up, dn) pairs."""
         return self._eig(True, op, None, nev, which, prec, max_apps, vectors, start, cheb)
+
+    # --- LapH eigensystem: the 3D Laplacian of jacobi.c on all time-slices (LapH_ev.c, solver/eigenvalues_Jacobi.c; laph.hip) ---
+    def cvfield(self, host=None):
+        f = CvField(self)
+        if host is not None:
+            f.upload(host)
+        return f
+
+    def _slices(self, t0, nt):
+        return t0, (self.T - t0 if nt is None else nt)
+
+    @staticmethod
+    def _flags(active, nt):
+        """None, or nt flags -> (keep-alive, pointer)"""
+        if active is None:
+            return None, None
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        if a.shape != (nt,):
+            raise TmHipError("active: one flag per time-slice of the range")
+        return a, a.ctypes.data_as(C.POINTER(C.c_int))
+
+    def laph_apply(self, out, inp, t0=0, nt=None, dot=False, coef=None, prev=None):
+        """out[t] = Jacobi(in[t], t) for t0 <= t < t0 + nt in one launch.  dot: returns the complex <in, out> of every slice from the
+        same pass.  coef [nt][3]: out = c1 (A in) + c2 in + c3 prev instead, the Chebyshev step (prev None: c3 is not read)."""
+        t0, nt = self._slices(t0, nt)
+        pd = C.POINTER(C.c_double)
+        if coef is not None:
+            cf = np.ascontiguousarray(coef, dtype=np.float64)
+            if cf.shape != (nt, 3):
+                raise TmHipError("laph_apply: coef must be [nt = %d][3]" % nt)
+            _ck(self.lib.tmhip_laph_apply_filter(self.h, out.h, inp.h, prev.h if prev is not None else None, t0, nt, cf.ctypes.data_as(pd)), "laph_apply_filter")
+            return None
+        if dot:
+            d = np.zeros(nt, dtype=np.complex128)
+            _ck(self.lib.tmhip_laph_apply_dot(self.h, out.h, inp.h, t0, nt, d.view(np.float64).ctypes.data_as(pd)), "laph_apply_dot")
+            return d
+        _ck(self.lib.tmhip_laph_apply(self.h, out.h, inp.h, t0, nt), "laph_apply")
+        return None
+
+    def laph_dots(self, vs, w, t0=0, nt=None, active=None, out=None):
+        """<v_i, w> per slice as a complex128 [nt][nv] array (`out`: filled in place; the rows of frozen slices are left alone)"""
+        t0, nt = self._slices(t0, nt)
+        keep, pa = self._flags(active, nt)
+        if out is None:
+            out = np.zeros((nt, len(vs)), dtype=np.complex128)
+        if out.shape != (nt, len(vs)) or out.dtype != np.complex128 or not out.flags.c_contiguous:
+            raise TmHipError("laph_dots: out must be a C-contiguous complex128 [nt][nv] array")
+        _ck(self.lib.tmhip_laph_dots(self.h, len(vs), self._handles(vs), w.h, t0, nt, pa, out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))), "laph_dots")
+        return out
+
+    def laph_project(self, vs, w, h, t0=0, nt=None, active=None, out=None):
+        """w[t] -= sum_i h[t][i] v_i[t], ascending i; returns |w[t]|^2 of the result, float64 [nt]"""
+        t0, nt = self._slices(t0, nt)
+        keep, pa = self._flags(active, nt)
+        hc = np.ascontiguousarray(h, dtype=np.complex128)
+        if hc.shape != (nt, len(vs)):
+            raise TmHipError("laph_project: h must be [nt][nv]")
+        if out is None:
+            out = np.zeros(nt)
+        pd = C.POINTER(C.c_double)
+        _ck(self.lib.tmhip_laph_project(self.h, len(vs), self._handles(vs) if len(vs) else None, w.h, hc.view(np.float64).ctypes.data_as(pd), t0, nt, pa,
+                                        out.ctypes.data_as(pd)), "laph_project")
+        return out
+
+    def laph_normalise(self, out, inp, t0=0, nt=None, active=None, sqnorm=None):
+        """out[t] = in[t] / |in[t]|; returns |in[t]|^2, float64 [nt]"""
+        t0, nt = self._slices(t0, nt)
+        keep, pa = self._flags(active, nt)
+        if sqnorm is None:
+            sqnorm = np.zeros(nt)
+        _ck(self.lib.tmhip_laph_normalise(self.h, out.h, inp.h, t0, nt, pa, sqnorm.ctypes.data_as(C.POINTER(C.c_double))), "laph_normalise")
+        return sqnorm
+
+    def laph_rotate(self, vs, Y, t0=0, nt=None, active=None):
+        """V[t][:, 0:k] = V[t][:, 0:n] Y[t] in place; Y real [nt][n][k]"""
+        t0, nt = self._slices(t0, nt)
+        keep, pa = self._flags(active, nt)
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 3 or Y.shape[0] != nt or Y.shape[1] != len(vs):
+            raise TmHipError("laph_rotate: Y must be [nt = %d][n = %d][k]" % (nt, len(vs)))
+        _ck(self.lib.tmhip_laph_rotate(self.h, Y.shape[1], Y.shape[2], self._handles(vs), Y.ctypes.data_as(C.POINTER(C.c_double)), t0, nt, pa), "laph_rotate")
+
+    def laph_set_interval(self, lo=0.0, hi=0.0):
+        """the interval of the Chebyshev filter ("laph_cheb") of every slice; 0, 0 = per slice from one unfiltered cycle"""
+        _ck(self.lib.tmhip_laph_set_interval(self.h, lo, hi), "laph_set_interval")
+
+    def laph_timing(self):
+        """(host seconds in the small eigenproblems, host seconds in all) of the last laph_eigensystem"""
+        out = (C.c_double * 2)()
+        _ck(self.lib.tmhip_laph_timing(self.h, out), "laph_timing")
+        return out[0], out[1]
+
+    def laph_eigensystem(self, nev, prec=1e-8, max_apps=5000, t0=0, nt=None, vectors=False, start=None):
+        """The nev lowest eigenpairs of the 3D Laplacian on every slice of the range -> {"evals" [nt][nev], "resid" [nt][nev],
+        "converged" [nt], "apps" [nt][, "vectors": nev colour-vector fields, the caller's to free]}.  start: a host colour-vector
+        array, the start vector of every slice where its norm is non-zero."""
+        t0, nt = self._slices(t0, nt)
+        fields = None
+        if vectors or start is not None:
+            fields = [self.cvfield() for _ in range(nev)]
+            if start is not None:
+                fields[0].upload(start)
+        ev, rs = np.zeros((nt, nev)), np.zeros((nt, nev))
+        conv, apps = np.zeros(nt, dtype=np.int32), np.zeros(nt, dtype=np.int32)
+        pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        rc = self.lib.tmhip_laph_eigensystem(self.h, t0, nt, nev, prec, max_apps, self._handles(fields) if fields else None, ev.ctypes.data_as(pd),
+                                             rs.ctypes.data_as(pd), conv.ctypes.data_as(pi), apps.ctypes.data_as(pi))
+        if fields and (rc != 0 or not vectors):
+            for f in fields:
+                f.free()
+        _ck(rc, "laph_eigensystem")
+        out = {"evals": ev, "resid": rs, "converged": conv, "apps": apps}
+        if vectors:
+            out["vectors"] = fields
+        return out
+
+    def laph_write(self, directory, nstore, vectors, evals, t0=0, nt=None):
+        """eigenvalues.TTT.NNNN and eigenvector.EEE.TTT.NNNN of eigenvalues_Jacobi.c:176-209 into `directory`"""
+        t0, nt = self._slices(t0, nt)
+        ev = np.ascontiguousarray(evals, dtype=np.float64)
+        if ev.shape != (nt, len(vectors)):
+            raise TmHipError("laph_write: evals must be [nt][nev]")
+        _ck(self.lib.tmhip_laph_write(self.h, str(directory).encode(), nstore, t0, nt, len(vectors), self._handles(vectors),
+                                      ev.ctypes.data_as(C.POINTER(C.c_double))), "laph_write")
 
     # --- non-degenerate doublet (operator/tm_operators_nd.c; strange = up = first field of a pair) ---
     def set_nd(self, mubar, epsbar, invmaxev=1.0):

@@ -7,7 +7,7 @@ compiler's remarks next to the object (lib/<name>.ru.txt).  This script parses t
 spills (scratch > 0) or drops below three waves per SIMD -- the split path once lost 40 % to a spill nobody looked at
 (profiles/r03_split_forms.md, last paragraph of `split_early`).
 
-    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/bicgstab.ru.txt lib/eig.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/nd32.ru.txt lib/poly.ru.txt
+    check_resources.py [--table OUT.txt] lib/linalg.ru.txt lib/bicgstab.ru.txt lib/eig.ru.txt lib/laph.ru.txt lib/hopping.ru.txt lib/hopping32.ru.txt lib/clover.ru.txt lib/gauge.ru.txt lib/flow.ru.txt lib/meas.ru.txt lib/rational.ru.txt lib/nd.ru.txt lib/nd32.ru.txt lib/poly.ru.txt
 """
 import re
 import subprocess
@@ -97,6 +97,17 @@ RULES = [
     (r"^void eighip::basis_rotate_kernel<16>", "basis rotation, 16 columns", 6),
     (r"^void eighip::basis_rotate_kernel<32>", "basis rotation, 32 columns", 3),
     (r"^void eighip::basis_rotate_kernel<64>", "basis rotation, 64 columns", 1),
+    # the LapH eigensystem (laph.hip): the 3D Laplacian on colour vectors holds one link and two colour vectors per site -- no scratch,
+    # the stencils' three waves per SIMD in all three forms; its dots, projection, scaling and combination are the streams of eig.hip with
+    # a slice dimension -- no scratch, eight waves per SIMD; the final pass, the fill and the layout
+    # change hold a handful of registers: eight waves as well.  The rotation parks its n inputs in LDS (n x 512 bytes per one-wave block: at
+    # n = 24 that alone admits three waves per SIMD) and keeps 16 real accumulators next to a row of Y in scalar registers: no scratch,
+    # four waves per SIMD is more than its LDS ever lets in
+    (r"^void laphhip::laph_kernel<[012]>", "3D Laplacian", 3),
+    (r"^(void )?laphhip::(laph_dots_kernel|laph_project_kernel|laph_scale_kernel|laph_comb_kernel)", "LapH streams", 8),
+    (r"^(void )?laphhip::(laph_final_kernel|laph_fill_kernel)", "LapH final pass, fill", 8),
+    (r"^(void )?laphhip::laph_rotate_kernel", "LapH rotation", 4),
+    (r"^void laphhip::cv_layout_kernel<(true|false)>", "colour-vector layout", 8),
     # the four-term combination of the polynomial monomial (poly.hip), both flavours of a doublet per launch: a stream like the ones above
     (r"^(void )?polyhip::comb4_kernel", "four-term combination", 8),
     # propagator / source records (spinor_io.hip): byte work through an LDS tile, a handful of registers; "no scratch" is the floor
